@@ -12,11 +12,16 @@ frames are gathered to rank 0 over RCCL inside the timed region.
 already running under a launcher (WORLD_SIZE unset); under `python -m torch.distributed.run ... bench.py
 --gpus N` it reads RANK / LOCAL_RANK / WORLD_SIZE as given.
 
-Prints ONE JSON line (rank 0):
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: set-up, W untimed and K timed steps, the
+outputs of the last timed step if `--dump-outputs DIR` is given, and ONE JSON line (rank 0) with `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the workload's `config`; the timed steps run without per-kernel events or power
+sampling.  `--full` adds every other record below (the timed steps then carry the per-kernel HIP events and the power / clock
+sampler, as the records need):
   value / ms_per_step   the headline, at REFERENCE precision (the reference computes in fp32): `--precision f16x3` (default) =
                         split-f16, fp32-grade — every operand hi + lo in f16, three f16 MFMAs per product, fp32 accumulate —
-                        admitted IN THE SAME RUN by `cpu_baseline.parity_vs_oracle` and by `config.fp32_grade_check` (the fine
-                        network's 9 raw channels, split-f16 vs the exact-fp32 MFMA kernel on the same samples);
+                        admitted (with --full) IN THE SAME RUN by `cpu_baseline.parity_vs_oracle` and by `config.fp32_grade_check`
+                        (the fine network's 9 raw channels, split-f16 vs the exact-fp32 MFMA kernel on the same samples);
+  ranks                 per-rank render / gather seconds, mean package power and shader clock over the timed steps;
   precisions            the same workload on the other arithmetic modes — "f32" (exact fp32 MFMA), "f16" (f16 MFMA inputs:
                         narrower than the reference, the fast option) and split-f16 fine + f16 coarse — each with value,
                         ms_per_step, the fine kernel's roofline against ITS peak, and parity vs the oracle;
@@ -29,8 +34,12 @@ Prints ONE JSON line (rank 0):
   cpu_baseline          the oracle (torch-CPU port of the reference path) on this box's host cores as SURVEY §8(d) defines it:
                         median of 3 runs over a 16,384-ray subset of the judged frame at the fastest thread count of a sweep,
                         plus one full 160x120 frame at 32+64 samples (BASELINE configs[0] shape) (rank 0, N = 1 only).
+
+`--dump-outputs DIR` writes what the timed path returned in its last step as float32 arrays (see dump_outputs); the inputs
+(weights, poses, histogram) are seeded, so two runs with the same arguments render the same frames.
 """
 import argparse
+import contextlib
 import ctypes
 import json
 import os
@@ -414,9 +423,10 @@ def per_rank_record(stats, gathered_bytes):
     return rec
 
 
-def timed_render(E, lib, precision, poses, hist, rgbs, disps, acc, K, Wm, world=1, gather=None):
+def timed_render(E, lib, precision, poses, hist, rgbs, disps, acc, K, Wm, world=1, gather=None, telemetry=True):
     """Wm untimed + K timed frames; returns (seconds for the K frames, max over ranks; per-kernel HIP-event averages; [world, 5]
-    per-rank record: this rank's render seconds, gather seconds, mean package power, mean shader clock, sample count)."""
+    per-rank record: this rank's render seconds, gather seconds, mean package power, mean shader clock, sample count).
+    telemetry=False (a plain run): no per-kernel events and no power / clock sampler around the timed frames -> (seconds, None, None)."""
     from dfnet_amd import dist as ddist
     nf = poses.shape[0]
 
@@ -430,9 +440,10 @@ def timed_render(E, lib, precision, poses, hist, rgbs, disps, acc, K, Wm, world=
         gather()
     torch.cuda.synchronize()
     ddist.barrier()
-    lib.dfn_profile_enable(1)
-    torch.cuda.synchronize()
-    with GpuSampler(rgbs.device.index or 0) as smp:
+    if telemetry:
+        lib.dfn_profile_enable(1)
+        torch.cuda.synchronize()
+    with GpuSampler(rgbs.device.index or 0) if telemetry else contextlib.nullcontext() as smp:
         t0 = time.perf_counter()
         for k in range(K):
             step(k)
@@ -445,11 +456,28 @@ def timed_render(E, lib, precision, poses, hist, rgbs, disps, acc, K, Wm, world=
         ddist.barrier()
         dt = time.perf_counter() - t0
     dt = ddist.max_over_ranks(dt, rgbs.device)
+    if not telemetry:
+        return dt, None, None
     prof = read_profile(lib)
     lib.dfn_profile_enable(0)
     pw, ck, ns = smp.means()
     stats = ddist.all_gather_floats([t_render, t_gather, pw, ck, ns], rgbs.device)
     return dt, prof, stats
+
+
+DUMP_MAX_RANKS = 12   # 12 x (rgb + disp of a 640x480 frame) + acc = 60 MB, inside the 64 MB an output dump may take
+
+
+def dump_outputs(out_dir, frames, acc, K, world):
+    """--dump-outputs: what the timed path handed its caller in its LAST timed step, as float32 DIR/<name>.npy (rank 0, after the
+    gather): rgb [ranks, H, W, 3] and disp [ranks, H, W] = the frame each rank rendered in that step (the last of its block of
+    the gathered frames; the first DUMP_MAX_RANKS ranks), acc [H, W] = rank 0's accumulated opacity of that step (render_image's
+    third output, not gathered).  `frames` = the [n_frames, ...] rgb and disp tensors that hold every rank's block."""
+    from dfnet_amd import dist as ddist
+    os.makedirs(out_dir, exist_ok=True)
+    last = [ddist.frame_block(K * world, r, world)[1] - 1 for r in range(min(world, DUMP_MAX_RANKS))]
+    for name, t in (("rgb", frames[0][last]), ("disp", frames[1][last]), ("acc", acc)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def mlp_roofline(prof, K, precision, value_per_gpu):
@@ -1083,8 +1111,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--precision", default="f16x3", choices=["f16", "f32", "f16x3"],
                     help="arithmetic of the headline value (default: split-f16, fp32-grade = the reference's precision)")
-    ap.add_argument("--cpu-sample", type=int, default=16384, help="rays in the CPU baseline subset (0 = skip the oracle legs)")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (no precisions / hbm / secondary records)")
+    ap.add_argument("--full", action="store_true",
+                    help="every record besides the headline: roofline, per-rank telemetry, CPU baseline, hbm, the other precisions, "
+                         "the secondary workloads (default: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's rgb / disp / acc as DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-sample", type=int, default=16384, help="with --full: rays in the CPU baseline subset (0 = skip the oracle legs)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: headline, roofline and CPU baseline only (no precisions / hbm / secondary records)")
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"], help="torch.distributed backend (default nccl = RCCL)")
     ap.add_argument("--cpu-dry", action="store_true", help="no GPU work: exercise launch + sharding + gather only (CPU tests)")
     ap.add_argument("--cpu-worker", nargs=3, metavar=("MODE", "RAYS", "OUT"), help="internal: the pinned child process of the CPU baseline")
@@ -1124,17 +1157,13 @@ def main():
     def gather():
         ddist.gather_frames_direct([rgbs, disps], n_frames, outs=outs)   # one grouped exchange: every peer sends rgb + disp to rank 0
 
-    dt, prof, stats = timed_render(E, lib, args.precision, poses, hist, rgbs, disps, acc, K, Wm, world, gather)
+    dt, prof, stats = timed_render(E, lib, args.precision, poses, hist, rgbs, disps, acc, K, Wm, world, gather, telemetry=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs or [rgbs, disps], acc, K, world)
 
     if rank == 0:
         rays = H * W
         value = world * K * rays / dt
-        roof = mlp_roofline(prof, K, args.precision, value / world)
-        roof["traffic"] = pmc_traffic("nerfh_fine_kernel", args.precision)
-        roof["traffic_note"] = ("HBM bytes per launch of this precision's instantiation, rocprofv3 PMC (2*FETCH_SIZE + WRITE_SIZE) from "
-                                "profiles/*_pmc_summary*.json; algorithmic bytes per launch = rays * (768 z + 24 o,d + 512 ray-bias + "
-                                "segment composites: 144 at 64-sample segments (f16), 288 at 32-sample segments (f16x3 / f32)); raw "
-                                "(6912 B/ray) stays in registers since compositing is fused")
         line = {
             "metric": "rendered rays/sec (64+128 samples, 640x480)",
             "value": value, "unit": "rays/s", "n_gpus": world, "steps": K, "warmup": Wm,
@@ -1143,14 +1172,21 @@ def main():
             "config": {"workload": "BASELINE configs[1]: synthetic random-weight NeRF-H (D=8, W=128), 640x480, "
                                    "64+128 samples, test-time render_image, 1 frame per step per GPU",
                        "rays_per_step_per_gpu": rays, "precision": PREC_TEXT[args.precision],
-                       "precision_gate": PREC_GATE[args.precision],
                        "parallelism": f"frames sharded over {world} GPU(s), gather at end",
                        "collectives": ("one grouped RCCL send / receive batch of rgb + disp into rank 0's final tensors, inside the timed region" + (" (forced at world size 1: padded gather)" if world == 1 else ""))
                                       if ddist.active() else "none (one rank)"},
-            "roofline": roof,
-            "ranks": per_rank_record(stats, ddist.gathered_bytes([rgbs, disps], n_frames)),
         }
-        if world == 1 and not args.no_extras:
+        if args.full:
+            roof = mlp_roofline(prof, K, args.precision, value / world)
+            roof["traffic"] = pmc_traffic("nerfh_fine_kernel", args.precision)
+            roof["traffic_note"] = ("HBM bytes per launch of this precision's instantiation, rocprofv3 PMC (2*FETCH_SIZE + WRITE_SIZE) from "
+                                    "profiles/*_pmc_summary*.json; algorithmic bytes per launch = rays * (768 z + 24 o,d + 512 ray-bias + "
+                                    "segment composites: 144 at 64-sample segments (f16), 288 at 32-sample segments (f16x3 / f32)); raw "
+                                    "(6912 B/ray) stays in registers since compositing is fused")
+            line["config"]["precision_gate"] = PREC_GATE[args.precision]
+            line["roofline"] = roof
+            line["ranks"] = per_rank_record(stats, ddist.gathered_bytes([rgbs, disps], n_frames))
+        if args.full and world == 1 and not args.no_extras:
             sus = sustained_mfma(lib)
             SUSTAINED.update(sus)
             roof["sustained_mfma"] = sus
@@ -1205,7 +1241,7 @@ def main():
                 except Exception as e:  # a failing secondary must not lose the headline line
                     sec[name] = {"error": f"{type(e).__name__}: {e}"}
             line["secondary"] = sec
-        elif world == 1 and args.cpu_sample > 0:
+        elif args.full and world == 1 and args.cpu_sample > 0:
             rec, ref_pack = cpu_baseline(args.cpu_sample)
             rec["parity_vs_oracle"] = parity(E, ref_pack[0], ref_pack[1], args.precision, dev)
             line["cpu_baseline"] = rec

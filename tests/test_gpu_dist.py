@@ -56,7 +56,7 @@ def test_rccl_collectives_forced_at_world1(tmp_path):
 def test_bench_under_torchrun_with_rccl_gather(tmp_path):
     """bench.py exactly as the driver launches it for N > 1 (torch.distributed.run, nccl), here with one rank: the frames go
     through the RCCL gather inside the timed region."""
-    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--no-extras"])
+    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--cpu-sample", "0", "--no-extras"])
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["steps"] == 2 and line["value"] > 1e5
@@ -66,6 +66,34 @@ def test_bench_under_torchrun_with_rccl_gather(tmp_path):
     assert len(ranks["render_s"]["per_rank"]) == 1 and ranks["render_s"]["max"] > 0 and ranks["gather_s"]["max"] >= 0
     assert ranks["gathered_bytes"] == 0   # one rank: every frame is the root's own
     assert ranks["samples_per_rank"][0] > 0 and 100 < ranks["power_w"]["mean"] < 1600 and 300 < ranks["sclk_mhz"]["mean"] < 2600, ranks
+
+
+def test_bench_plain_line_and_output_dump(tmp_path):
+    """A plain bench run: the headline line alone (no --full records), and --dump-outputs writes what the timed path rendered in its
+    LAST timed step — bit for bit the frame render_image gives for the same seeded weights and pose in this process."""
+    import numpy as np
+    import torch
+    from dfnet_amd import engine as eng, synthetic as syn
+    K = 3
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == K and line["warmup"] == 1 and line["dtype"] == "f16x3" and line["unit"] == "rays/s"
+    assert line["higher_is_better"] is True and line["value"] > 1e5
+    assert abs(line["ms_per_step"] - 640 * 480 / line["value"] * 1e3) < 1e-6 * line["ms_per_step"]
+    assert not {"roofline", "ranks", "cpu_baseline", "precisions", "hbm", "secondary"} & set(line), sorted(line)
+    got = {k: np.load(os.path.join(tmp_path, k + ".npy")) for k in ("rgb", "disp", "acc")}
+    assert got["rgb"].shape == (1, 480, 640, 3) and got["disp"].shape == (1, 480, 640) and got["acc"].shape == (480, 640)
+    assert all(v.dtype == np.float32 for v in got.values())
+    dev = torch.device("cuda:0")
+    E = eng.NerfHEngine(precision="f16x3").load_numpy(*syn.nerfh_weights(0))
+    want = E.render_image(torch.from_numpy(syn.orbit_pose(K - 1, K)).to(dev), 480, 640, 585.0, torch.from_numpy(syn.HIST_IDX).to(dev),
+                          64, 128, 0.0, 2.5, precision="f16x3")
+    for k, w in zip(("rgb", "disp", "acc"), want):
+        np.testing.assert_array_equal(got[k].reshape(w.shape), w.cpu().numpy(), err_msg=k)
 
 
 def test_row_bands_equal_the_full_frame_bit_for_bit():

@@ -450,6 +450,29 @@ def test_cambridge_front_end(tmp_path):
     assert hwf2 == hwf and (near, far) == (0.0, 10.0) and tr.dataset.pose_scale == 0.3 and len(te) == 3
 
 
+def test_bench_dump_outputs_takes_every_ranks_last_frame(tmp_path):
+    """bench.py --dump-outputs on rank 0 after the gather: the frame each rank rendered in the last timed step (the last of its
+    block of the gathered [K * world, ...] tensors), capped at DUMP_MAX_RANKS ranks, as float32 .npy files."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    K, h, w = 3, 4, 5
+    for world in (1, 2, bench.DUMP_MAX_RANKS + 2):
+        n = K * world
+        rgb = torch.arange(n, dtype=torch.float32)[:, None, None, None].expand(n, h, w, 3).contiguous()
+        disp = rgb[..., 0] + 0.5
+        acc = torch.full((h, w), 0.25, dtype=torch.float64)
+        out = tmp_path / str(world)
+        bench.dump_outputs(str(out), [rgb, disp], acc, K, world)
+        got = {k: np.load(out / (k + ".npy")) for k in ("rgb", "disp", "acc")}
+        last = [K * r + K - 1 for r in range(min(world, bench.DUMP_MAX_RANKS))]
+        assert all(v.dtype == np.float32 for v in got.values())
+        assert got["rgb"].shape == (len(last), h, w, 3) and got["rgb"][:, 0, 0, 0].tolist() == last
+        assert got["disp"][:, 0, 0].tolist() == [f + 0.5 for f in last] and got["acc"].shape == (h, w)
+    assert bench.DUMP_MAX_RANKS * 4 * (480 * 640 * 4) + 480 * 640 * 4 <= 64 * 2 ** 20
+
+
 @pytest.mark.parametrize("launcher", ["self", "torchrun"])
 def test_bench_entry_point_two_ranks_gloo(launcher):
     """`python bench.py --gpus 2` must start its own two ranks (the form the driver uses on an 8-GPU node), and must also

@@ -6,6 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-r06}
 cd $R
 mkdir -p gpurun_out
+OUT=$_   # the output directory just made
 if [[ " $* " != *" notest "* ]]; then
   timeout 2400 python -m pytest tests -x -q -m gpu > gpurun_out/pytest_gpu.log 2>&1; echo "pytest rc=$?"
   tail -6 gpurun_out/pytest_gpu.log
@@ -14,12 +15,12 @@ if [[ " $* " != *" notest "* ]]; then
   timeout 900 python -m pytest tests/test_gpu_nerfh.py tests/test_gpu_cli.py -q -m gpu -s -k "trained" 2>&1 | grep -oE "(trained (stages|weights|checkpoint)|create_nerf engine).*" > gpurun_out/trained_parity.log
   wc -l gpurun_out/trained_parity.log
 fi
-timeout 1500 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err; echo "bench rc=$?"; cut -c1-3000 gpurun_out/bench.json; tail -3 gpurun_out/bench.err
+timeout 1500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-3000 $OUT/bench.json; tail -3 $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 # rocprofv3 kernel stats + three PMC passes of the SAME command per arithmetic mode (the headline's f16x3, exact f32, f16)
 for PREC in f16x3 f32 f16; do
   rm -rf $R/gpurun_out/prof_$PREC $R/gpurun_out/pmc_$PREC
-  CMD="python $R/bench.py --precision $PREC --steps 3 --warmup 1 --cpu-sample 0 --no-extras"
+  CMD="python $R/bench.py --precision $PREC --steps 3 --warmup 1 --full --cpu-sample 0 --no-extras"
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$PREC -o $TAG -- $CMD > $R/gpurun_out/prof_bench_$PREC.json 2> $R/gpurun_out/prof_$PREC.err; echo "rocprof $PREC rc=$?"
   head -6 $R/gpurun_out/prof_$PREC/${TAG}_kernel_stats.csv | cut -c1-170
   if [[ " $* " != *" nopmc "* ]]; then
