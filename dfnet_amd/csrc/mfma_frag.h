@@ -15,6 +15,7 @@ template <> struct FragOf<PrecF16> { using type = half8; using elem = _Float16; 
 template <> struct FragOf<PrecF32> { using type = float; using elem = float; };
 struct half8x2 { half8 hi, lo; };
 template <> struct FragOf<PrecX3> { using type = half8x2; using elem = float; };
+template <> struct FragOf<PrecX3M16> { using type = half8x2; using elem = float; };   // (nerfh_layout.h; no mfma<> form: nerfh_mlp_core.h)
 
 // D = A(32 x k) * B(k x 32) + C; A/B lanes: row/col = lane&31, k-half = lane>>5.
 template <class P>

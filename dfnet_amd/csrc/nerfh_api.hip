@@ -206,6 +206,18 @@ struct Packer {
     if (layer == LY_L5) return s < 32 ? pe_xyz_feature(hh, s) : kChXyz + hidden_feature(hh, s - 32);
     return hidden_feature(hh, s);
   }
+  // PrecX3M16: source column of slot s of lane group g (nerfh_layout.h: pe_xyz_feature_m16, hidden_feature_m16)
+  static int col_source_m16(int layer, int g, int s) {
+    if (layer == LY_L1) return pe_xyz_feature_m16(g, s);
+    if (layer == LY_L5) return s < 16 ? pe_xyz_feature_m16(g, s) : kChXyz + hidden_feature_m16(g, s - 16);
+    return hidden_feature_m16(g, s);
+  }
+  // M-blocks whose rows are heads (read back by the kernels) rather than the next layer's operand
+  bool head_block(int layer, int mb) const {
+    return layer == LY_RGB || layer == LY_THEAD || layer == LY_SIG || (layer == LY_FIN && mb == width() / 32);
+  }
+  // PrecX3M16: row of the 32-row M-block's weights behind packed row i (-1 = zero row), see head_row_m16
+  int row_m16(int layer, int mb, int i) const { return head_block(layer, mb) ? head_row_m16(i) : i; }
   // The bias folded per ray (DIR, TE0) is NOT packed into the unit.
   static bool unit_has_bias(int layer) { return layer != LY_DIR && layer != LY_TE0; }
 
@@ -222,6 +234,39 @@ struct Packer {
     float* bias = reinterpret_cast<float*>(base + size_t(group) * KC * 64 * P::kLaneBytes);
     for (int g = 0; g < group; ++g) {
       const int mb = mb0 + g;
+      if constexpr (P::kM16) {
+        // fragment kc = (32-K chunk kc >> 1, 16-row half kc & 1); lane l: row 16 (kc & 1) + (l & 15), slots 8 (kc >> 1) + j of group l >> 4
+        auto source = [&](int i, Mat& m, int& row) {
+          const int ri = row_m16(layer, mb, i);
+          if (ri < 0) { m = Mat(); row = -1; return; }
+          row_source(layer, mb, ri, m, row);
+          if (row >= m.rows) row = -1;
+        };
+        for (int lane = 0; lane < 64; ++lane)
+          for (int kc = 0; kc < KC; ++kc) {
+            Mat m;
+            int row;
+            source(16 * (kc & 1) + (lane & 15), m, row);
+            for (int j = 0; j < 8; ++j) {
+              const int col = col_source_m16(layer, lane >> 4, 8 * (kc >> 1) + j);
+              const float v = (row >= 0 && col >= 0 && col < m.cols) ? m.w[size_t(row) * m.cols + col] : 0.f;
+              Elem* fr = frag + (size_t(g) * KC + kc) * 64 * 16;
+              const Elem hi = Elem(v * wscale);
+              fr[lane * 8 + j] = hi;
+              fr[512 + lane * 8 + j] = Elem(v * wscale - float(hi));
+            }
+          }
+        for (int lg = 0; lg < 4; ++lg)   // bias block [g][ms][r] (load_bias_m16)
+          for (int ms = 0; ms < 2; ++ms)
+            for (int r = 0; r < 4; ++r) {
+              Mat m;
+              int row;
+              source(16 * ms + 4 * lg + r, m, row);
+              const float b = (row >= 0 && unit_has_bias(layer)) ? m.b[row] : 0.f;
+              bias[g * 32 + lg * 8 + ms * 4 + r] = b * wscale * kX3ActScale;
+            }
+        continue;
+      }
       for (int lane = 0; lane < 64; ++lane) {
         const int i = lane & 31, hh = lane >> 5;
         Mat m;
@@ -531,7 +576,8 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
           sexp = sexp < -8 ? -8 : (sexp > 24 ? 24 : sexp);
           pk.wscale = std::ldexp(1.f, sexp);
           n.in_scale = pk.wscale * kX3ActScale;
-          pk.pack<PrecX3>(f, unit_mb<PrecX3>(var), false, blob, tab, l5_unit_mb_p<PrecX3>(unit_mb<PrecX3>(var)));
+          if (var == 4) pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)));
+          else pk.pack<PrecX3>(f, unit_mb<PrecX3>(var), false, blob, tab, l5_unit_mb_p<PrecX3>(unit_mb<PrecX3>(var)));
         }
         int rc = upload(blob.data(), blob.size(), reinterpret_cast<void**>(&n.blob));
         if (rc) return rc;
@@ -680,14 +726,15 @@ static int check_grad_prec(int prec, const char* fn) {
   return DFN_OK;
 }
 
-// Kernel variant: DFN_MLP_VARIANT=0|1|2 (A/B aid, see nerfh_layout.h).
+// Kernel variant: DFN_MLP_VARIANT=0..4 (A/B aid, see nerfh_layout.h).  Default 4: split-f16 on 16x16x32 MFMAs (f16 / exact fp32 run their
+// variant-0 kernels under it); DFN_MLP_VARIANT=0 keeps the 32x32x16 split-f16 kernels.
 static int mlp_variant_128();
 static int mlp_variant_of(dfn_nerfh_t h) { return h->desc.width == kWidth ? mlp_variant_128() : 0; }
 static int mlp_variant_128() {
   static int v = -1;
   if (v < 0) {
     const char* e = getenv("DFN_MLP_VARIANT");
-    v = (e && e[0] >= '0' && e[0] < '0' + kVariants) ? e[0] - '0' : 0;
+    v = (e && e[0] >= '0' && e[0] < '0' + kVariants) ? e[0] - '0' : 4;
   }
   return v;
 }

@@ -83,23 +83,53 @@ DFN_HD constexpr int pe_xyz_feature(int h, int s) {
   return s < 30 ? 3 + 6 * (5 * h + s / 6) + (s % 6) : (s == 30 ? (h ? 2 : 0) : (h ? -1 : 1));
 }
 
+// PrecX3M16: feature held in slot s (0 .. K/4 - 1, s = 8 k32 + j) of lane group g when the vector was produced by M-blocks of a
+// previous layer: rows 16 (j >> 2) + 4 g + (j & 3) of M-block k32.
+DFN_HD constexpr int hidden_feature_m16(int g, int s) { return 32 * (s >> 3) + 16 * ((s & 7) >> 2) + 4 * g + (s & 3); }
+// PrecX3M16 positional-encoding slot map: 16 slots per lane group and point.  Slots 0..11: octaves 2g, 2g+1 (6k'+c sin of coord c,
+// 6k'+3+c cos); slots 12..15 = two (sin, cos) pairs rho = 2g, 2g+1 of the last two octaves (rho < 6: coord rho % 3, octave
+// 8 + rho / 3), group 3 holds the raw coordinates there instead (x, y, z, pad).
+DFN_HD constexpr int pe_xyz_feature_m16(int g, int s) {
+  return s < 12 ? 3 + 6 * (2 * g + s / 6) + (s % 6)
+       : (g == 3 ? (s < 15 ? s - 12 : -1)
+                 : 3 + 6 * (8 + (2 * g + ((s - 12) >> 1)) / 3) + 3 * ((s - 12) & 1) + (2 * g + ((s - 12) >> 1)) % 3);
+}
+// PrecX3M16 head M-blocks: row i (0..31) of the packed block -> row of the 32x32 head block it copies (-1 = zero).  Head value c (the
+// C register of half 0 that carries it in the 32x32 kernels: row mblock_row(0, c)) goes to rows 16 (c >> 2) + 4 g + (c & 3) of lane
+// groups g = 0, 1: fragment q = 2 (c >> 2) + g holds it for the sample of lane 16 g + (l & 15).
+DFN_HD constexpr int head_row_m16(int i) {
+  return ((i >> 2) & 3) < 2 ? (i & 3) + 8 * (i >> 4) : -1;
+}
+
 // Per-precision fragment geometry.
-struct PrecF16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 16; static constexpr bool kSplit = false; };
-struct PrecF32 { static constexpr int kSlotsPerChunk = 1, kLaneBytes = 4; static constexpr bool kSplit = false; };
+struct PrecF16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 16; static constexpr bool kSplit = false, kM16 = false; };
+struct PrecF32 { static constexpr int kSlotsPerChunk = 1, kLaneBytes = 4; static constexpr bool kSplit = false, kM16 = false; };
 // Split-f16: every operand is hi + lo in f16 (hi = f16(x), lo = f16(x - hi)) and a product is accumulated in fp32
 // as hi*hi + hi*lo + lo*hi — three v_mfma_f32_32x32x16_f16 instead of eight v_mfma_f32_32x32x2_f32 per 16
 // contraction elements, fp32-grade results (the dropped lo*lo term is 2^-22 relative).  A fragment = 8 hi + 8 lo
 // halves per lane.  Operands are pre-scaled by powers of two (activations x kX3ActScale, weights x 2^s per
 // network) so the lo parts stay normal f16 numbers; MlpArgs::{in,out}_scale carry the product and its inverse.
-struct PrecX3 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; static constexpr bool kSplit = true; };
+struct PrecX3 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; static constexpr bool kSplit = true, kM16 = false; };
 constexpr float kX3ActScale = 16.f;
+// Split-f16 on v_mfma_f32_16x16x32_f16 (kernel variant 4).  A 32-row M-block is two 16-row halves ms = 0, 1 and a wave's 32 points
+// are two 16-point N-blocks nb = 0, 1.  The array geometry is PrecX3's, only what sits where differs:
+//   - A fragment t = (k32 = kc >> 1, ms = kc & 1) of an M-block: 16 rows x 32 K, lane l holds row 16 ms + (l & 15),
+//     k = 32 k32 + 8 (l >> 4) + j (j = 0..7), hi plane then lo plane (2 KB, lane-linear 16-byte reads, as PrecX3);
+//   - B chunk c = 2 k32 + nb: the 32-K chunk k32 of N-block nb, lane l holds point 16 nb + (l & 15), k as above;
+//   - the f32x16 accumulator of an M-block = four 16x16 C fragments q = 2 ms + nb (registers 4q..4q+3), lane l holding
+//     rows 16 ms + 4 g + r (g = l >> 4, r = 0..3) of point 16 nb + (l & 15).
+// Rows of hidden M-blocks are the layer's output features in order, so two converted C fragments (ms = 0, 1) of one N-block are the
+// next layer's B chunk directly (hidden_feature_m16); head M-blocks duplicate their rows on lane groups 0 and 1 (head_row_m16) so that
+// head value c of sample p lands on lane p of half 0 with one select.
+struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; static constexpr bool kSplit = true, kM16 = true; };
 
 // Kernel variants (nerfh_mlp.hip): workgroup width and staging granularity (M-blocks per unit).
 //   variant 0: 8 waves per workgroup, 1 workgroup per CU, a unit = a whole layer (f16) / one M-block (f32)
 //   variant 1: 4 waves per workgroup, 2 workgroups per CU, a unit = 2 M-blocks (f16) / one M-block (f32)
 //   variant 3: variant 0's geometry without the pipelined epilogue (A/B reference)
 //   variant 2: 4 waves per workgroup x 3 point blocks, 1 workgroup per CU (1 wave per SIMD, 512 VGPRs), unit as variant 0
-constexpr int kVariants = 4;
+//   variant 4: split-f16 as variant 0 on 16x16x32 MFMAs (PrecX3M16); f16 and exact fp32 run their variant-0 kernels
+constexpr int kVariants = 5;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));
 }

@@ -79,19 +79,22 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   stage_prime(st, smem, max_unit_bytes<P>(UMB, W), ring_slots<P, W>());
   for (; tile < n_tiles; tile += gridDim.x) {
     st.more = tile + gridDim.x < n_tiles;
-    float x[NB][3];
+    constexpr int LP = lane_pts<P>(NB);
+    float x[LP][3];
     uint32_t pt[NB];   // launch_one() bounds a launch to < 2^31 points: 32-bit indices (64-bit ones cost 2 registers each and spilled)
     const uint32_t npts = uint32_t(n_pts);
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      pt[nb] = uint32_t(tile) * uint32_t(PPT) + st.wave * (NB * 32) + nb * 32 + p;
-      const uint32_t q = pt[nb] < npts ? pt[nb] : npts - 1;
+    for (int nb = 0; nb < NB; ++nb) pt[nb] = uint32_t(tile) * uint32_t(PPT) + st.wave * (NB * 32) + nb * 32 + p;   // the lane's output
+#pragma unroll
+    for (int n = 0; n < LP; ++n) {   // the lane's MLP inputs (PrecX3M16: point 16 n + (lane & 15) of the wave)
+      const uint32_t pn = P::kM16 ? uint32_t(tile) * uint32_t(PPT) + st.wave * 32 + 16 * n + (st.lane & 15) : pt[n];
+      const uint32_t q = pn < npts ? pn : npts - 1;
       const uint32_t ray = q / uint32_t(a.n_samples);
       const int i = int(q - ray * uint32_t(a.n_samples));
       const float z = coarse_z_at(i, a.n_samples, a.near, a.far, a.lindisp != 0);
 #pragma unroll
       for (int c = 0; c < 3; ++c)
-        x[nb][c] = add_rn(a.rays_o[ray * 3 + c], mul_rn(a.rays_d[ray * 3 + c], z));
+        x[n][c] = add_rn(a.rays_o[ray * 3 + c], mul_rn(a.rays_d[ray * 3 + c], z));
     }
     constexpr bool CY = PIPE && P::kSlotsPerChunk == 8, MERGE = UMB >= 8;
     F hid[NB][chunks_of<P>(W / 2)];
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     trunk<P, UMB, PIPE, FAST, NB, W>(st, smem, x, hid, carry);
     f32x16 head[NB];
     F dummy[NB][chunks_of<P>(16)];
-    const float* const norb[NB] = {};
+    const float* const norb[LP] = {};
     layer<P, UMB, PIPE, NB, chunks_of<P>(W / 2), 0, false, true, false, !MERGE, (CY ? 6 : -1), true, false>(st, smem, hid, dummy, head, norb, carry);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
@@ -113,13 +116,14 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 // DFNet_dm step's 3.7 M points against this kernel's 3.1).
 template <class P, bool FAST, int WAVES, int UMB, int NB, bool PIPE, int W = kWidth, bool MASKS = false>
 __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) void nerfh_fine_kernel(MlpArgs a) {
-  static_assert(!MASKS || (P::kSplit && NB == 1 && WAVES == 8 && W == kWidth), "the sign masks follow the gradient kernel's tile geometry");
+  static_assert(!MASKS || (P::kSplit && !P::kM16 && NB == 1 && WAVES == 8 && W == kWidth), "the sign masks follow the gradient kernel's tile geometry");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int PPT = WAVES * NB * 32;
   constexpr int HC = chunks_of<P>(W / 2), QC = chunks_of<P>(W / 4);
   constexpr int MBW = W / 32, MBQ = W / 64;       // M-blocks of a W-wide / a W/2-wide layer
   constexpr uint32_t USTRIDE = max_unit_bytes<P>(UMB, W);
   constexpr int PF_ROUNDS = (NB * 32 + 63) / 64;  // 64-point rounds of the next-tile input prefetch
+  constexpr int LP = lane_pts<P>(NB);             // points whose inputs a lane carries (PrecX3M16: 16 n + (lane & 15), n = 0, 1)
   using F = typename FragOf<P>::type;
   Stager st;
   st.blob = a.blob; st.tab = a.tab; st.n_units = a.n_units; st.u = 0;
@@ -148,24 +152,24 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   // Tile inputs.  The first tile's are loaded normally; every later tile's are PREFETCHED during the
   // previous tile's small layers with direct-to-LDS loads and only
   // waited for at the end of that tile, so the HBM latency of z / o / d is off the critical path.
-  float zin[NB], znext[NB], oin[NB][3], din[NB][3];
+  float zin[LP], znext[LP], oin[LP][3], din[LP][3];
   // launch_one() guarantees n_pts < 2^31: point / ray indices are 32-bit (as 64-bit values and as per-ray table POINTERS held
   // across the trunk they cost 16 registers at NB = 2 and the f16 kernel spilled them: any scratch use costs this kernel clock)
-  uint32_t pt[NB], ray_of[NB];
+  uint32_t pt[LP], ray_of[LP];
   const uint32_t npts = uint32_t(n_pts);
   auto tile_coords = [&](long long t) {
     uint32_t lp = st.lane;
     asm volatile("" : "+v"(lp));   // the lane's offset inside the tile is formed here (hoisted as a loop invariant, it was spilled)
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      pt[nb] = uint32_t(t) * uint32_t(PPT) + st.wave * (NB * 32) + nb * 32 + (lp & 31);
+    for (int nb = 0; nb < LP; ++nb) {
+      pt[nb] = uint32_t(t) * uint32_t(PPT) + st.wave * (NB * 32) + (P::kM16 ? 16 * nb + (lp & 15) : nb * 32 + (lp & 31));
       const uint32_t q = pt[nb] < npts ? pt[nb] : npts - 1;
       ray_of[nb] = q / uint32_t(a.n_samples);
     }
   };
   tile_coords(tile);
 #pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
+  for (int nb = 0; nb < LP; ++nb) {
     const uint32_t q = pt[nb] < npts ? pt[nb] : npts - 1;
     zin[nb] = a.z[q];
     znext[nb] = a.z[q + 1 < npts ? q + 1 : q];
@@ -174,31 +178,31 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   }
   for (; tile < n_tiles; tile += gridDim.x) {
     st.more = tile + gridDim.x < n_tiles;
-    float x[NB][3];
-    uint32_t pt_cur[NB], ray_cur[NB];
+    float x[LP][3];
+    uint32_t pt_cur[LP], ray_cur[LP];
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
+    for (int nb = 0; nb < LP; ++nb) {
       pt_cur[nb] = pt[nb];
       ray_cur[nb] = ray_of[nb];
 #pragma unroll
       for (int c = 0; c < 3; ++c) x[nb][c] = add_rn(oin[nb][c], mul_rn(din[nb][c], zin[nb]));
     }
     // per-ray table rows: the pointers are formed where they are used (opaque ray index: not hoisted above the trunk)
-    auto ray_table = [&](const float* (&rb)[NB], int half_table) {
+    auto ray_table = [&](const float* (&rb)[LP], int half_table) {
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
+      for (int nb = 0; nb < LP; ++nb) {
         uint32_t r = ray_cur[nb];
         asm volatile("" : "+v"(r));
         rb[nb] = a.ray_bias + (size_t)r * ray_bias_floats(W) + half_table * (ray_bias_floats(W) / 2);
       }
     };
-    const float* const norb[NB] = {};
+    const float* const norb[LP] = {};
     F hid[NB][HC];
 #ifdef DFN_TIMING
     {
       const unsigned long long c0 = __builtin_amdgcn_s_memtime();
       float keep = 0.f;
-      for (int nb = 0; nb < NB; ++nb) keep += x[nb][0] + x[nb][1] + x[nb][2];
+      for (int nb = 0; nb < LP; ++nb) keep += x[nb][0] + x[nb][1] + x[nb][2];
       asm volatile("" ::"v"(keep));   // inputs have arrived
       t_pro += __builtin_amdgcn_s_memtime() - c0;
     }
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     // dir_encoding (per-ray bias = b + W[:,128:] [pe_dir, a]) -> static_rgb
     {
       F de[NB][QC], dummy[NB][chunks_of<P>(16)];
-      const float* rb_dir[NB];
+      const float* rb_dir[LP];
       ray_table(rb_dir, 0);
       layer<P, UMB, PIPE, NB, HC, MBQ, true, false, true, true, -1, true, CY>(st, smem, fin, de, head, rb_dir, carry);
       layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE, (CY ? 2 : -1), true, false>(st, smem, de, dummy, head, norb, carry);
@@ -249,7 +253,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     // transient branch
     {
       F t0[NB][QC], t1[NB][QC], dummy[NB][chunks_of<P>(16)];
-      const float* rb_tr[NB];
+      const float* rb_tr[LP];
       ray_table(rb_tr, 1);
       layer<P, UMB, PIPE, NB, HC, MBQ, true, false, true, true, -1, true, CY>(st, smem, fin, t0, head, rb_tr, carry);
       if (st.more) {
@@ -288,6 +292,21 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
         o[nb][8] = head_softplus<P, FAST>(head[nb][4]);  // C register 4 of half 0 = row 8 = transient_beta
       }
     }
+    // the lane's own sample (sample p on lane p of half 0, as the heads): PrecX3M16 lane 16 g + (l & 15) carries it as point n = g & 1
+    uint32_t pt_own[NB], ray_own[NB];
+    float z_own[NB], zn_own[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      if constexpr (P::kM16) {
+        const bool n1 = (st.lane & 16) != 0;
+        pt_own[nb] = n1 ? pt_cur[1] : pt_cur[0];
+        ray_own[nb] = n1 ? ray_cur[1] : ray_cur[0];
+        z_own[nb] = n1 ? zin[1] : zin[0];
+        zn_own[nb] = n1 ? znext[1] : znext[0];
+      } else {
+        pt_own[nb] = pt_cur[nb]; ray_own[nb] = ray_cur[nb]; z_own[nb] = zin[nb]; zn_own[nb] = znext[nb];
+      }
+    }
     if (a.partial) {
       // Fused compositing (n_samples % (32 NB) == 0): this wave holds 32 NB consecutive samples of ONE ray, sample
       // 32 nb + p on lane p of half 0.  Transmittance factorises over segments, so the wave composites its
@@ -298,8 +317,8 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       float s_rgb[3] = {0.f, 0.f, 0.f}, s_acc = 0.f, s_dso = 0.f, s_dj = 0.f, s_beta = 0.f;
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
-        const uint32_t smp = pt_cur[nb] - ray_cur[nb] * uint32_t(a.n_samples);
-        const float delta = smp + 1 == uint32_t(a.n_samples) ? 1e2f : sub_rn(znext[nb], zin[nb]);
+        const uint32_t smp = pt_own[nb] - ray_own[nb] * uint32_t(a.n_samples);
+        const float delta = smp + 1 == uint32_t(a.n_samples) ? 1e2f : sub_rn(zn_own[nb], z_own[nb]);
         const float sg_s = o[nb][3], sg_t = o[nb][7];
         const float as = live ? sub_rn(1.f, head_exp<P, FAST>(-mul_rn(delta, sg_s))) : 0.f;
         const float at = live ? sub_rn(1.f, head_exp<P, FAST>(-mul_rn(delta, sg_t))) : 0.f;
@@ -313,8 +332,8 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #pragma unroll
         for (int c = 0; c < 3; ++c) s_rgb[c] += live ? ws * o[nb][c] + wt * o[nb][4 + c] : 0.f;
         s_acc += wj;
-        s_dso += as * Ts * zin[nb];
-        s_dj += wj * zin[nb];
+        s_dso += as * Ts * z_own[nb];
+        s_dj += wj * z_own[nb];
         s_beta += live ? wt * o[nb][8] : 0.f;
         Pj *= read_lane31(ij);   // lane 31 holds the block's full product
         Ps *= read_lane31(is);
@@ -323,8 +342,8 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       for (int c = 0; c < 3; ++c) s_rgb[c] = read_lane31(scan32_sum(s_rgb[c]));   // lanes 32..63 contribute zeros
       s_acc = read_lane31(scan32_sum(s_acc)); s_dso = read_lane31(scan32_sum(s_dso));
       s_dj = read_lane31(scan32_sum(s_dj)); s_beta = read_lane31(scan32_sum(s_beta));
-      if (st.lane == 0 && pt_cur[0] < npts) {
-        f32x4* dst = reinterpret_cast<f32x4*>(a.partial + (size_t)(pt_cur[0] / uint32_t(NB * 32)) * 12);   // one segment per wave
+      if (st.lane == 0 && pt_own[0] < npts) {
+        f32x4* dst = reinterpret_cast<f32x4*>(a.partial + (size_t)(pt_own[0] / uint32_t(NB * 32)) * 12);   // one segment per wave
         dst[0] = f32x4{s_rgb[0], s_rgb[1], s_rgb[2], s_acc};
         dst[1] = f32x4{s_dso, s_dj, s_beta, Pj};
         dst[2] = f32x4{Ps, 0.f, 0.f, 0.f};
@@ -332,8 +351,8 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     } else {
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
-        if (h == 0 && pt_cur[nb] < npts) {
-          float* dst = a.out + (size_t)pt_cur[nb] * 9;
+        if (h == 0 && pt_own[nb] < npts) {
+          float* dst = a.out + (size_t)pt_own[nb] * 9;
 #pragma unroll
           for (int c = 0; c < 9; ++c) dst[c] = o[nb][c];
         }
@@ -344,8 +363,8 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       tile_coords(tile + gridDim.x);
       const char* slot = smem + ring_slots<P, W>() * USTRIDE + st.wave * (PF_ROUNDS * 8 * 256);
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        int loc = nb * 32 + p;
+      for (int nb = 0; nb < LP; ++nb) {
+        int loc = P::kM16 ? 16 * nb + (st.lane & 15) : nb * 32 + p;
         asm volatile("" : "+v"(loc));   // formed here: as a loop invariant it was hoisted to the prologue and spilled
         const int r = loc >> 6, l = loc & 63;
         const float* f = reinterpret_cast<const float*>(slot + r * 8 * 256) + l;
@@ -381,7 +400,7 @@ static hipError_t launch_one(bool fine, const MlpArgs& a, int n_cu, hipStream_t 
   const uint32_t lds = lds_bytes<P, UMB, WAVES, NB, W>();
   auto kern = fine ? nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W> : nerfh_coarse_kernel<P, FAST, WAVES, UMB, NB, PIPE, W>;
   int slot = fine ? 1 : 0;
-  if constexpr (P::kSplit && NB == 1 && WAVES == 8 && W == kWidth && PIPE) {
+  if constexpr (P::kSplit && !P::kM16 && NB == 1 && WAVES == 8 && W == kWidth && PIPE) {
     if (fine && a.masks) { kern = nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W, true>; slot = 2; }
   } else if (a.masks) return hipErrorInvalidValue;
   static bool attr_done[3] = {false, false, false};
@@ -405,6 +424,7 @@ static hipError_t launch_one(bool fine, const MlpArgs& a, int n_cu, hipStream_t 
 // variant 1: 4 waves x NB 2, 2 WG/CU, unit = 2 M-blocks  (2 waves/SIMD from different workgroups)
 // variant 2: 4 waves x NB 3, 1 WG/CU, unit = layer      (1 wave/SIMD, 512 registers, pipelined epilogue)
 // variant 3: variant 0 without the pipelined epilogue (A/B reference)
+// variant 4: split-f16 as variant 0 on 16x16x32 MFMAs (PrecX3M16); f16 and exact fp32 run their variant-0 kernels
 // netwidth 256: the plain variants (one point block per wave, no pipelined epilogue); staging units of 2 M-blocks (f16) /
 // 1 M-block (f32, split-f16) keep three buffers inside the 160 KB of LDS (a 256 x 256 f16 layer is 128 KB).
 hipError_t launch_mlp(bool fine, int prec, int variant, const MlpArgs& a, int n_cu, hipStream_t stream, int width) {
@@ -416,6 +436,7 @@ hipError_t launch_mlp(bool fine, int prec, int variant, const MlpArgs& a, int n_
     return launch_one<PrecF32, false, 4, unit_mb_w256<PrecF32>(), 1, 1, false, 256>(fine, a, n_cu, stream);
   }
   if (width != kWidth) return hipErrorInvalidValue;
+  if (variant == 4 && prec != 2) variant = 0;
   if (prec == 0) {
     if (variant == 0) return launch_one<PrecF16, true, 8, 8, 2, 1, true>(fine, a, n_cu, stream);
     if (variant == 1) return launch_one<PrecF16, true, 4, 2, 2, 1, true>(fine, a, n_cu, stream);
@@ -424,6 +445,7 @@ hipError_t launch_mlp(bool fine, int prec, int variant, const MlpArgs& a, int n_
   }
   if (prec == 2) {  // split-f16: variant 3 = without the pipelined epilogue (A/B reference), every other variant with it
     if (variant == 3) return launch_one<PrecX3, false, 8, unit_mb<PrecX3>(0), 1, 1, false>(fine, a, n_cu, stream);
+    if (variant == 4) return launch_one<PrecX3M16, false, 8, unit_mb<PrecX3M16>(0), 1, 1, true>(fine, a, n_cu, stream);
     return launch_one<PrecX3, false, 8, unit_mb<PrecX3>(0), 1, 1, true>(fine, a, n_cu, stream);
   }
   if (variant == 1) return launch_one<PrecF32, false, 4, 1, 1, 1, false>(fine, a, n_cu, stream);

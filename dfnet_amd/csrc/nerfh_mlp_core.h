@@ -18,6 +18,12 @@ namespace dfn {
 
 // chunks (B-operand registers groups) per 32 produced features / per n slots
 template <class P> constexpr int chunks_of(int slots) { return slots / P::kSlotsPerChunk; }
+// sample points per lane and point block: PrecX3M16 lanes carry one point of each 16-point N-block (16 nb + (lane & 15))
+template <class P> constexpr int lane_pts(int NB) { return P::kM16 ? 2 : NB; }
+// Split-f16 result pair i (accumulator registers 2i, 2i + 1 of an M-block) -> B chunk (2 mb + x3_chunk) and position x3_pos, x3_pos + 1
+// of the next layer's operand: 32x32 = rows of the two 16-K halves; PrecX3M16 = fragment q = i >> 1 (N-block q & 1, rows 16 (q >> 1) ..)
+template <class P> DFN_HD constexpr int x3_chunk(int i) { return P::kM16 ? (i >> 1) & 1 : i >> 2; }
+template <class P> DFN_HD constexpr int x3_pos(int i) { return P::kM16 ? 4 * (i >> 2) + 2 * (i & 1) : 2 * (i & 3); }
 
 template <class P, int KC>
 DFN_DEV void set_slot(typename FragOf<P>::type (&arr)[KC], int s, float v) {
@@ -219,6 +225,31 @@ DFN_DEV f32x16 load16(const float* p) {
   for (int i = 0; i < 4; ++i) { r[i] = a[i]; r[4 + i] = b[i]; r[8 + i] = c[i]; r[12 + i] = d[i]; }
   return r;
 }
+// PrecX3M16 bias fragment of an M-block: the unit's 128-byte bias block is [g][ms][r] (Packer::pack_blocks), p = its lane group's 8
+// floats; registers 4 ms + r (ms = 0, 1) are the seed of both N-blocks' fragments q = 2 ms + nb.
+DFN_DEV f32x16 load_bias_m16(const float* p) {
+  const f32x4* q = reinterpret_cast<const f32x4*>(p);
+  const f32x4 a = q[0], b = q[1];
+  f32x16 r = {};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { r[i] = a[i]; r[4 + i] = b[i]; }
+  return r;
+}
+// PrecX3M16 per-ray seeds of M-block mb: the ray-bias table keeps the 32x32 order [mb][h][r] (ray_bias_kernel), in which row
+// 16 ms + 4 g + r sits at h = g & 1, r' = r + 4 (2 ms + (g >> 1)); fragment q = 2 ms + nb takes the row of N-block nb's own ray.
+DFN_DEV f32x16 load_raybias_m16(const float* const (&rb)[2], int mb, int g) {
+  f32x16 r;
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb) {
+    const f32x4* q = reinterpret_cast<const f32x4*>(rb[nb] + mb * 32 + (g & 1) * 16 + 4 * (g >> 1));
+    const f32x4 a = q[0], b = q[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { r[4 * nb + i] = a[i]; r[8 + 4 * nb + i] = b[i]; }
+  }
+  return r;
+}
+DFN_DEV f32x4 sub4(const f32x16& v, int o) { return f32x4{v[o], v[o + 1], v[o + 2], v[o + 3]}; }
+DFN_DEV void put4(f32x16& v, int o, const f32x4& x) { v[o] = x[0]; v[o + 1] = x[1]; v[o + 2] = x[2]; v[o + 3] = x[3]; }
 
 // C fragment -> B-operand registers of the next layer (ReLU optional).
 template <class P, bool RELU, int OC>
@@ -242,8 +273,9 @@ DFN_DEV void store_hidden(const f32x16& acc, typename FragOf<P>::type (&out)[OC]
         asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hb), "v"(x1));
         const pk2 l = __builtin_amdgcn_cvt_pkrtz(r0, r1);
         range_track(rmax, hb, RELU);
-        out[2 * mb + c].hi[j] = (_Float16)h[0]; out[2 * mb + c].hi[j + 1] = (_Float16)h[1];
-        out[2 * mb + c].lo[j] = (_Float16)l[0]; out[2 * mb + c].lo[j + 1] = (_Float16)l[1];
+        const int oc = 2 * mb + x3_chunk<P>(4 * c + j / 2), oj = x3_pos<P>(4 * c + j / 2);
+        out[oc].hi[oj] = (_Float16)h[0]; out[oc].hi[oj + 1] = (_Float16)h[1];
+        out[oc].lo[oj] = (_Float16)l[0]; out[oc].lo[oj + 1] = (_Float16)l[1];
       }
   } else if constexpr (P::kSlotsPerChunk == 8) {
 #pragma unroll
@@ -305,8 +337,9 @@ DFN_DEV void store_hidden_piece(const f32x16& acc, typename FragOf<P>::type (&ou
     if (RELU) asm volatile("v_pk_max_u16 %0, %0, %1" : "+v"(rmax) : "v"(hb));   // range guard (range_track), pinned with the piece
     else range_track(rmax, hb, false);
     const half2v hv = __builtin_bit_cast(half2v, hb), lv = __builtin_bit_cast(half2v, lb);
-    out[2 * mb + c].hi[j] = hv[0]; out[2 * mb + c].hi[j + 1] = hv[1];
-    out[2 * mb + c].lo[j] = lv[0]; out[2 * mb + c].lo[j + 1] = lv[1];
+    const int oc = 2 * mb + x3_chunk<P>(i), oj = x3_pos<P>(i);
+    out[oc].hi[oj] = hv[0]; out[oc].hi[oj + 1] = hv[1];
+    out[oc].lo[oj] = lv[0]; out[oc].lo[oj + 1] = lv[1];
   } else if constexpr (P::kSlotsPerChunk == 8) {
     typedef _Float16 half2v __attribute__((ext_vector_type(2)));
     const int c = i >> 2, j = i & 3;
@@ -355,10 +388,21 @@ struct X3Piece {
                  "v_fma_mix_f32 %3, %3, %4, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
                  : "=&v"(hb), "=&v"(hs), "+v"(t0), "+v"(t1) : "v"(s), "v"(s2));
   }
-  template <bool RELU, int OC>
+  // B in two halves (the 16x16x32 chunk spreads the parts over more, shorter MFMA gaps): B1 = hi pair and its scaled copy, B2 = remainders
+  DFN_DEV void B1(uint32_t s2) {
+    asm volatile("v_cvt_pkrtz_f16_f32 %0, %2, %3\n\t"
+                 "v_pk_mul_f16 %1, %0, %4"
+                 : "=&v"(hb), "=&v"(hs) : "v"(t0), "v"(t1), "v"(s2));
+  }
+  DFN_DEV void B2(float s) {
+    asm volatile("v_fma_mix_f32 %0, %0, %2, -%3 op_sel_hi:[0,0,1]\n\t"
+                 "v_fma_mix_f32 %1, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+                 : "+v"(t0), "+v"(t1) : "v"(s), "v"(hs));
+  }
+  template <bool RELU, class P = PrecX3, int OC>
   DFN_DEV void C(half8x2 (&out)[OC], int mb, int i, uint32_t& rmax) {
     typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-    const int c = i >> 2, j = (i & 3) * 2;
+    const int c = x3_chunk<P>(i), j = x3_pos<P>(i);
     asm volatile("v_cvt_pkrtz_f16_f32 %0, %1, %2" : "=v"(lb) : "v"(t0), "v"(t1));
     // range guard on the UNSCALED hi pair: that conversion is the one that saturates
     if (RELU) asm volatile("v_pk_max_u16 %0, %0, %1" : "+v"(rmax) : "v"(hb));
@@ -394,8 +438,9 @@ template <class P, int UMB, bool PIPE, int NB, int KC, int MB, bool RELU, bool E
           int CIN, bool CIN_RELU, bool COUT, bool NOBIAS = false, bool SCALE_FIRST = false, bool TRACK = true>
 DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][KC],
                    typename FragOf<P>::type (&Bout)[NB][(MB ? MB : 1) * chunks_of<P>(16)],
-                   f32x16 (&head)[NB], const float* const (&raybias)[NB], f32x16 (&carry)[NB]) {
+                   f32x16 (&head)[NB], const float* const (&raybias)[lane_pts<P>(NB)], f32x16 (&carry)[NB]) {
   using F = typename FragOf<P>::type;
+  static_assert(!P::kM16 || (PIPE && NB == 1 && !SCALE_FIRST), "the 16x16x32 split-f16 layer is the pipelined one-point-block form");
   constexpr int TOT = MB + (EXTRA ? 1 : 0);
   constexpr int PF = P::kSplit ? 2 : (P::kSlotsPerChunk == 8 ? DFN_PF : 4);  // fragments in flight
   constexpr uint32_t FB = 64 * P::kLaneBytes;         // bytes of one A fragment
@@ -404,7 +449,7 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
   static_assert(CIN < 0 || (PIPE && P::kSlotsPerChunk == 8 && CIN > 0 && CIN + 1 < KC + 1), "carry-in needs the pipelined f16 path");
   static_assert(!COUT || (PIPE && MB >= 1 && !EXTRA), "carry-out needs a regular last M-block");
   static_assert(NEWUNIT || UMB >= TOT, "a layer that continues a unit must fit in it");
-  const int h = st.lane >> 5;
+  const int h = st.lane >> 5, g16 = st.lane >> 4;   // g16: lane group of the 16x16 fragments (PrecX3M16)
   uint32_t rmax_sink = 0;
   uint32_t& rmax_ = TRACK ? st.rmax : rmax_sink;
   const float pscale = P::kSplit ? st.out_scale * st.lane_mul * kX3ActScale : 1.f;  // split-f16 pieces: accumulator -> operand scale
@@ -417,7 +462,8 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
     for (int mb = 0; mb < TOT; ++mb)
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
-        rb[mb][nb] = load16(raybias[nb] + (mb * 2 + h) * 16);
+        if constexpr (P::kM16) rb[mb][nb] = load_raybias_m16(raybias, mb, g16);
+        else rb[mb][nb] = load16(raybias[nb] + (mb * 2 + h) * 16);
         if constexpr (P::kSplit) rb[mb][nb] *= st.in_scale;   // accumulators carry in_scale x the true value
       }
   }
@@ -432,14 +478,18 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
     st.uoff += nmb * KC * FB + nmb * 128;
     // split-f16 fragment = a hi plane (64 lanes x 16 B) followed by a lo plane: both reads stay lane-linear 16-byte
     const char* wl = smem + ub + st.lane * (P::kSplit ? 16 : P::kLaneBytes);
-    const char* bl = smem + ub + nmb * KC * FB + h * 64;
+    const char* bl = smem + ub + nmb * KC * FB + (P::kM16 ? g16 * 32 : h * 64);
     F a[PF];
 #define DFN_AFRAG(t) load_afrag<P>(wl + (t) * FB)
 #pragma unroll
     for (int t = 0; t < PF; ++t)
       if (t < nt) a[t] = DFN_AFRAG(t);
     f32x16 bias = {};
-    if (!RAYBIAS && !NOBIAS) bias = load16(reinterpret_cast<const float*>(bl));
+    auto load_bias = [&](const char* p) {
+      if constexpr (P::kM16) return load_bias_m16(reinterpret_cast<const float*>(p));
+      else return load16(reinterpret_cast<const float*>(p));
+    };
+    if (!RAYBIAS && !NOBIAS) bias = load_bias(bl);
 #pragma unroll
     for (int lm = 0; lm < UMB; ++lm) {
       if (lm < nmb) {
@@ -449,7 +499,8 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
         if (RAYBIAS) {
 #pragma unroll
           for (int nb = 0; nb < NB; ++nb) {
-            acc[nb] = RB_ALL ? rb[RB_ALL ? mb : 0][nb] : load16(raybias[nb] + (mb * 2 + h) * 16);
+            if constexpr (P::kM16) acc[nb] = RB_ALL ? rb[RB_ALL ? mb : 0][nb] : load_raybias_m16(raybias, mb, g16);
+            else acc[nb] = RB_ALL ? rb[RB_ALL ? mb : 0][nb] : load16(raybias[nb] + (mb * 2 + h) * 16);
             if constexpr (P::kSplit && !RB_ALL) acc[nb] *= st.in_scale;
           }
         }
@@ -459,7 +510,7 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
           if (NEWUNIT && lm == 0 && kc == (KC > 1 ? KC / 2 : 0)) mid_sync(st, smem);
           const F cur = a[t % PF];
           if (t + PF < nt) a[t % PF] = DFN_AFRAG(t + PF);
-          if (kc == (PIPE ? KC / 2 : 0) && !RAYBIAS && !NOBIAS && lm + 1 < nmb) bias_next = load16(reinterpret_cast<const float*>(bl + (lm + 1) * 128));
+          if (kc == (PIPE ? KC / 2 : 0) && !RAYBIAS && !NOBIAS && lm + 1 < nmb) bias_next = load_bias(bl + (lm + 1) * 128);
           __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ABOVE this chunk's MFMAs (hipcc otherwise sinks it to its use)
           if constexpr (P::kSplit && PIPE && NB == 1 && !SCALE_FIRST) {
             // split-f16: the conversion pieces of this chunk go BETWEEN its three dependent MFMAs, a third each (the block form
@@ -474,9 +525,6 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
             // parts behind its third MFMA, >= 3 MFMA issues after the producer (read one issue later, the last correction product
             // of some results was missing: 1e-6 instead of 2.4e-7 against exact fp32).
             const bool late = kc == 0;
-            f32x16 c0 = (kc == 0) ? (RAYBIAS ? acc[0] : bias) : acc[0];
-            c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.hi, Bin[0][kc].hi, c0, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
 #define DFN_X3_PARTS_A \
             _Pragma("unroll") for (int q = 0; q < NPMAX; ++q) \
               if (q < np && base + q < 8) { \
@@ -486,6 +534,50 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
 #define DFN_X3_PARTS_B \
             _Pragma("unroll") for (int q = 0; q < NPMAX; ++q) \
               if (q < np && base + q < 8) pc[q].B(pscale, pscale2);
+            if constexpr (P::kM16) {
+              // 16x16x32: chunk kc = the 32-K chunk kc >> 1 of the M-block's 16-row half ms = kc & 1.  Its A fragment feeds both N-blocks
+              // (B chunks 2 (kc >> 1) + nb), three products each: two independent accumulation chains, fragments q = 2 ms + nb.  The
+              // conversion parts go into the gaps after MFMAs 2..5 (A, B1, B2, C: 8 VALU cycles per 16-cycle MFMA are free).
+              // Hazard (8-pass XDL result -> VALU read in inline asm: 12 wait states, no interlock): piece i reads fragment q = i >> 1 of
+              // half ms = i >> 2, last written in chunk KC - 2 + ms of the previous M-block (layer), and half 1's pieces start at chunk
+              // 8 / (2 np) >= 1 (np <= 4 pieces per chunk): >= 8 MFMA issues lie between producer and reader in every chunk, the first
+              // one included (the 32x32 path's `late` rule holds by construction).
+              const int ms = kc & 1, bc = 2 * (kc >> 1);
+              f32x4 c0, c1;
+              if (kc < 2 && !RAYBIAS) { c0 = sub4(bias, 4 * ms); c1 = c0; }
+              else { c0 = sub4(acc[0], 8 * ms); c1 = sub4(acc[0], 8 * ms + 4); }
+#define DFN_X3_PARTS(...) \
+              _Pragma("unroll") for (int q = 0; q < NPMAX; ++q) \
+                if (q < np && base + q < 8) { __VA_ARGS__; }
+              c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.hi, Bin[0][bc].hi, c0, 0, 0, 0);
+              c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.hi, Bin[0][bc + 1].hi, c1, 0, 0, 0);
+              __builtin_amdgcn_sched_barrier(0);
+              DFN_X3_PARTS_A
+              __builtin_amdgcn_sched_barrier(0);
+              c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.hi, Bin[0][bc].lo, c0, 0, 0, 0);
+              __builtin_amdgcn_sched_barrier(0);
+              DFN_X3_PARTS(pc[q].B1(pscale2))
+              __builtin_amdgcn_sched_barrier(0);
+              c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.hi, Bin[0][bc + 1].lo, c1, 0, 0, 0);
+              __builtin_amdgcn_sched_barrier(0);
+              DFN_X3_PARTS(pc[q].B2(pscale))
+              __builtin_amdgcn_sched_barrier(0);
+              c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.lo, Bin[0][bc].hi, c0, 0, 0, 0);
+              __builtin_amdgcn_sched_barrier(0);
+              DFN_X3_PARTS(if (from_carry) pc[q].template C<CIN_RELU, P>(Bin[0], CIN / 2, base + q, rmax_);
+                           else pc[q].template C<RELU, P>(Bout[0], mb - 1, base + q, rmax_))
+              __builtin_amdgcn_sched_barrier(0);
+              c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.lo, Bin[0][bc + 1].hi, c1, 0, 0, 0);
+#undef DFN_X3_PARTS
+              put4(acc[0], 8 * ms, c0);
+              put4(acc[0], 8 * ms + 4, c1);
+              if (from_carry && kc == CIN - 1) asm volatile("s_nop 3");
+              __builtin_amdgcn_sched_barrier(0);
+              continue;
+            }
+            f32x16 c0 = (kc == 0) ? (RAYBIAS ? acc[0] : bias) : acc[0];
+            c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.hi, Bin[0][kc].hi, c0, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
             if (!late) { DFN_X3_PARTS_A }
             __builtin_amdgcn_sched_barrier(0);
             c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.hi, Bin[0][kc].lo, c0, 0, 0, 0);
@@ -508,10 +600,12 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
             __builtin_amdgcn_sched_barrier(0);
             continue;
           }
+          if constexpr (!P::kM16) {
 #pragma unroll
           for (int nb = 0; nb < NB; ++nb) {
             if (kc == 0) acc[nb] = mfma<P>(cur, Bin[nb][0], RAYBIAS ? acc[nb] : bias);
             else acc[nb] = mfma<P>(cur, Bin[nb][kc], acc[nb]);
+          }
           }
           if (CIN > 0 && mb == 0 && kc < CIN) {  // the previous layer's last M-block -> chunks CIN, CIN+1 of Bin
 #pragma unroll
@@ -544,6 +638,12 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
           for (int nb = 0; nb < NB; ++nb) {  // (the M-block before a head is converted during the head's MFMAs)
             head[nb] = acc[nb];
             if constexpr (P::kSplit) head[nb] *= st.out_scale * st.lane_mul;
+            if constexpr (P::kM16) {  // head value c of the sample of lane 16 g + (l & 15), g = 0, 1: fragment 2 (c >> 2) + g (head_row_m16)
+              const f32x16 v = head[nb];
+              const bool g1 = (g16 & 1) != 0;
+#pragma unroll
+              for (int c = 0; c < 8; ++c) head[nb][c] = g1 ? v[8 * (c >> 2) + 4 + (c & 3)] : v[8 * (c >> 2) + (c & 3)];
+            }
           }
         }
       }
@@ -612,6 +712,43 @@ DFN_DEV void posenc_xyz(const float (&x)[NB][3], int h, typename FragOf<P>::type
   }
 }
 
+// PrecX3M16: the same exact-fract hardware path for the two points of a lane (16 nb + (lane & 15)), 16 slots each in lane group g
+// (slot map: pe_xyz_feature_m16): octaves 2g, 2g+1 of all three coordinates, then two of the six (coordinate, octave 8 | 9) pairs —
+// group 3 puts the raw coordinates there.  Eight sin/cos evaluations per point and lane, as the 32x32 kernels' fifteen per point and half.
+template <class P, int PC>
+DFN_DEV void posenc_xyz_m16(const float (&x)[2][3], int g, typename FragOf<P>::type (&pe)[1][PC]) {
+  static_assert(P::kM16 && PC == 4, "16 slots of two points");
+  auto put = [&](int n, int s, float v) {
+    _Float16 hi, lo;
+    x3_split(v, hi, lo);
+    pe[0][2 * (s >> 3) + n].hi[s & 7] = hi;
+    pe[0][2 * (s >> 3) + n].lo[s & 7] = lo;
+  };
+  const float base = float(1 << (2 * g));          // octaves 2g, 2g + 1
+  const float f6 = g == 2 ? 512.f : 256.f, f7 = g == 0 ? 256.f : 512.f;   // octave of the pairs rho = 2g, 2g + 1
+#pragma unroll
+  for (int n = 0; n < 2; ++n) {
+    float uh[3], ul[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rev_split(x[n][c], uh[c], ul[c]);
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float sn, cs;
+        rev_sincos(uh[c], ul[c], base * float(1 << k), sn, cs);
+        put(n, 6 * k + c, sn);
+        put(n, 6 * k + 3 + c, cs);
+      }
+    // rho = 2g: coordinate 0, 2, 1 (g = 0, 1, 2); rho = 2g + 1: coordinate 1, 0, 2
+    float s6, c6, s7, c7;
+    rev_sincos(g == 0 ? uh[0] : (g == 1 ? uh[2] : uh[1]), g == 0 ? ul[0] : (g == 1 ? ul[2] : ul[1]), f6, s6, c6);
+    rev_sincos(g == 0 ? uh[1] : (g == 1 ? uh[0] : uh[2]), g == 0 ? ul[1] : (g == 1 ? ul[0] : ul[2]), f7, s7, c7);
+    if (g == 3) { s6 = x[n][0]; c6 = x[n][1]; s7 = x[n][2]; c7 = 0.f; }
+    put(n, 12, s6); put(n, 13, c6); put(n, 14, s7); put(n, 15, c7);
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // The 8-layer trunk (xyz_encoding_1..8, skip concat [pe, h] before layer 5).
 // `hook(l, h)` (optional) is called once per trunk layer l = 0..6 with that layer's COMPLETE output operand (point block 0) — one
@@ -621,7 +758,7 @@ struct NoTrunkHook {
   template <class A> DFN_DEV void operator()(int, A&) const {}
 };
 template <class P, int UMB, bool PIPE, bool FAST, int NB, int W = kWidth, class Hook = NoTrunkHook>
-DFN_DEV void trunk(Stager& st, char* smem, const float (&x)[NB][3],
+DFN_DEV void trunk(Stager& st, char* smem, const float (&x)[lane_pts<P>(NB)][3],
                    typename FragOf<P>::type (&out)[NB][chunks_of<P>(W / 2)], f32x16 (&carry)[NB], Hook hook = Hook()) {
   using F = typename FragOf<P>::type;
   constexpr int PC = chunks_of<P>(32), HC = chunks_of<P>(W / 2), MBW = W / 32;
@@ -630,9 +767,13 @@ DFN_DEV void trunk(Stager& st, char* smem, const float (&x)[NB][3],
   static_assert(!PIPE || W == kWidth, "the pipelined epilogue is tuned for netwidth 128");
   const int h = st.lane >> 5;
   f32x16 nohead[NB];
-  const float* const norb[NB] = {};
+  const float* const norb[lane_pts<P>(NB)] = {};
   F pe[NB][PC];
-  posenc_xyz<P, FAST, NB, PC>(x, h, pe);
+  auto encode = [&](const float (&xx)[lane_pts<P>(NB)][3]) {
+    if constexpr (P::kM16) { static_assert(!FAST, "split-f16 only"); posenc_xyz_m16<P, PC>(xx, st.lane >> 4, pe); }
+    else posenc_xyz<P, FAST, NB, PC>(xx, h, pe);
+  };
+  encode(x);
   F a[NB][HC], b[NB][HC];
   layer<P, UMB, PIPE, NB, PC, MBW, true, false, false, true, -1, true, CY>(st, smem, pe, a, nohead, norb, carry);
   layer<P, UMB, PIPE, NB, HC, MBW, true, false, false, true, CI, true, CY>(st, smem, a, b, nohead, norb, carry);
@@ -644,15 +785,15 @@ DFN_DEV void trunk(Stager& st, char* smem, const float (&x)[NB][3],
   {
     F cat[NB][PC + HC];
     if constexpr (P::kSlotsPerChunk == 8 && (!PIPE || P::kSplit)) {  // recompute: cheaper than 32 VGPRs live across 4 layers
-      float x2[NB][3];
+      float x2[lane_pts<P>(NB)][3];
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
+      for (int nb = 0; nb < lane_pts<P>(NB); ++nb)
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           x2[nb][c] = x[nb][c];
           asm volatile("" : "+v"(x2[nb][c]));  // opaque copy: stops the compiler from CSE-ing the two encodings
         }
-      posenc_xyz<P, FAST, NB, PC>(x2, h, pe);
+      encode(x2);
     }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
