@@ -23,15 +23,19 @@ static inline int grid_for(size_t n, int block, int cap = 256 * 8) {
 //   d sigma_s,i = delta_i [(1 - a_s,i) T_i g.c_s,i - S_i]      S_i = sum_{k>i} e_k  (sigma_i attenuates every later sample)
 //   d sigma_t,i = delta_i [(1 - a_t,i) T_i g.c_t,i - S_i]      d beta_i = 0 (beta does not reach rgb)
 // One wavefront per ray, SPL consecutive samples per lane.
-template <int SPL>
+// EXT (render(retraw=True) under autograd, rendering.py:318-320: `raw` itself is an output): gext [n_rays, Nf, 9] is a gradient that
+// reaches the returned raw directly; it is read where the result is written and graw = d raw(compositor) + gext.  EXT = false is the
+// rgb-only kernel, instruction for instruction.
+template <int SPL, bool EXT>
 __global__ __launch_bounds__(256) void composite_fine_backward_kernel(const float* __restrict__ raw, const float* __restrict__ z,
                                                                       const float* __restrict__ grad_rgb, size_t n_rays,
-                                                                      int Nf, float* __restrict__ graw) {
+                                                                      int Nf, float* __restrict__ graw, const float* __restrict__ gext) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (size_t ray = size_t(blockIdx.x) * 4 + wave; ray < n_rays; ray += size_t(gridDim.x) * 4) {
     const float* rr = raw + ray * size_t(Nf) * 9;
     const float* zr = z + ray * size_t(Nf);
     float* gr = graw + ray * size_t(Nf) * 9;
+    const float* xr = EXT ? gext + ray * size_t(Nf) * 9 : nullptr;
     const float g0 = grad_rgb[ray * 3], g1 = grad_rgb[ray * 3 + 1], g2 = grad_rgb[ray * 3 + 2];
     float v[SPL][9], zz[SPL + 1];
 #pragma unroll
@@ -86,18 +90,42 @@ __global__ __launch_bounds__(256) void composite_fine_backward_kernel(const floa
         o[4] = g0 * wt; o[5] = g1 * wt; o[6] = g2 * wt;
         o[7] = dl[k] * ((1.f - a_t[k]) * T[k] * gct[k] - S);
         o[8] = 0.f;
+        if constexpr (EXT) {
+          const float* x = xr + size_t(i) * 9;
+#pragma unroll
+          for (int c = 0; c < 9; ++c) o[c] = add_rn(o[c], x[c]);
+        }
       }
     }
   }
 }
 
+// grad_rgb == NULL (a loss on raw alone): nothing comes through the compositor, graw = gext — no scan, one coalesced copy.
+__global__ __launch_bounds__(256) void composite_fine_backward_ext_only_kernel(const float* __restrict__ gext, size_t n,
+                                                                               float* __restrict__ graw) {
+  for (size_t e = blockIdx.x * size_t(blockDim.x) + threadIdx.x; e < n; e += size_t(gridDim.x) * blockDim.x) graw[e] = gext[e];
+}
+
 hipError_t launch_composite_fine_backward(const float* raw, const float* z, const float* grad_rgb, size_t n_rays, int Nf,
-                                          float* graw, hipStream_t stream) {
+                                          float* graw, hipStream_t stream, const float* grad_raw_ext) {
   if (!n_rays) return hipSuccess;
+  if (!grad_rgb) {
+    if (!grad_raw_ext) return hipErrorInvalidValue;
+    const size_t n = n_rays * size_t(Nf) * 9;
+    hipLaunchKernelGGL(composite_fine_backward_ext_only_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, grad_raw_ext, n, graw);
+    return hipGetLastError();
+  }
   const int spl = (Nf + 63) / 64;
   const dim3 grid(grid_for((n_rays + 3) / 4, 1, 256 * 16)), block(256);
-#define DFN_COMPB(S) \
-  hipLaunchKernelGGL(composite_fine_backward_kernel<S>, grid, block, 0, stream, raw, z, grad_rgb, n_rays, Nf, graw)
+#define DFN_COMPB(S)                                                                                                              \
+  do {                                                                                                                            \
+    if (grad_raw_ext)                                                                                                             \
+      hipLaunchKernelGGL((composite_fine_backward_kernel<S, true>), grid, block, 0, stream, raw, z, grad_rgb, n_rays, Nf, graw,   \
+                         grad_raw_ext);                                                                                           \
+    else                                                                                                                          \
+      hipLaunchKernelGGL((composite_fine_backward_kernel<S, false>), grid, block, 0, stream, raw, z, grad_rgb, n_rays, Nf, graw,  \
+                         static_cast<const float*>(nullptr));                                                                     \
+  } while (0)
   if (spl <= 1) DFN_COMPB(1);
   else if (spl == 2) DFN_COMPB(2);
   else if (spl == 3) DFN_COMPB(3);

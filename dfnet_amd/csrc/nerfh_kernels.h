@@ -90,9 +90,11 @@ struct BwdArgs {
 constexpr int kBwdMaskWords = 21;    // 8 trunk layers x 128 bits, dir_encoding 64, transient_encoding 4 x 64 — per point
 constexpr int kBwdTilePoints = 256;  // points per workgroup tile of the split-f16 gradient kernel (8 waves x 32)
 hipError_t launch_mlp_fine_backward(int prec, const BwdArgs& a, int n_cu, hipStream_t stream, int mode = 0);
-// d L / d raw from d L / d rgb through the fine compositing (test-time, rgb only).
+// d L / d raw from d L / d rgb through the fine compositing (test-time, rgb only).  grad_raw_ext [n_rays, Nf, 9] (optional): a
+// gradient that reaches raw directly, added in the same kernel (graw = d raw(compositor) + grad_raw_ext); with grad_rgb == nullptr
+// graw = grad_raw_ext and the scan is skipped.  Without it: the rgb-only kernel, unchanged.
 hipError_t launch_composite_fine_backward(const float* raw, const float* z, const float* grad_rgb, size_t n_rays, int Nf,
-                                          float* graw, hipStream_t stream);
+                                          float* graw, hipStream_t stream, const float* grad_raw_ext = nullptr);
 // Per-ray reduction of the per-sample gradients: d o = sum g, d d = sum z g (+ viewdir normalisation when
 // `derive_viewdirs`), d viewdirs = sum gv (when grad_viewdirs != nullptr).  accumulate: add to what grad_o / grad_d hold.
 hipError_t launch_ray_grad_reduce(const float* gpts, const float* z, const float* rays_d, size_t n_rays, int Nf,

@@ -495,26 +495,32 @@ extern "C" size_t dfn_nerfh_generic_workspace_bytes(dfn_nerfh_t h, size_t n_rays
   return carve_train(nullptr, dims_of(h->desc), n_rays ? n_rays : 1, Nc, Ni, false).total + al64((n_rays ? n_rays : 1) * size_t(Nc)) * 4;
 }
 
-extern "C" int dfn_nerfh_generic_render_rays(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* hist, size_t hist_rows,
-                                             size_t n_rays, int Nc, int Ni, float near, float far, float* rgb, float* disp, float* acc,
-                                             float* raw, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_generic_render_rays")) return rc;
-  if (!h->committed) return set_error(DFN_ERR_STATE, "dfn_nerfh_generic_render_rays: dfn_nerfh_commit() has not been called");
+namespace {
+// `entry`: the public name the messages carry (the two entries share this body; viewdirs == nullptr: d / |d|, written to w.view)
+int generic_render_rays_impl(const char* entry, dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
+                             const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far, float* rgb,
+                             float* disp, float* acc, float* raw, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_train_args(h, Nc, Ni, entry)) return rc;
+  if (!h->committed) return set_error(DFN_ERR_STATE, "%s: dfn_nerfh_commit() has not been called", entry);
   if (!n_rays) return DFN_OK;
   if (!rays_o || !rays_d || !hist || !rgb || !disp || !acc || !raw || !workspace || (hist_rows != 1 && hist_rows != n_rays))
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_generic_render_rays: bad argument (raw [n_rays, Nc+Ni, 9] is required scratch/output)");
+    return set_error(DFN_ERR_ARG, "%s: bad argument (raw [n_rays, Nc+Ni, 9] is required scratch/output)", entry);
   const Dims m = dims_of(h->desc);
   const TrainWs w = carve_train(static_cast<float*>(workspace), m, n_rays, Nc, Ni, false);
   float* sigma = static_cast<float*>(workspace) + w.total / 4;
   if (w.total + al64(n_rays * size_t(Nc)) * 4 > workspace_bytes)
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_generic_render_rays: workspace too small (%zu)", workspace_bytes);
+    return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu)", entry, workspace_bytes);
   hipStream_t s = HS(stream);
   const size_t R = n_rays;
   const int Nf = Nc + Ni;
   const float* const* params = h->gen_params.data();
   const Net nc = net_of(params, nullptr, false), nf = net_of(params, nullptr, true);
-  CHECK_HIP(launch_viewdirs(rays_d, R, w.view, s), "generic render: viewdirs");
-  CHECK_HIP(ray_inputs(w.view, hist, hist_rows, params[kCoarseParams + kFineParams], params[kCoarseParams + kFineParams + 1], m.hist_bin,
+  const float* v = viewdirs;
+  if (!v) {
+    CHECK_HIP(launch_viewdirs(rays_d, R, w.view, s), "generic render: viewdirs");
+    v = w.view;
+  }
+  CHECK_HIP(ray_inputs(v, hist, hist_rows, params[kCoarseParams + kFineParams], params[kCoarseParams + kFineParams + 1], m.hist_bin,
                        m.dim_a, m.dim_t, m.n_vocab, R, w.dir_f, m.ld_df, w.t_in, m.ld_t, s),
             "generic render: ray inputs");
   CHECK_HIP(stratified_z(nullptr, R, Nc, near, far, w.z_c, s, h->render_flags & DFN_RENDER_LINDISP), "generic render: z");
@@ -530,6 +536,23 @@ extern "C" int dfn_nerfh_generic_render_rays(dfn_nerfh_t h, const float* rays_o,
                                   nullptr, s),
             "generic render: composite");
   return DFN_OK;
+}
+}  // namespace
+
+extern "C" int dfn_nerfh_generic_render_rays(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* hist, size_t hist_rows,
+                                             size_t n_rays, int Nc, int Ni, float near, float far, float* rgb, float* disp, float* acc,
+                                             float* raw, void* workspace, size_t workspace_bytes, void* stream) {
+  return generic_render_rays_impl("dfn_nerfh_generic_render_rays", h, rays_o, rays_d, nullptr, hist, hist_rows, n_rays, Nc, Ni, near, far,
+                                  rgb, disp, acc, raw, workspace, workspace_bytes, stream);
+}
+// The same render with the view directions of the fine network's direction encoding given by the caller (models/rendering.py:364-371:
+// render() takes them from the rays BEFORE c2w_staticcam / ndc replace those rays), used as given.
+extern "C" int dfn_nerfh_generic_render_rays_v(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                               const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
+                                               float* rgb, float* disp, float* acc, float* raw, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+  return generic_render_rays_impl("dfn_nerfh_generic_render_rays_v", h, rays_o, rays_d, viewdirs, hist, hist_rows, n_rays, Nc, Ni, near,
+                                  far, rgb, disp, acc, raw, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------ generic-width render gradient
@@ -560,19 +583,24 @@ extern "C" size_t dfn_nerfh_generic_backward_workspace_bytes(dfn_nerfh_t h, size
   return carve_gen_bwd(nullptr, dims_of(h->desc), n_rays ? n_rays : 1, Nc, Ni).total;
 }
 
-extern "C" int dfn_nerfh_generic_render_rays_backward(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
-                                                      const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near,
-                                                      float far, const float* grad_rgb, float* grad_rays_o, float* grad_rays_d,
-                                                      float* grad_viewdirs, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_generic_render_rays_backward")) return rc;
-  if (!h->committed) return set_error(DFN_ERR_STATE, "dfn_nerfh_generic_render_rays_backward: dfn_nerfh_commit() has not been called");
+namespace {
+// `entry`: the public name the messages carry.  grad_raw [n_rays, Nc+Ni, 9] (optional): d L / d of the RETURNED raw, added to the
+// compositor's d L / d raw inside the compositing-backward kernel, before the head derivatives.  rgb_required: the entry without
+// grad_raw, where grad_rgb is not optional.
+int generic_render_rays_backward_impl(const char* entry, dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                      const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
+                                      const float* grad_rgb, const float* grad_raw, float* grad_rays_o, float* grad_rays_d,
+                                      float* grad_viewdirs, void* workspace, size_t workspace_bytes, void* stream, bool rgb_required) {
+  if (int rc = check_train_args(h, Nc, Ni, entry)) return rc;
+  if (!h->committed) return set_error(DFN_ERR_STATE, "%s: dfn_nerfh_commit() has not been called", entry);
   if (!n_rays) return DFN_OK;
-  if (!rays_o || !rays_d || !hist || !grad_rgb || !grad_rays_o || !grad_rays_d || !workspace || (hist_rows != 1 && hist_rows != n_rays))
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_generic_render_rays_backward: bad argument (hist_rows must be 1 or n_rays)");
+  if (!grad_rgb && !grad_raw && !rgb_required)
+    return set_error(DFN_ERR_ARG, "%s: bad argument (grad_rgb and grad_raw are both NULL: at least one is required)", entry);
+  if (!rays_o || !rays_d || !hist || (rgb_required && !grad_rgb) || !grad_rays_o || !grad_rays_d || !workspace || (hist_rows != 1 && hist_rows != n_rays))
+    return set_error(DFN_ERR_ARG, "%s: bad argument (hist_rows must be 1 or n_rays)", entry);
   const Dims m = dims_of(h->desc);
   const GenBwdWs g = carve_gen_bwd(static_cast<float*>(workspace), m, n_rays, Nc, Ni);
-  if (g.total > workspace_bytes)
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_generic_render_rays_backward: workspace too small (%zu < %zu)", workspace_bytes, g.total);
+  if (g.total > workspace_bytes) return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", entry, workspace_bytes, g.total);
   hipStream_t s = HS(stream);
   const TrainWs& w = g.t;
   const size_t R = n_rays;
@@ -601,7 +629,7 @@ extern "C" int dfn_nerfh_generic_render_rays_backward(dfn_nerfh_t h, const float
   if (int rc = net_forward(nf, m, b, true, false, s)) return rc;
   // ---- d rgb -> d raw -> d pre-activation (in place)
   float* gpre = w.gpre_f;
-  CHECK_HIP(launch_composite_fine_backward(g.raw, w.z_f, grad_rgb, R, Nf, gpre, s), "generic render gradient: composite");
+  CHECK_HIP(launch_composite_fine_backward(g.raw, w.z_f, grad_rgb, R, Nf, gpre, s, grad_raw), "generic render gradient: composite");
   CHECK_HIP(head_prime(g.raw, gpre, size_t(P), s), "generic render gradient: head derivatives");
   // ---- data gradients (the calls of net_backward, without the weight gradients)
   const int C = 9, ldw_dir = W + b.kd, ldw_te0 = W + m.nt;
@@ -639,6 +667,26 @@ extern "C" int dfn_nerfh_generic_render_rays_backward(dfn_nerfh_t h, const float
                                    viewdirs ? grad_viewdirs : nullptr, s),
             "generic render gradient: per-ray reduction");
   return DFN_OK;
+}
+}  // namespace
+
+extern "C" int dfn_nerfh_generic_render_rays_backward(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                                      const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near,
+                                                      float far, const float* grad_rgb, float* grad_rays_o, float* grad_rays_d,
+                                                      float* grad_viewdirs, void* workspace, size_t workspace_bytes, void* stream) {
+  return generic_render_rays_backward_impl("dfn_nerfh_generic_render_rays_backward", h, rays_o, rays_d, viewdirs, hist, hist_rows, n_rays,
+                                           Nc, Ni, near, far, grad_rgb, nullptr, grad_rays_o, grad_rays_d, grad_viewdirs, workspace,
+                                           workspace_bytes, stream, true);
+}
+// With d L / d raw as well (render(retraw=True) under autograd, models/rendering.py:318-320: extras['raw'] is part of the graph).
+extern "C" int dfn_nerfh_generic_render_rays_backward_raw(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                                          const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near,
+                                                          float far, const float* grad_rgb, const float* grad_raw, float* grad_rays_o,
+                                                          float* grad_rays_d, float* grad_viewdirs, void* workspace,
+                                                          size_t workspace_bytes, void* stream) {
+  return generic_render_rays_backward_impl("dfn_nerfh_generic_render_rays_backward_raw", h, rays_o, rays_d, viewdirs, hist, hist_rows,
+                                           n_rays, Nc, Ni, near, far, grad_rgb, grad_raw, grad_rays_o, grad_rays_d, grad_viewdirs,
+                                           workspace, workspace_bytes, stream, false);
 }
 
 // ------------------------------------------------------------------------------------------ the three products, for parity tests

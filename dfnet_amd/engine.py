@@ -187,10 +187,15 @@ class NerfHEngine:
     GENERIC_GRAD_CHUNK = 8192   # rays per pass of the generic-width gradient (every fine activation is kept: ~1.3 MB per ray at 64+128, netwidth 256)
     GENERIC_CHUNK = 4096   # rays per pass of the generic path (its activations live in HBM: ~1.2 MB per ray at 64+128, W=128)
 
-    def generic_render_rays(self, rays_o, rays_d, hist, Nc, Ni, near, far, retraw=False):
-        """Test-time render on the generic-width path (dfn_nerfh_generic_render_rays): exact fp32, any netwidth."""
+    def generic_render_rays(self, rays_o, rays_d, hist, Nc, Ni, near, far, retraw=False, viewdirs=None):
+        """Test-time render on the generic-width path (dfn_nerfh_generic_render_rays_v): exact fp32, any netwidth.  viewdirs [n,3]:
+        the fine network's view directions, used as given (None: d/|d|)."""
         rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
         n, dev = rays_o.shape[0], rays_o.device
+        if viewdirs is not None:
+            viewdirs = _f32c(viewdirs).reshape(-1, 3)
+            if viewdirs.shape[0] != n:
+                raise ValueError(f"viewdirs must have {n} rows, got {tuple(viewdirs.shape)}")
         hist = _f32c(hist).reshape(-1, self.hist_bin)
         rgb, disp, acc = torch.empty(n, 3, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev)
         Nf = Nc + Ni
@@ -202,18 +207,18 @@ class NerfHEngine:
             m = min(C, n - r0)
             h = hist if hist.shape[0] == 1 else hist[r0:r0 + m]
             raw = raw_all[r0:r0 + m] if retraw else raw_tmp[:m]
-            check(self.lib.dfn_nerfh_generic_render_rays(self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(h), h.shape[0], m,
-                                                         Nc, Ni, float(near), float(far), ptr(rgb[r0:r0 + m]), ptr(disp[r0:r0 + m]),
-                                                         ptr(acc[r0:r0 + m]), ptr(raw), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                                         current_stream()), "dfn_nerfh_generic_render_rays")
+            v = None if viewdirs is None else viewdirs[r0:r0 + m]
+            check(self.lib.dfn_nerfh_generic_render_rays_v(self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(v), ptr(h),
+                                                           h.shape[0], m, Nc, Ni, float(near), float(far), ptr(rgb[r0:r0 + m]),
+                                                           ptr(disp[r0:r0 + m]), ptr(acc[r0:r0 + m]), ptr(raw),
+                                                           ctypes.c_void_p(ws.data_ptr()), ws.numel(), current_stream()),
+                  "dfn_nerfh_generic_render_rays_v")
         return rgb, disp, acc, raw_all
 
     def render_rays(self, rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs=None, retraw=False, precision=None):
         """Test-time render of a ray batch -> (rgb [n,3], disp [n], acc [n], raw|None)."""
         if not self.fast or precision == "generic":
-            if viewdirs is not None:
-                raise NotImplementedError("explicit viewdirs on the generic-width path")
-            return self.generic_render_rays(rays_o, rays_d, hist, Nc, Ni, near, far, retraw)
+            return self.generic_render_rays(rays_o, rays_d, hist, Nc, Ni, near, far, retraw, viewdirs=viewdirs)
         rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
         n = rays_o.shape[0]
         dev = rays_o.device
@@ -294,30 +299,41 @@ class NerfHEngine:
         return go, gd, gv
 
     # ------------------------------------------------------------------ gradient of the whole path
-    def render_rays_backward(self, rays_o, rays_d, hist, Nc, Ni, near, far, grad_rgb, viewdirs=None, precision=None):
+    def render_rays_backward(self, rays_o, rays_d, hist, Nc, Ni, near, far, grad_rgb, viewdirs=None, precision=None, grad_raw=None):
         """d L/d (rays_o, rays_d[, viewdirs]) of render_rays from d L/d rgb [n,3].  With viewdirs=None they are
-        d/|d| and their gradient is folded into grad_rays_d (what autograd does for render(rays=...))."""
+        d/|d| and their gradient is folded into grad_rays_d (what autograd does for render(rays=...)).  grad_raw [n,Nc+Ni,9]
+        (generic-width path): d L/d of the returned raw, added to the compositor's; grad_rgb may then be None."""
         rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
-        grad_rgb = _f32c(grad_rgb).reshape(-1, 3)
         n, dev = rays_o.shape[0], rays_o.device
+        generic = self.width != 128 or precision == "generic"
+        if grad_raw is not None:
+            if not generic:
+                raise NotImplementedError("render_rays_backward(grad_raw=...) on the register-resident netwidth-128 kernels: use "
+                                          "precision='generic' or backward_from_saved(grad_raw=...)")
+            grad_raw = _f32c(grad_raw).reshape(n, Nc + Ni, 9)
+        elif grad_rgb is None:
+            raise ValueError("render_rays_backward: grad_rgb and grad_raw are both None")
+        if grad_rgb is not None:
+            grad_rgb = _f32c(grad_rgb).reshape(n, 3)
         hist = _f32c(hist).reshape(-1, self.hist_bin)
         go, gd = torch.empty(n, 3, device=dev), torch.empty(n, 3, device=dev)
         gv = None
         if viewdirs is not None:
             viewdirs = _f32c(viewdirs).reshape(-1, 3)
             gv = torch.empty(n, 3, device=dev)
-        if self.width != 128 or precision == "generic":
+        if generic:
             # the register-resident gradient kernels are netwidth 128; every other width takes the layer-by-layer exact-fp32 path
             C = self.GENERIC_GRAD_CHUNK
             ws = self._workspace(self.lib.dfn_nerfh_generic_backward_workspace_bytes(self.handle, min(n, C), Nc, Ni), dev)
+            cut = lambda t, r0, m: None if t is None else t[r0:r0 + m]
             for r0 in range(0, n, C):
                 m = min(C, n - r0)
                 hh = hist if hist.shape[0] == 1 else hist[r0:r0 + m]
-                check(self.lib.dfn_nerfh_generic_render_rays_backward(
-                    self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(None if viewdirs is None else viewdirs[r0:r0 + m]),
-                    ptr(hh), hh.shape[0], m, Nc, Ni, float(near), float(far), ptr(grad_rgb[r0:r0 + m]), ptr(go[r0:r0 + m]), ptr(gd[r0:r0 + m]),
-                    ptr(None if gv is None else gv[r0:r0 + m]), ctypes.c_void_p(ws.data_ptr()), ws.numel(), current_stream()),
-                    "dfn_nerfh_generic_render_rays_backward")
+                check(self.lib.dfn_nerfh_generic_render_rays_backward_raw(
+                    self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(cut(viewdirs, r0, m)), ptr(hh), hh.shape[0], m, Nc, Ni,
+                    float(near), float(far), ptr(cut(grad_rgb, r0, m)), ptr(cut(grad_raw, r0, m)), ptr(go[r0:r0 + m]), ptr(gd[r0:r0 + m]),
+                    ptr(cut(gv, r0, m)), ctypes.c_void_p(ws.data_ptr()), ws.numel(), current_stream()),
+                    "dfn_nerfh_generic_render_rays_backward_raw")
             return go, gd, gv
         ws = self._workspace(self.lib.dfn_render_backward_workspace_bytes(n, Nc, Ni), dev)
         check(self.lib.dfn_render_rays_backward(self.handle, self._prec(precision), ptr(rays_o), ptr(rays_d), ptr(viewdirs),

@@ -9,7 +9,7 @@ frame-sharded loop with one gather when torch.distributed is initialised (dfnet_
 Test-time kwargs (`render_kwargs_test`: perturb=0, raw_noise_std=0, test_time=True) run on the packed MFMA engine;
 training kwargs (`render_kwargs_train`: test_time=False, perturb, raw_noise_std) run on the exact-fp32 training kernels and
 return tensors attached to autograd with the reference's extras (dfnet_amd/nerf_train.py).  `lindisp` works everywhere; `ndc`
-and `c2w_staticcam` at test time without autograd (their only use in the reference: LLFF-style visualisation).  `white_bkgd=True`
+and `c2w_staticcam` at test time without autograd (their only use in the reference: LLFF-style visualisation), at every netwidth.  `white_bkgd=True`
 raises: it is not a working option of this path in the reference either (rendering.py:295 passes it to the coarse compositor as
 `output_transient`, which fails with a TypeError at test time and mis-slices the 4-channel coarse output in training).
 
@@ -64,13 +64,16 @@ def _two_pass():
     return GRAD_TWO_PASS and GRAD_PRECISION == "f16x3"
 
 
-def _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far):
-    """(rgb, disp, acc, saved tensors for the backward)."""
+def _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far, retraw=False):
+    """(rgb, disp, acc, saved tensors for the backward); with retraw at a generic width: (rgb, disp, acc, saved, raw)."""
     if eng.width != 128:
         # the register-resident gradient kernels (and their saved state) are netwidth 128: other widths render as usual and the
-        # backward is the stateless generic-width gradient, which recomputes the forward layer by layer in exact fp32
-        rgb, disp, acc, _ = eng.render_rays(o, d, hist, Nc, Ni, near, far)
-        return rgb, disp, acc, (o, d, v, hist, torch.tensor([Nc, Ni, near, far, float(eng.lindisp)], dtype=torch.float64))
+        # backward is the stateless generic-width gradient, which recomputes the forward layer by layer in exact fp32.  At
+        # netwidth 256 (fast render kernels) GRAD_FORWARD_PRECISION, when set, names the arithmetic of this tracked forward.
+        prec = GRAD_FORWARD_PRECISION if eng.fast else None
+        rgb, disp, acc, raw = eng.render_rays(o, d, hist, Nc, Ni, near, far, retraw=retraw, precision=prec)
+        saved = (o, d, v, hist, torch.tensor([Nc, Ni, near, far, float(eng.lindisp)], dtype=torch.float64))
+        return (rgb, disp, acc, saved, raw) if retraw else (rgb, disp, acc, saved)
     if _two_pass():
         rgb, disp, acc, z, raw, masks = eng.render_rays_saving(o, d, v, hist, Nc, Ni, near, far, precision=GRAD_FORWARD_PRECISION,
                                                              with_masks=True)
@@ -80,13 +83,16 @@ def _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far):
 
 
 def _saved_backward(eng, saved, g_rgb, g_raw=None):
-    if g_rgb is None:
-        g_rgb = torch.zeros(saved[0].shape[0], 3, device=saved[0].device)
     if len(saved) == 5:   # generic width: (rays, viewdirs = d / |d|, histograms, [Nc, Ni, near, far])
         o, d, _, hist, cfg = saved
         Nc, Ni, near, far, lindisp = cfg.tolist()
         eng.set_render_options(lindisp=bool(lindisp))
-        return eng.render_rays_backward(o, d, hist, int(Nc), int(Ni), near, far, g_rgb.contiguous(), precision="generic")
+        if g_rgb is None and g_raw is None:
+            g_rgb = torch.zeros(o.shape[0], 3, device=o.device)
+        return eng.render_rays_backward(o, d, hist, int(Nc), int(Ni), near, far, None if g_rgb is None else g_rgb.contiguous(),
+                                        precision="generic", grad_raw=None if g_raw is None else g_raw.contiguous())
+    if g_rgb is None:
+        g_rgb = torch.zeros(saved[0].shape[0], 3, device=saved[0].device)
     o, d, v, hist, z, raw = saved[:6]
     masks = saved[6] if len(saved) > 6 else None
     return eng.backward_from_saved(o, d, v, hist, z, raw, g_rgb.contiguous(), True, precision=GRAD_PRECISION, masks=masks, grad_raw=g_raw)
@@ -183,14 +189,13 @@ class _RenderRaysFn(torch.autograd.Function):
     def forward(ctx, rays_o, rays_d, eng, hist, Nc, Ni, near, far, retraw=False):
         o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
         v = d / torch.norm(d, dim=-1, keepdim=True)
-        rgb, disp, acc, saved = _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far)
+        rgb, disp, acc, saved, *gen_raw = _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far, retraw=retraw)
         ctx.eng = eng
         ctx.mark_non_differentiable(disp, acc)
         if retraw:
-            if len(saved) == 5:
-                raise NotImplementedError("render(): retraw together with autograd at a network width other than 128 (the generic-width "
-                                          "gradient is stateless and takes d L/d rgb only)")
-            raw = saved[5].clone()    # the caller's tensor: an in-place edit of it must not reach the state the backward reads
+            # the caller's tensor: an in-place edit of it must not reach the state the backward reads (generic widths keep no raw: the
+            # stateless gradient recomputes it, so the rendered tensor is the caller's own)
+            raw = gen_raw[0] if len(saved) == 5 else saved[5].clone()
             ctx.save_for_backward(*saved)
             return rgb, disp, acc, raw
         ctx.save_for_backward(*saved)

@@ -565,6 +565,13 @@ size_t dfn_nerfh_generic_workspace_bytes(dfn_nerfh_t h, size_t n_rays, int Nc, i
 int dfn_nerfh_generic_render_rays(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* hist, size_t hist_rows,
                                   size_t n_rays, int Nc, int Ni, float near, float far, float* rgb, float* disp, float* acc,
                                   float* raw, void* workspace, size_t workspace_bytes, void* stream);
+/* The same render with explicit view directions (models/rendering.py:364-371: render() derives them from the rays BEFORE
+ * c2w_staticcam / ndc replace those rays): viewdirs [n_rays, 3] enter the fine network's direction encoding as given (not
+ * renormalised; the reference normalises first, the caller does the same); viewdirs == NULL: d/|d|, i.e. exactly
+ * dfn_nerfh_generic_render_rays, which calls this entry with NULL.  Same workspace (dfn_nerfh_generic_workspace_bytes). */
+int dfn_nerfh_generic_render_rays_v(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs, const float* hist,
+                                    size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far, float* rgb, float* disp,
+                                    float* acc, float* raw, void* workspace, size_t workspace_bytes, void* stream);
 /* The gradient of that render for ANY even netwidth (what dfn_render_rays_backward is for netwidth 128): d L / d rays_o,
  * d L / d rays_d [n_rays, 3] from grad_rgb [n_rays, 3]; viewdirs == NULL: they are d/|d| and the normalisation is differentiated
  * into grad_rays_d, otherwise grad_viewdirs (optional) receives their gradient.  Exact fp32; recomputes the forward keeping the
@@ -575,6 +582,17 @@ int dfn_nerfh_generic_render_rays_backward(dfn_nerfh_t h, const float* rays_o, c
                                            const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near,
                                            float far, const float* grad_rgb, float* grad_rays_o, float* grad_rays_d,
                                            float* grad_viewdirs, void* workspace, size_t workspace_bytes, void* stream);
+/* That gradient with d L / d raw as well: render(retraw=True) under autograd (models/rendering.py:318-320: extras['raw'] is part of
+ * the graph; :364-371 for the view directions).  grad_raw [n_rays, Nc+Ni, 9] is d L / d of the RETURNED raw (post-activation: the
+ * sigmoid / softplus outputs, in raw's layout); it is added to the compositor's d L / d raw inside the compositing-backward kernel,
+ * before the head derivatives.  grad_rgb and grad_raw are each optional (grad_rgb == NULL: a loss on raw alone, the compositor scan
+ * is skipped); both NULL is DFN_ERR_ARG.  grad_raw == NULL is exactly dfn_nerfh_generic_render_rays_backward, which calls this
+ * body.  Same workspace (dfn_nerfh_generic_backward_workspace_bytes); no allocation, no synchronisation. */
+int dfn_nerfh_generic_render_rays_backward_raw(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                               const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near,
+                                               float far, const float* grad_rgb, const float* grad_raw, float* grad_rays_o,
+                                               float* grad_rays_d, float* grad_viewdirs, void* workspace, size_t workspace_bytes,
+                                               void* stream);
 
 /* The three fp32-MFMA products of the training path, for parity tests (torch.nn.functional.linear and its autograd):
  *   y[p, n]  = act(sum_k x[p / x_row_div, k] w[n, wcol + k] + b[n])   act: 0 none, 1 ReLU, 2 Sigmoid, 3 Softplus
