@@ -33,6 +33,15 @@ class AdamTensor(Structure):
                 ("step_size", c_float), ("bias_correction2_sqrt", c_float)]
 
 
+class RenderMaps(Structure):
+    """dfn_render_maps (include/dfnet_hip.h): optional per-ray outputs of the *_maps entries, NULL = not wanted"""
+    _fields_ = [("depth", c_void_p), ("depth_static", c_void_p), ("beta", c_void_p), ("rgb_static", c_void_p),
+                ("rgb_transient", c_void_p)]
+
+
+MAP_NAMES = tuple(n for n, _ in RenderMaps._fields_)   # trailing shape: () for the first three, (3,) for the rgb_* maps
+
+
 # name -> (restype, argtypes); mirrors include/dfnet_hip.h one to one
 _P = c_void_p
 SIGNATURES = {
@@ -68,6 +77,12 @@ SIGNATURES = {
                                 _P, _P, _P, _P, _P, c_size_t, _P]),
     "dfn_render_image": (c_int, [_P, c_int, _P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, _P,
                                  _P, _P, _P, _P, c_size_t, _P]),
+    "dfn_render_maps_workspace_bytes": (c_size_t, [c_size_t, c_int, c_int]),
+    "dfn_render_rays_maps": (c_int, [_P, c_int, _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, c_float, c_float,
+                                     _P, _P, _P, _P, _P, c_size_t, POINTER(RenderMaps), _P]),
+    "dfn_render_image_maps": (c_int, [_P, c_int, _P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, _P,
+                                      _P, _P, _P, _P, c_size_t, POINTER(RenderMaps), _P]),
+    "dfn_composite_fine_maps": (c_int, [_P, _P, c_size_t, c_int, c_float, POINTER(RenderMaps), _P]),
     "dfn_composite_fine_backward": (c_int, [_P, _P, _P, c_size_t, c_int, _P, _P]),
     "dfn_mlp_fine_backward": (c_int, [_P, c_int, _P, _P, _P, _P, c_size_t, c_size_t, _P, c_int, _P, _P, _P, _P]),
     "dfn_mlp_fine_mask_bytes": (c_size_t, [c_size_t]),
@@ -134,6 +149,8 @@ SIGNATURES = {
                                               _P, c_size_t, _P]),
     "dfn_nerfh_generic_render_rays_v": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, c_float, c_float, _P, _P, _P, _P,
                                                 _P, c_size_t, _P]),
+    "dfn_nerfh_generic_render_rays_maps": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, c_float, c_float, _P, _P, _P, _P,
+                                                   _P, c_size_t, POINTER(RenderMaps), _P]),
     "dfn_nerfh_generic_backward_workspace_bytes": (c_size_t, [_P, c_size_t, c_int, c_int]),
     "dfn_nerfh_generic_render_rays_backward": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P,
                                                c_size_t, _P]),

@@ -870,6 +870,18 @@ extern "C" int dfn_composite_fine(const float* raw, const float* z, size_t n_ray
   return DFN_OK;
 }
 
+// dfn_render_maps -> the kernels' MapPtrs; nothing requested (NULL or five NULL members) = no maps at all
+static MapPtrs map_ptrs(const dfn_render_maps* m) {
+  return m ? MapPtrs{m->depth, m->depth_static, m->beta, m->rgb_static, m->rgb_transient} : MapPtrs{};
+}
+
+extern "C" int dfn_composite_fine_maps(const float* raw, const float* z, size_t n_rays, int Nf, float beta_min,
+                                       const dfn_render_maps* maps, void* stream) {
+  if (!raw || !z || Nf < 1 || Nf > 512) return set_error(DFN_ERR_ARG, "dfn_composite_fine_maps: bad argument (1 <= Nf <= 512)");
+  CHECK_HIP(launch_composite_fine_maps(raw, z, n_rays, Nf, beta_min, map_ptrs(maps), HS(stream)), "dfn_composite_fine_maps");
+  return DFN_OK;
+}
+
 // ------------------------------------------------------------------------------------------ whole path
 namespace {
 constexpr size_t kMaxChunkRays = 65536;  // rays per internal pass (bounds the raw buffer)
@@ -884,7 +896,7 @@ struct Workspace {
   float *o, *d, *v, *sigma, *z, *raw, *bias, *partial;
   size_t total;
 };
-Workspace carve(char* base, size_t n_rays, int Nc, int Ni, bool own_rays) {
+Workspace carve(char* base, size_t n_rays, int Nc, int Ni, bool own_rays, int rec_floats = 12) {
   const size_t chunk = chunk_rays(n_rays);
   const size_t Nf = size_t(Nc) + Ni;
   Workspace w{};
@@ -897,15 +909,16 @@ Workspace carve(char* base, size_t n_rays, int Nc, int Ni, bool own_rays) {
   w.z = take(chunk * Nf * 4);
   w.raw = take(chunk * Nf * 9 * 4);
   w.bias = take(chunk * ray_bias_floats(kMaxWidth) * 4);
-  w.partial = take(chunk * ((Nf + 31) / 32) * 12 * 4);
+  w.partial = take(chunk * ((Nf + 31) / 32) * rec_floats * 4);   // kMapsRecFloats per segment for the render-maps entries
   w.total = off;
   return w;
 }
 
 int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const float* v, const float* hist,
                 size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far, float* rgb, float* disp,
-                float* acc, float* raw_out, const Workspace& w, hipStream_t s) {
+                float* acc, float* raw_out, const Workspace& w, hipStream_t s, const MapPtrs& maps = MapPtrs{}) {
   const int Nf = Nc + Ni;
+  const bool want_maps = maps.any();   // w.partial then holds kMapsRecFloats floats per segment (carve)
   // Compositing is fused into the fine kernel when a wave's points are one ray segment and raw is not wanted: 64 samples per wave in
   // the f16 variants 0/1/3, 32 in the split-f16 and fp32 kernels (one point block per wave); the 3-block f16 variant and netwidth
   // 256 keep the separate compositor.
@@ -944,9 +957,15 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
       MlpArgs a{nf.blob, nf.tab, nf.n_units, co, cd, w.z, w.bias, raw, fused ? w.partial : nullptr, (long long)n, Nf, 0.f, 0.f, g_timing_buf, nf.in_scale};
       a.status = range_flag_of(h);
       ScopedTimer t(1, s);
-      CHECK_HIP(launch_mlp(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP");
+      if (fused && want_maps) CHECK_HIP(launch_mlp_maps(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP (maps)");
+      else CHECK_HIP(launch_mlp(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP");
     }
-    if (fused) {
+    if (fused && want_maps) {
+      ScopedTimer t(DFN_PROF_COMBINE, s);
+      CHECK_HIP(launch_composite_combine_maps(w.partial, n, Nf / seg, 0.1f, DFN_COMP_TEST_TIME | DFN_COMP_STATIC_ONLY, rgb + r0 * 3,
+                                              disp + r0, acc + r0, maps.at(r0), s),
+                "render: composite combine (maps)");
+    } else if (fused) {
       ScopedTimer t(DFN_PROF_COMBINE, s);
       CHECK_HIP(launch_composite_combine(w.partial, n, Nf / seg, 0.1f, DFN_COMP_TEST_TIME | DFN_COMP_STATIC_ONLY, rgb + r0 * 3,
                                          disp + r0, acc + r0, s),
@@ -956,6 +975,7 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
       CHECK_HIP(launch_composite_fine(raw, w.z, n, Nf, 0.1f, DFN_COMP_TEST_TIME | DFN_COMP_STATIC_ONLY, rgb + r0 * 3,
                                       disp + r0, acc + r0, nullptr, nullptr, nullptr, s),
                 "render: composite");
+      if (want_maps) CHECK_HIP(launch_composite_fine_maps(raw, w.z, n, Nf, 0.1f, maps.at(r0), s), "render: composite (maps)");
     }
   }
   return DFN_OK;
@@ -972,41 +992,77 @@ extern "C" size_t dfn_render_workspace_bytes(size_t n_rays, int Nc, int Ni) {
   return carve(nullptr, n_rays ? n_rays : 1, Nc, Ni, true).total;
 }
 
+// dfn_render_rays / dfn_render_rays_maps (`fn`: the name the messages carry; no map requested: the plain entry's launches)
+static int render_rays_entry(const char* fn, dfn_nerfh_t h, int prec, const float* rays_o, const float* rays_d, const float* viewdirs,
+                             const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
+                             float* rgb, float* disp, float* acc, float* raw, void* workspace, size_t workspace_bytes,
+                             const MapPtrs& maps, void* stream) {
+  if (int rc = check_net(h, prec, fn, true)) return rc;
+  if (int rc = check_render_args(Nc, Ni, fn)) return rc;
+  if (!n_rays) return DFN_OK;  // an empty batch is valid (its buffers may be null)
+  if (!rays_o || !rays_d || !hist || !rgb || !disp || !acc || !workspace || (hist_rows != 1 && hist_rows != n_rays))
+    return set_error(DFN_ERR_ARG, "%s: bad argument (hist_rows must be 1 or n_rays)", fn);
+  const Workspace w = carve(static_cast<char*>(workspace), n_rays, Nc, Ni, true, maps.any() ? kMapsRecFloats : 12);
+  if (w.total > workspace_bytes)
+    return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.total);
+  const float* v = viewdirs;
+  if (!v) {
+    if (hipError_t e = launch_viewdirs(rays_d, n_rays, w.v, HS(stream)); e != hipSuccess)
+      return set_error(DFN_ERR_HIP, "%s: viewdirs: %s", fn, hipGetErrorString(e));
+    v = w.v;
+  }
+  return render_core(h, prec, rays_o, rays_d, v, hist, hist_rows, n_rays, Nc, Ni, near, far, rgb, disp, acc, raw, w,
+                     HS(stream), maps);
+}
+
+static int render_image_entry(const char* fn, dfn_nerfh_t h, int prec, const float* c2w, int H, int W, float focal, float near,
+                              float far, int Nc, int Ni, const float* hist, float* rgb, float* disp, float* acc,
+                              void* workspace, size_t workspace_bytes, const MapPtrs& maps, void* stream) {
+  if (int rc = check_net(h, prec, fn, true)) return rc;
+  if (int rc = check_render_args(Nc, Ni, fn)) return rc;
+  if (!c2w || !hist || !rgb || !disp || !acc || !workspace || H < 1 || W < 1 || !(focal > 0))
+    return set_error(DFN_ERR_ARG, "%s: bad argument", fn);
+  const size_t n_rays = size_t(H) * W;
+  const Workspace w = carve(static_cast<char*>(workspace), n_rays, Nc, Ni, true, maps.any() ? kMapsRecFloats : 12);
+  if (w.total > workspace_bytes)
+    return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.total);
+  if (hipError_t e = launch_raygen(H, W, focal, c2w, w.o, w.d, w.v, HS(stream)); e != hipSuccess)
+    return set_error(DFN_ERR_HIP, "%s: raygen: %s", fn, hipGetErrorString(e));
+  return render_core(h, prec, w.o, w.d, w.v, hist, 1, n_rays, Nc, Ni, near, far, rgb, disp, acc, nullptr, w, HS(stream), maps);
+}
+
 extern "C" int dfn_render_rays(dfn_nerfh_t h, int prec, const float* rays_o, const float* rays_d, const float* viewdirs,
                                const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
                                float* rgb, float* disp, float* acc, float* raw, void* workspace, size_t workspace_bytes,
                                void* stream) {
-  if (int rc = check_net(h, prec, "dfn_render_rays", true)) return rc;
-  if (int rc = check_render_args(Nc, Ni, "dfn_render_rays")) return rc;
-  if (!n_rays) return DFN_OK;  // an empty batch is valid (its buffers may be null)
-  if (!rays_o || !rays_d || !hist || !rgb || !disp || !acc || !workspace || (hist_rows != 1 && hist_rows != n_rays))
-    return set_error(DFN_ERR_ARG, "dfn_render_rays: bad argument (hist_rows must be 1 or n_rays)");
-  if (!n_rays) return DFN_OK;
-  const Workspace w = carve(static_cast<char*>(workspace), n_rays, Nc, Ni, true);
-  if (w.total > workspace_bytes)
-    return set_error(DFN_ERR_ARG, "dfn_render_rays: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  const float* v = viewdirs;
-  if (!v) {
-    CHECK_HIP(launch_viewdirs(rays_d, n_rays, w.v, HS(stream)), "dfn_render_rays: viewdirs");
-    v = w.v;
-  }
-  return render_core(h, prec, rays_o, rays_d, v, hist, hist_rows, n_rays, Nc, Ni, near, far, rgb, disp, acc, raw, w,
-                     HS(stream));
+  return render_rays_entry("dfn_render_rays", h, prec, rays_o, rays_d, viewdirs, hist, hist_rows, n_rays, Nc, Ni, near, far, rgb, disp,
+                           acc, raw, workspace, workspace_bytes, MapPtrs{}, stream);
 }
 
 extern "C" int dfn_render_image(dfn_nerfh_t h, int prec, const float* c2w, int H, int W, float focal, float near,
                                 float far, int Nc, int Ni, const float* hist, float* rgb, float* disp, float* acc,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_net(h, prec, "dfn_render_image", true)) return rc;
-  if (int rc = check_render_args(Nc, Ni, "dfn_render_image")) return rc;
-  if (!c2w || !hist || !rgb || !disp || !acc || !workspace || H < 1 || W < 1 || !(focal > 0))
-    return set_error(DFN_ERR_ARG, "dfn_render_image: bad argument");
-  const size_t n_rays = size_t(H) * W;
-  const Workspace w = carve(static_cast<char*>(workspace), n_rays, Nc, Ni, true);
-  if (w.total > workspace_bytes)
-    return set_error(DFN_ERR_ARG, "dfn_render_image: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  CHECK_HIP(launch_raygen(H, W, focal, c2w, w.o, w.d, w.v, HS(stream)), "dfn_render_image: raygen");
-  return render_core(h, prec, w.o, w.d, w.v, hist, 1, n_rays, Nc, Ni, near, far, rgb, disp, acc, nullptr, w, HS(stream));
+  return render_image_entry("dfn_render_image", h, prec, c2w, H, W, focal, near, far, Nc, Ni, hist, rgb, disp, acc, workspace,
+                            workspace_bytes, MapPtrs{}, stream);
+}
+
+extern "C" size_t dfn_render_maps_workspace_bytes(size_t n_rays, int Nc, int Ni) {
+  return carve(nullptr, n_rays ? n_rays : 1, Nc, Ni, true, kMapsRecFloats).total;
+}
+
+extern "C" int dfn_render_rays_maps(dfn_nerfh_t h, int prec, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                    const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
+                                    float* rgb, float* disp, float* acc, float* raw, void* workspace, size_t workspace_bytes,
+                                    const dfn_render_maps* maps, void* stream) {
+  return render_rays_entry("dfn_render_rays_maps", h, prec, rays_o, rays_d, viewdirs, hist, hist_rows, n_rays, Nc, Ni, near, far, rgb,
+                           disp, acc, raw, workspace, workspace_bytes, map_ptrs(maps), stream);
+}
+
+extern "C" int dfn_render_image_maps(dfn_nerfh_t h, int prec, const float* c2w, int H, int W, float focal, float near,
+                                     float far, int Nc, int Ni, const float* hist, float* rgb, float* disp, float* acc,
+                                     void* workspace, size_t workspace_bytes, const dfn_render_maps* maps, void* stream) {
+  return render_image_entry("dfn_render_image_maps", h, prec, c2w, H, W, focal, near, far, Nc, Ni, hist, rgb, disp, acc, workspace,
+                            workspace_bytes, map_ptrs(maps), stream);
 }
 
 // ------------------------------------------------------------------------------------------ gradient path

@@ -15,7 +15,8 @@ struct MlpArgs {
   const float* z;          // fine: [n_rays, n_samples]; coarse: unused (linspace in-kernel)
   const float* ray_bias;   // fine: [n_rays, kRayBiasFloats]
   float* out;              // coarse: sigma [n_rays, n_samples]; fine: raw [n_rays, n_samples, 9]
-  float* partial;          // fine, fused compositing: [n_rays * n_samples / 64][12] per-segment composites (raw unused)
+  float* partial;          // fine, fused compositing: [n_rays * n_samples / 64][12] per-segment composites (raw unused);
+                           // the render-maps flavour (launch_mlp_maps): kMapsRecFloats floats per segment
   long long n_rays;
   int n_samples;
   float near, far;
@@ -29,7 +30,10 @@ struct MlpArgs {
                            // backward-only pass ([tiles][waves][kBwdMaskWords][64 lanes], as BwdArgs::masks); null otherwise
 };
 
+constexpr int kMapsRecFloats = 16;   // segment record of the maps flavour: the 9 floats of the plain one, rgb_static at 9..11, rgb_transient at 12..14
 hipError_t launch_mlp(bool fine, int prec, int variant, const MlpArgs& a, int n_cu, hipStream_t stream, int width = 128);
+// The fine kernel's render-maps flavour (nerfh_mlp_maps.hip): fine = true, a.partial with kMapsRecFloats floats per segment.
+hipError_t launch_mlp_maps(bool fine, int prec, int variant, const MlpArgs& a, int n_cu, hipStream_t stream, int width = 128);
 
 // --- stages (nerfh_stages.hip)
 // (frames > 1: c2w [frames,3,4], outputs [frames,H,W,3] — one launch for the frames of a mini-batch)
@@ -66,6 +70,23 @@ hipError_t launch_composite_fine(const float* raw, const float* z, size_t n_rays
 // Chains the per-64-sample segment composites written by the fused fine kernel: partial [n_rays, segs, 12].
 hipError_t launch_composite_combine(const float* partial, size_t n_rays, int segs, float beta_min, int flags, float* rgb,
                                     float* disp, float* acc, hipStream_t stream);
+
+// Render maps (dfn_render_maps): optional per-ray outputs beside rgb / disp / acc, each null when not wanted.
+struct MapPtrs {
+  float *depth, *depth_static, *beta, *rgb_static, *rgb_transient;
+  bool any() const { return depth || depth_static || beta || rgb_static || rgb_transient; }
+  MapPtrs at(size_t ray) const {   // the same maps from ray `ray` on
+    return MapPtrs{depth ? depth + ray : nullptr, depth_static ? depth_static + ray : nullptr, beta ? beta + ray : nullptr,
+                   rgb_static ? rgb_static + ray * 3 : nullptr, rgb_transient ? rgb_transient + ray * 3 : nullptr};
+  }
+};
+// The maps from raw [n_rays, Nf, 9] and z [n_rays, Nf] in HBM (the non-fused routes and the stage on its own).
+hipError_t launch_composite_fine_maps(const float* raw, const float* z, size_t n_rays, int Nf, float beta_min, const MapPtrs& maps,
+                                      hipStream_t stream);
+// launch_composite_combine over the maps flavour's records (partial [n_rays, segs, kMapsRecFloats]): the same rgb / disp / acc, and
+// the requested maps.
+hipError_t launch_composite_combine_maps(const float* partial, size_t n_rays, int segs, float beta_min, int flags, float* rgb,
+                                         float* disp, float* acc, const MapPtrs& maps, hipStream_t stream);
 
 // --- gradient path (nerfh_bwd.hip, nerfh_stages.hip)
 struct BwdArgs {

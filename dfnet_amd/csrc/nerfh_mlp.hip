@@ -26,6 +26,17 @@
 
 namespace dfn {
 
+// The render-maps flavour of the fine kernel (MAPS below) is compiled in a translation unit of its own: nerfh_mlp_maps.hip includes
+// this file with DFN_MLP_MAPS_TU defined and gets launch_mlp_maps and the MAPS kernels only.  Every translation unit is a code
+// object of its own, so the code object of the kernels that run without maps is the one it was before the maps existed.
+#ifdef DFN_MLP_MAPS_TU
+constexpr bool kMapsTU = true;
+#define DFN_LAUNCH_MLP launch_mlp_maps
+#else
+constexpr bool kMapsTU = false;
+#define DFN_LAUNCH_MLP launch_mlp
+#endif
+
 // Head activations per arithmetic mode: f16 = hardware transcendentals (1e-6), split-f16 = the fp32-grade hardware forms
 // (exp_hw / rcp_nr, 1.5e-7: nerfh_device.h), exact fp32 = libm.
 template <class P, bool FAST> DFN_DEV float head_softplus(float v) { return FAST ? softplus_fast(v) : (P::kSplit ? softplus_hw(v) : softplus(v)); }
@@ -114,9 +125,12 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 // MASKS: the saving forward of the gradient path (dfn_mlp_fine_saving): the same kernel, recording one ReLU sign bit per hidden unit
 // for nerfh_fine_backward_kernel's backward-only pass (its own forward-only mode ran without the pipelined conversion: 3.64 ms for the
 // DFNet_dm step's 3.7 M points against this kernel's 3.1).
-template <class P, bool FAST, int WAVES, int UMB, int NB, bool PIPE, int W = kWidth, bool MASKS = false>
+// MAPS: the render-maps flavour of the fused compositing epilogue (dfn_render_*_maps): the segment record grows from 12 to
+// kMapsRecFloats floats by the static-only and the transient colour sums.  Its own instantiation: the kernels without it are unchanged.
+template <class P, bool FAST, int WAVES, int UMB, int NB, bool PIPE, int W = kWidth, bool MASKS = false, bool MAPS = false>
 __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) void nerfh_fine_kernel(MlpArgs a) {
   static_assert(!MASKS || (P::kSplit && !P::kM16 && NB == 1 && WAVES == 8 && W == kWidth), "the sign masks follow the gradient kernel's tile geometry");
+  static_assert(!MAPS || (!MASKS && W == kWidth && NB <= 2), "the maps flavour exists where the fused compositing does");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int PPT = WAVES * NB * 32;
   constexpr int HC = chunks_of<P>(W / 2), QC = chunks_of<P>(W / 4);
@@ -315,6 +329,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       const bool live = h == 0;
       float Pj = 1.f, Ps = 1.f;                    // running products through the previous blocks of the segment
       float s_rgb[3] = {0.f, 0.f, 0.f}, s_acc = 0.f, s_dso = 0.f, s_dj = 0.f, s_beta = 0.f;
+      [[maybe_unused]] float s_rs[3] = {0.f, 0.f, 0.f}, s_rt[3] = {0.f, 0.f, 0.f};   // MAPS: static-only / transient colour
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         const uint32_t smp = pt_own[nb] - ray_own[nb] * uint32_t(a.n_samples);
@@ -335,6 +350,19 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
         s_dso += as * Ts * z_own[nb];
         s_dj += wj * z_own[nb];
         s_beta += live ? wt * o[nb][8] : 0.f;
+        if constexpr (MAPS) {
+          // rendering.py:218-227 (the static field under its own transmittance), :201-203 (the transient layer under the joint one).
+          // The transient weight goes through an opaque copy: its products must not be shared with s_rgb's, whose rounding
+          // (and so the bits of rgb) stays that of the kernel without the maps.
+          float wt_m = wt;
+          asm volatile("" : "+v"(wt_m));
+          const float wso = as * Ts;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            s_rs[c] += live ? wso * o[nb][c] : 0.f;
+            s_rt[c] += live ? wt_m * o[nb][4 + c] : 0.f;
+          }
+        }
         Pj *= read_lane31(ij);   // lane 31 holds the block's full product
         Ps *= read_lane31(is);
       }
@@ -342,11 +370,21 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       for (int c = 0; c < 3; ++c) s_rgb[c] = read_lane31(scan32_sum(s_rgb[c]));   // lanes 32..63 contribute zeros
       s_acc = read_lane31(scan32_sum(s_acc)); s_dso = read_lane31(scan32_sum(s_dso));
       s_dj = read_lane31(scan32_sum(s_dj)); s_beta = read_lane31(scan32_sum(s_beta));
+      if constexpr (MAPS) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { s_rs[c] = read_lane31(scan32_sum(s_rs[c])); s_rt[c] = read_lane31(scan32_sum(s_rt[c])); }
+      }
       if (st.lane == 0 && pt_own[0] < npts) {
-        f32x4* dst = reinterpret_cast<f32x4*>(a.partial + (size_t)(pt_own[0] / uint32_t(NB * 32)) * 12);   // one segment per wave
+        constexpr int REC = MAPS ? kMapsRecFloats : 12;
+        f32x4* dst = reinterpret_cast<f32x4*>(a.partial + (size_t)(pt_own[0] / uint32_t(NB * 32)) * REC);   // one segment per wave
         dst[0] = f32x4{s_rgb[0], s_rgb[1], s_rgb[2], s_acc};
         dst[1] = f32x4{s_dso, s_dj, s_beta, Pj};
-        dst[2] = f32x4{Ps, 0.f, 0.f, 0.f};
+        if constexpr (MAPS) {
+          dst[2] = f32x4{Ps, s_rs[0], s_rs[1], s_rs[2]};
+          dst[3] = f32x4{s_rt[0], s_rt[1], s_rt[2], 0.f};
+        } else {
+          dst[2] = f32x4{Ps, 0.f, 0.f, 0.f};
+        }
       }
     } else {
 #pragma unroll
@@ -398,11 +436,22 @@ static hipError_t launch_one(bool fine, const MlpArgs& a, int n_cu, hipStream_t 
   const long long slots = (long long)n_cu * WG_PER_CU;  // resident workgroups
   const int grid = int(n_tiles < slots ? n_tiles : slots);
   const uint32_t lds = lds_bytes<P, UMB, WAVES, NB, W>();
-  auto kern = fine ? nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W> : nerfh_coarse_kernel<P, FAST, WAVES, UMB, NB, PIPE, W>;
+  void (*kern)(MlpArgs) = nullptr;
   int slot = fine ? 1 : 0;
-  if constexpr (P::kSplit && !P::kM16 && NB == 1 && WAVES == 8 && W == kWidth && PIPE) {
-    if (fine && a.masks) { kern = nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W, true>; slot = 2; }
-  } else if (a.masks) return hipErrorInvalidValue;
+  if constexpr (kMapsTU) {
+    // render maps: the fused fine kernel with the kMapsRecFloats-float segment record, where the fused compositing exists at all
+    if constexpr (W == kWidth && NB <= 2) {
+      if (!fine || !a.partial || a.masks) return hipErrorInvalidValue;
+      kern = nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W, false, true>;
+    } else {
+      return hipErrorInvalidValue;
+    }
+  } else {
+    kern = fine ? nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W> : nerfh_coarse_kernel<P, FAST, WAVES, UMB, NB, PIPE, W>;
+    if constexpr (P::kSplit && !P::kM16 && NB == 1 && WAVES == 8 && W == kWidth && PIPE) {
+      if (fine && a.masks) { kern = nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W, true>; slot = 2; }
+    } else if (a.masks) return hipErrorInvalidValue;
+  }
   static bool attr_done[3] = {false, false, false};
   if (!attr_done[slot]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -425,9 +474,11 @@ static hipError_t launch_one(bool fine, const MlpArgs& a, int n_cu, hipStream_t 
 // variant 2: 4 waves x NB 3, 1 WG/CU, unit = layer      (1 wave/SIMD, 512 registers, pipelined epilogue)
 // variant 3: variant 0 without the pipelined epilogue (A/B reference)
 // variant 4: split-f16 as variant 0 on 16x16x32 MFMAs (PrecX3M16); f16 and exact fp32 run their variant-0 kernels
+// launch_mlp_maps (this body in nerfh_mlp_maps.hip): the fine kernels' render-maps flavour (fused compositing only: fine, a.partial
+// with kMapsRecFloats floats per segment; the 3-block f16 variant and netwidth 256 have none and are refused).
 // netwidth 256: the plain variants (one point block per wave, no pipelined epilogue); staging units of 2 M-blocks (f16) /
 // 1 M-block (f32, split-f16) keep three buffers inside the 160 KB of LDS (a 256 x 256 f16 layer is 128 KB).
-hipError_t launch_mlp(bool fine, int prec, int variant, const MlpArgs& a, int n_cu, hipStream_t stream, int width) {
+hipError_t DFN_LAUNCH_MLP(bool fine, int prec, int variant, const MlpArgs& a, int n_cu, hipStream_t stream, int width) {
   if (width == 256) {
     if (prec == 0) {
       return launch_one<PrecF16, true, 8, unit_mb_w256<PrecF16>(), 1, 1, false, 256>(fine, a, n_cu, stream);

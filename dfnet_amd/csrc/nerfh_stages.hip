@@ -616,6 +616,153 @@ hipError_t launch_composite_combine(const float* partial, size_t n_rays, int seg
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------ render maps
+// The quantities raw2outputs_NeRFW forms and the test-time render drops (rendering.py:196-241), per ray:
+//   depth = sum a T z (:241)                    depth_static = sum a_s T_s z (:218-228, the numerator of disp)
+//   beta = sum a_t T beta + beta_min (:204-208)
+//   rgb_static = sum a_s T_s c_s (:218-227)     rgb_transient = sum a_t T c_t (:201-203)
+// with T the exclusive product of 1 - a (joint) and T_s that of 1 - a_s.  No white background.
+// From raw in HBM: composite_fine_kernel's staging, alphas and scans; one wave per ray, SPL consecutive samples per lane.
+template <int SPL>
+__global__ __launch_bounds__(256) void composite_fine_maps_kernel(const float* __restrict__ raw, const float* __restrict__ z,
+                                                                  size_t n_rays, int Nf, float beta_min, int staged, MapPtrs m) {
+  extern __shared__ __attribute__((aligned(16))) float craw[];   // per wave: one ray's raw [Nf][9] (when staged)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* sr = craw + size_t(wave) * Nf * 9;
+  for (size_t ray = size_t(blockIdx.x) * 4 + wave; ray < n_rays; ray += size_t(gridDim.x) * 4) {
+    const float* rr = raw + ray * size_t(Nf) * 9;
+    const float* zr = z + ray * size_t(Nf);
+    float v[SPL][9], zz[SPL + 1];
+    if (staged) {
+      const f32x4_t* src = reinterpret_cast<const f32x4_t*>(rr);
+      f32x4_t* dst = reinterpret_cast<f32x4_t*>(sr);
+      for (int i = lane; i < Nf * 9 / 4; i += 64) dst[i] = src[i];
+      wave_sync();
+    }
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+      const int i = lane * SPL + k;
+      zz[k] = i < Nf ? zr[i] : 0.f;
+#pragma unroll
+      for (int c = 0; c < 9; ++c) v[k][c] = i < Nf ? (staged ? sr[i * 9 + c] : rr[size_t(i) * 9 + c]) : 0.f;
+    }
+    if (staged) wave_sync();   // the next ray's staging overwrites the buffer
+    zz[SPL] = __shfl_down(zz[0], 1, 64);
+    float a_s[SPL], a_t[SPL], a_j[SPL];
+    float pj = 1.f, ps = 1.f;
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+      const int i = lane * SPL + k;
+      const float delta = i + 1 < Nf ? sub_rn(zz[k + 1], zz[k]) : 1e2f;
+      const bool ok = i < Nf;
+      a_s[k] = ok ? sub_rn(1.f, expf(-mul_rn(delta, v[k][3]))) : 0.f;
+      a_t[k] = ok ? sub_rn(1.f, expf(-mul_rn(delta, v[k][7]))) : 0.f;
+      a_j[k] = ok ? sub_rn(1.f, expf(-mul_rn(delta, add_rn(v[k][3], v[k][7])))) : 0.f;
+      pj = mul_rn(pj, sub_rn(1.f, a_j[k]));
+      ps = mul_rn(ps, sub_rn(1.f, a_s[k]));
+    }
+    float Tj = __shfl_up(wave_incl_prod(pj, lane), 1, 64);
+    float Ts = __shfl_up(wave_incl_prod(ps, lane), 1, 64);
+    if (lane == 0) { Tj = 1.f; Ts = 1.f; }
+    float s_rs[3] = {0.f, 0.f, 0.f}, s_rt[3] = {0.f, 0.f, 0.f}, s_dj = 0.f, s_dso = 0.f, s_beta = 0.f;
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+      const float wso = mul_rn(a_s[k], Ts), wt = mul_rn(a_t[k], Tj), wj = mul_rn(a_j[k], Tj);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        s_rs[c] += mul_rn(wso, v[k][c]);
+        s_rt[c] += mul_rn(wt, v[k][4 + c]);
+      }
+      s_beta += mul_rn(wt, v[k][8]);
+      s_dso += mul_rn(wso, zz[k]);
+      s_dj += mul_rn(wj, zz[k]);
+      Tj = mul_rn(Tj, sub_rn(1.f, a_j[k]));
+      Ts = mul_rn(Ts, sub_rn(1.f, a_s[k]));
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { s_rs[c] = wave_sum(s_rs[c]); s_rt[c] = wave_sum(s_rt[c]); }
+    s_dj = wave_sum(s_dj);
+    s_dso = wave_sum(s_dso);
+    s_beta = wave_sum(s_beta);
+    if (lane == 0) {
+      if (m.depth) m.depth[ray] = s_dj;
+      if (m.depth_static) m.depth_static[ray] = s_dso;
+      if (m.beta) m.beta[ray] = s_beta + beta_min;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        if (m.rgb_static) m.rgb_static[ray * 3 + c] = s_rs[c];
+        if (m.rgb_transient) m.rgb_transient[ray * 3 + c] = s_rt[c];
+      }
+    }
+  }
+}
+
+hipError_t launch_composite_fine_maps(const float* raw, const float* z, size_t n_rays, int Nf, float beta_min, const MapPtrs& maps,
+                                      hipStream_t stream) {
+  if (!n_rays || !maps.any()) return hipSuccess;
+  const int spl = (Nf + 63) / 64;
+  const dim3 grid(grid_for((n_rays + 3) / 4, 1, 256 * 16)), block(256);
+  size_t lds = size_t(4) * Nf * 9 * sizeof(float);   // the four waves' staged rays
+  const int staged = (Nf & 3) == 0 && (reinterpret_cast<uintptr_t>(raw) & 15) == 0 && lds <= 64 * 1024;
+  if (!staged) lds = 0;
+#define DFN_COMP(S) \
+  hipLaunchKernelGGL(composite_fine_maps_kernel<S>, grid, block, lds, stream, raw, z, n_rays, Nf, beta_min, staged, maps)
+  if (spl <= 1) DFN_COMP(1);
+  else if (spl == 2) DFN_COMP(2);
+  else if (spl == 3) DFN_COMP(3);
+  else if (spl == 4) DFN_COMP(4);
+  else if (spl <= 6) DFN_COMP(6);
+  else if (spl <= 8) DFN_COMP(8);
+  else return hipErrorInvalidValue;
+#undef DFN_COMP
+  return hipGetLastError();
+}
+
+// Fused path: the maps flavour of the fine kernel leaves kMapsRecFloats floats per segment,
+//   [0..2] sum a_s T c_s + a_t T c_t   [3] sum a T   [4] sum a_s T_s z   [5] sum a T z   [6] sum a_t T beta   [7] prod (1 - a)
+//   [8] prod (1 - a_s)   [9..11] sum a_s T_s c_s   [12..14] sum a_t T c_t   [15] unused
+// (T, T_s relative to the segment's start).  Sums under the joint transmittance chain with Tj, the static-only ones with Ts;
+// rgb / disp / acc are composite_combine_kernel's, statement for statement.
+__global__ __launch_bounds__(256) void composite_combine_maps_kernel(const float* __restrict__ partial, size_t n_rays, int segs,
+                                                                     float beta_min, int flags, float* __restrict__ rgb,
+                                                                     float* __restrict__ disp, float* __restrict__ acc, MapPtrs m) {
+  const bool static_depth = (flags & 1) && (flags & 2);
+  for (size_t ray = blockIdx.x * size_t(blockDim.x) + threadIdx.x; ray < n_rays; ray += size_t(gridDim.x) * blockDim.x) {
+    float Tj = 1.f, Ts = 1.f, r = 0.f, g = 0.f, b = 0.f, a = 0.f, d = 0.f;
+    float dj = 0.f, dso = 0.f, be = 0.f, rs[3] = {0.f, 0.f, 0.f}, rt[3] = {0.f, 0.f, 0.f};
+    for (int s = 0; s < segs; ++s) {
+      const float4* q = reinterpret_cast<const float4*>(partial + (ray * segs + s) * kMapsRecFloats);
+      const float4 u = q[0], v = q[1], w = q[2], x = q[3];
+      r += Tj * u.x; g += Tj * u.y; b += Tj * u.z; a += Tj * u.w;
+      d += static_depth ? Ts * v.x : Tj * v.y;
+      dso += Ts * v.x; dj += Tj * v.y; be += Tj * v.z;
+      rs[0] += Ts * w.y; rs[1] += Ts * w.z; rs[2] += Ts * w.w;
+      rt[0] += Tj * x.x; rt[1] += Tj * x.y; rt[2] += Tj * x.z;
+      Tj *= v.w;
+      Ts *= w.x;
+    }
+    const float bg = (flags & 4) ? 1.f - a : 0.f;
+    rgb[ray * 3] = r + bg; rgb[ray * 3 + 1] = g + bg; rgb[ray * 3 + 2] = b + bg;
+    disp[ray] = 1.f / fmaxf(1e-10f, d / a);
+    acc[ray] = a;
+    if (m.depth) m.depth[ray] = dj;
+    if (m.depth_static) m.depth_static[ray] = dso;
+    if (m.beta) m.beta[ray] = be + beta_min;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (m.rgb_static) m.rgb_static[ray * 3 + c] = rs[c];
+      if (m.rgb_transient) m.rgb_transient[ray * 3 + c] = rt[c];
+    }
+  }
+}
+hipError_t launch_composite_combine_maps(const float* partial, size_t n_rays, int segs, float beta_min, int flags, float* rgb,
+                                         float* disp, float* acc, const MapPtrs& maps, hipStream_t stream) {
+  if (!n_rays) return hipSuccess;
+  hipLaunchKernelGGL(composite_combine_maps_kernel, dim3(grid_for(n_rays, 256)), dim3(256), 0, stream, partial, n_rays, segs,
+                     beta_min, flags, rgb, disp, acc, maps);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------ bicubic resize
 // nn.Upsample(size, mode='bicubic') (align_corners=False, A = -0.75, border-replicated taps) on an
 // [H, W, C] image -> [UH, UW, C]: the x4 enlargement of a quarter-resolution render

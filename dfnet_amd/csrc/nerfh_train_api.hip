@@ -499,7 +499,8 @@ namespace {
 // `entry`: the public name the messages carry (the two entries share this body; viewdirs == nullptr: d / |d|, written to w.view)
 int generic_render_rays_impl(const char* entry, dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
                              const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far, float* rgb,
-                             float* disp, float* acc, float* raw, void* workspace, size_t workspace_bytes, void* stream) {
+                             float* disp, float* acc, float* raw, void* workspace, size_t workspace_bytes, void* stream,
+                             const dfn_render_maps* maps = nullptr) {
   if (int rc = check_train_args(h, Nc, Ni, entry)) return rc;
   if (!h->committed) return set_error(DFN_ERR_STATE, "%s: dfn_nerfh_commit() has not been called", entry);
   if (!n_rays) return DFN_OK;
@@ -535,6 +536,10 @@ int generic_render_rays_impl(const char* entry, dfn_nerfh_t h, const float* rays
   CHECK_HIP(launch_composite_fine(raw, w.z_f, R, Nf, 0.1f, DFN_COMP_TEST_TIME | DFN_COMP_STATIC_ONLY, rgb, disp, acc, nullptr, nullptr,
                                   nullptr, s),
             "generic render: composite");
+  if (maps)   // rendering.py:196-241: the maps the compositor above does not return, from the same raw (nothing requested: no launch)
+    CHECK_HIP(launch_composite_fine_maps(raw, w.z_f, R, Nf, 0.1f,
+                                         MapPtrs{maps->depth, maps->depth_static, maps->beta, maps->rgb_static, maps->rgb_transient}, s),
+              "generic render: composite (maps)");
   return DFN_OK;
 }
 }  // namespace
@@ -553,6 +558,15 @@ extern "C" int dfn_nerfh_generic_render_rays_v(dfn_nerfh_t h, const float* rays_
                                                void* stream) {
   return generic_render_rays_impl("dfn_nerfh_generic_render_rays_v", h, rays_o, rays_d, viewdirs, hist, hist_rows, n_rays, Nc, Ni, near,
                                   far, rgb, disp, acc, raw, workspace, workspace_bytes, stream);
+}
+
+// The same render with the maps of models/rendering.py:196-241 (dfn_render_maps) from the raw it leaves in HBM.
+extern "C" int dfn_nerfh_generic_render_rays_maps(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                                  const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near,
+                                                  float far, float* rgb, float* disp, float* acc, float* raw, void* workspace,
+                                                  size_t workspace_bytes, const dfn_render_maps* maps, void* stream) {
+  return generic_render_rays_impl("dfn_nerfh_generic_render_rays_maps", h, rays_o, rays_d, viewdirs, hist, hist_rows, n_rays, Nc, Ni,
+                                  near, far, rgb, disp, acc, raw, workspace, workspace_bytes, stream, maps);
 }
 
 // ------------------------------------------------------------------------------------------ generic-width render gradient

@@ -44,6 +44,35 @@ def _f32c(t):
     return t.contiguous().float()
 
 
+MAP_NAMES = _lib.MAP_NAMES   # depth, depth_static, beta [n]; rgb_static, rgb_transient [n,3] (models/rendering.py:196-241)
+
+
+def map_names(maps):
+    """The render maps a caller asks for, in the library's order: True = all five, False / None = none, or an iterable of names."""
+    if maps is True:
+        return MAP_NAMES
+    if maps is False or maps is None:
+        return ()
+    if isinstance(maps, str):
+        maps = (maps,)
+    maps = tuple(maps)
+    unknown = [m for m in maps if m not in MAP_NAMES]
+    if unknown:
+        raise ValueError(f"unknown render map(s) {unknown}: the maps are {list(MAP_NAMES)}")
+    return tuple(m for m in MAP_NAMES if m in maps)
+
+
+def _alloc_maps(names, n, dev):
+    """({name: tensor [n] / [n,3]}, the dfn_render_maps struct pointing at them)."""
+    out = {m: torch.empty((n, 3) if m.startswith("rgb_") else (n,), device=dev) for m in names}
+    return out, _lib.RenderMaps(**{m: t.data_ptr() for m, t in out.items()})
+
+
+def _maps_at(out, r0, m):
+    """The struct for rows [r0, r0 + m) of the maps in `out`."""
+    return _lib.RenderMaps(**{k: t[r0:r0 + m].data_ptr() for k, t in out.items()})
+
+
 class NerfHEngine:
     """NeRF-H coarse+fine networks resident on one GPU in MFMA-fragment layout."""
 
@@ -262,6 +291,96 @@ class NerfHEngine:
               "dfn_render_image")
         return rgb, disp, acc
 
+
+    # ------------------------------------------------------------------ render maps
+    def generic_render_rays_maps(self, rays_o, rays_d, hist, Nc, Ni, near, far, retraw=False, viewdirs=None, maps=MAP_NAMES):
+        """generic_render_rays with the requested maps (dfn_nerfh_generic_render_rays_maps), chunked the same way:
+        (rgb, disp, acc, raw|None, {name: map})."""
+        names = map_names(maps)
+        rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
+        n, dev = rays_o.shape[0], rays_o.device
+        if viewdirs is not None:
+            viewdirs = _f32c(viewdirs).reshape(-1, 3)
+            if viewdirs.shape[0] != n:
+                raise ValueError(f"viewdirs must have {n} rows, got {tuple(viewdirs.shape)}")
+        hist = _f32c(hist).reshape(-1, self.hist_bin)
+        rgb, disp, acc = torch.empty(n, 3, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev)
+        out, _ = _alloc_maps(names, n, dev)
+        Nf = Nc + Ni
+        raw_all = torch.empty(n, Nf, 9, device=dev) if retraw else None
+        C = self.GENERIC_CHUNK
+        ws = self._workspace(self.lib.dfn_nerfh_generic_workspace_bytes(self.handle, min(n, C), Nc, Ni), dev)
+        raw_tmp = None if retraw else torch.empty(min(n, C), Nf, 9, device=dev)
+        for r0 in range(0, n, C):
+            m = min(C, n - r0)
+            h = hist if hist.shape[0] == 1 else hist[r0:r0 + m]
+            raw = raw_all[r0:r0 + m] if retraw else raw_tmp[:m]
+            v = None if viewdirs is None else viewdirs[r0:r0 + m]
+            st = _maps_at(out, r0, m)
+            check(self.lib.dfn_nerfh_generic_render_rays_maps(self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(v), ptr(h),
+                                                              h.shape[0], m, Nc, Ni, float(near), float(far), ptr(rgb[r0:r0 + m]),
+                                                              ptr(disp[r0:r0 + m]), ptr(acc[r0:r0 + m]), ptr(raw),
+                                                              ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.byref(st),
+                                                              current_stream()),
+                  "dfn_nerfh_generic_render_rays_maps")
+        return rgb, disp, acc, raw_all, out
+
+    def render_rays_maps(self, rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs=None, retraw=False, precision=None, maps=MAP_NAMES):
+        """render_rays that also returns the maps the compositor forms and the plain render drops (models/rendering.py:196-241):
+        (rgb [n,3], disp [n], acc [n], raw|None, {name: map}) with depth, depth_static, beta [n] and rgb_static, rgb_transient [n,3].
+        maps: an iterable of those names (default: all five).  rgb / disp / acc are the bits render_rays returns."""
+        if not self.fast or precision == "generic":
+            return self.generic_render_rays_maps(rays_o, rays_d, hist, Nc, Ni, near, far, retraw, viewdirs=viewdirs, maps=maps)
+        names = map_names(maps)
+        rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
+        n = rays_o.shape[0]
+        dev = rays_o.device
+        hist = _f32c(hist).reshape(-1, self.hist_bin)
+        if viewdirs is not None:
+            viewdirs = _f32c(viewdirs).reshape(-1, 3)
+        rgb = torch.empty(n, 3, device=dev)
+        disp = torch.empty(n, device=dev)
+        acc = torch.empty(n, device=dev)
+        raw = torch.empty(n, Nc + Ni, 9, device=dev) if retraw else None
+        out, st = _alloc_maps(names, n, dev)
+        ws = self._workspace(self.lib.dfn_render_maps_workspace_bytes(n, Nc, Ni), dev)
+        check(self.lib.dfn_render_rays_maps(self.handle, self._prec(precision), ptr(rays_o), ptr(rays_d), ptr(viewdirs),
+                                            ptr(hist), hist.shape[0], n, Nc, Ni, float(near), float(far), ptr(rgb),
+                                            ptr(disp), ptr(acc), ptr(raw), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                            ctypes.byref(st), current_stream()), "dfn_render_rays_maps")
+        return rgb, disp, acc, raw, out
+
+    def render_image_maps(self, c2w, H, W, focal, hist, Nc, Ni, near, far, precision=None, out=None, maps=MAP_NAMES):
+        """render_image with the maps of render_rays_maps, shaped like the image: (rgb [H,W,3], disp, acc [H,W], None,
+        {name: [H,W] or [H,W,3]})."""
+        names = map_names(maps)
+        c2w = _f32c(c2w)[:3, :4].contiguous()
+        dev = c2w.device
+        hist = _f32c(hist).reshape(-1)[: self.hist_bin].contiguous()
+        shaped = lambda d: {k: v.reshape(H, W, *v.shape[1:]) for k, v in d.items()}
+        if not self.fast or precision == "generic":
+            o, d, _ = raygen(H, W, focal, c2w, want_viewdirs=False)
+            rgb, disp, acc, _, mp = self.generic_render_rays_maps(o.reshape(-1, 3), d.reshape(-1, 3), hist, Nc, Ni, near, far, maps=names)
+            res = (rgb.reshape(H, W, 3), disp.reshape(H, W), acc.reshape(H, W))
+            if out is not None:
+                for dst, src in zip(out, res):
+                    dst.copy_(src)
+                res = tuple(out)
+            return res + (None, shaped(mp))
+        if out is None:
+            out = (torch.empty(H, W, 3, device=dev), torch.empty(H, W, device=dev), torch.empty(H, W, device=dev))
+        rgb, disp, acc = out
+        mp, st = _alloc_maps(names, H * W, dev)
+        ws = self._workspace(self.lib.dfn_render_maps_workspace_bytes(H * W, Nc, Ni), dev)
+        check(self.lib.dfn_render_image_maps(self.handle, self._prec(precision), ptr(c2w), H, W, float(focal), float(near),
+                                             float(far), Nc, Ni, ptr(hist), ptr(rgb), ptr(disp), ptr(acc),
+                                             ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.byref(st), current_stream()),
+              "dfn_render_image_maps")
+        return rgb, disp, acc, None, shaped(mp)
+
+    def composite_fine_maps(self, raw, z, beta_min=0.1, maps=MAP_NAMES):
+        """The maps from raw [n,Nf,9] and z [n,Nf] (the module-level composite_fine_maps)."""
+        return composite_fine_maps(raw, z, beta_min, maps)
 
     # ------------------------------------------------------------------ staged render that keeps what backward needs
     def render_rays_saving(self, rays_o, rays_d, viewdirs, hist, Nc, Ni, near, far, precision=None, with_masks=False):
@@ -786,6 +905,17 @@ def composite_fine(raw, z, beta_min=0.1, test_time=True, static_only=True, white
     out = dict(rgb=rgb, disp=disp, acc=acc)
     if want_aux:
         out.update(depth=depth, weights=w, beta=beta)
+    return out
+
+
+def composite_fine_maps(raw, z, beta_min=0.1, maps=MAP_NAMES):
+    """{name: map} of the requested render maps (models/rendering.py:196-241) from raw [n,Nf,9] and z [n,Nf]: depth, depth_static,
+    beta [n]; rgb_static, rgb_transient [n,3] (dfn_composite_fine_maps)."""
+    raw, z = _f32c(raw), _f32c(z)
+    n, Nf = z.shape
+    out, st = _alloc_maps(map_names(maps), n, raw.device)
+    check(_lib.load().dfn_composite_fine_maps(ptr(raw), ptr(z), n, Nf, float(beta_min), ctypes.byref(st), current_stream()),
+          "dfn_composite_fine_maps")
     return out
 
 

@@ -215,13 +215,15 @@ def _set_options(eng, kw, near):
     eng.set_render_options(lindisp=lindisp)
 
 
-def _check_test_time(kw, ndc, c2w_staticcam, use_viewdirs, training=False, tracked=False):
+def _check_test_time(kw, ndc, c2w_staticcam, use_viewdirs, training=False, tracked=False, ret_maps=False):
     bad = []
     if kw.get('white_bkgd', False):
         raise TypeError("render(): white_bkgd=True is not a working option of the NeRF-H path: the reference hands it to the coarse "
                         "compositor as output_transient (models/rendering.py:295) and fails the same way")
     if (ndc or c2w_staticcam is not None) and (training or tracked):
         bad.append("ndc / c2w_staticcam together with " + ("training-mode rendering" if training else "autograd"))
+    if ret_maps and (training or tracked):
+        bad.append("ret_maps together with " + ("training-mode rendering" if training else "autograd (the maps are not differentiable)"))
     if not training:
         if not kw.get('test_time', False):
             bad.append("test_time=False without a trainer (render kwargs must come from create_nerf with gradient updates enabled)")
@@ -239,19 +241,25 @@ def _check_test_time(kw, ndc, c2w_staticcam, use_viewdirs, training=False, track
 
 
 def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
-           c2w_staticcam=None, img_idx=torch.Tensor(0), **kwargs):
+           c2w_staticcam=None, img_idx=torch.Tensor(0), ret_maps=False, **kwargs):
     """Drop-in for rendering.py:353-400.  Returns [rgb_map, disp_map, acc_map, extras].
+
+    ret_maps (beyond the reference, test time without autograd only): True, or an iterable of names out of depth, depth_static, beta,
+    rgb_static, rgb_transient — the maps raw2outputs_NeRFW forms and the reference drops (rendering.py:196-241) are added to
+    `extras` under those names, shaped like the rays ([H,W] / [H,W,3] for c2w).
 
     c2w given: full image, outputs [H,W,3], [H,W], [H,W].  Otherwise `rays` = (rays_o, rays_d) (a tuple
     or a stacked [2,N,3] tensor), outputs shaped like rays_d[..., :1].  `img_idx`: the 10-bin histogram
     index vector, shape [10], [1,10] or [N,10]."""
     eng = _engine_of(kwargs)
     _set_options(eng, kwargs, near)
+    from .engine import map_names
+    map_list = map_names(ret_maps)
     trainer = getattr(kwargs.get('network_query_fn'), 'trainer', None)
     if not kwargs.get('test_time', False) and trainer is not None:
         # training mode (rendering.py:245-337 with test_time=False): stratified depths, coarse rgb + noise, importance sampling
         # with random u, the training extras — on the exact-fp32 training kernels, attached to autograd (nerf_train.py)
-        _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, training=True)
+        _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, training=True, ret_maps=bool(map_list))
         # The reference's training render is differentiable w.r.t. its rays / pose too: rays that require grad make the autograd node
         # run the exact-fp32 step and return d L / d rays (nerf_train._RenderTrainFn); c2w reaches them through get_rays' own node.
         from . import nerf_train
@@ -283,11 +291,24 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
             return t.requires_grad
         return isinstance(t, (tuple, list)) and any(_needs_grad(u) for u in t)
     track = torch.is_grad_enabled() and (_needs_grad(c2w) or _needs_grad(rays))
-    _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, tracked=track)
+    _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, tracked=track, ret_maps=bool(map_list))
     Nc, Ni = int(kwargs['N_samples']), int(kwargs['N_importance'])
     retraw = bool(kwargs.get('retraw', False))
     dev = torch.device("cuda", torch.cuda.current_device())
     hist = torch.as_tensor(img_idx, dtype=torch.float32, device=dev)
+
+    def _rays(o, d, h, lead, view=None):
+        """The untracked ray render; with ret_maps through the maps entry (the same rgb / disp / acc bits)."""
+        if map_list:
+            rgb, disp, acc, raw, mp = eng.render_rays_maps(o, d, h, Nc, Ni, near, far, viewdirs=view, retraw=retraw, maps=map_list)
+            extras = {k: v.reshape(lead + list(v.shape[1:])) for k, v in mp.items()}
+        else:
+            rgb, disp, acc, raw = eng.render_rays(o, d, h, Nc, Ni, near, far, viewdirs=view, retraw=retraw)
+            extras = {}
+        if retraw:
+            extras['raw'] = raw.reshape(lead + list(raw.shape[1:]))
+        return [rgb.reshape(lead + [3]), disp.reshape(lead), acc.reshape(lead), extras]
+
     if ndc or c2w_staticcam is not None:
         # rendering.py:364-376: the view directions come from the given rays / pose; the rays themselves are then replaced by the
         # static camera's and / or mapped to normalised device coordinates (ndc_rays at near = 1)
@@ -302,11 +323,7 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         if ndc:
             rays_o, rays_d = ndc_rays(H, W, focal, 1., rays_o, rays_d)
         hist = hist.reshape(-1, eng.hist_bin)
-        lead = list(rays_d.shape[:-1])
-        rgb, disp, acc, raw = eng.render_rays(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), hist, Nc, Ni, near, far, viewdirs=view,
-                                              retraw=retraw)
-        extras = {'raw': raw.reshape(lead + list(raw.shape[1:]))} if retraw else {}
-        return [rgb.reshape(lead + [3]), disp.reshape(lead), acc.reshape(lead), extras]
+        return _rays(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), hist, list(rays_d.shape[:-1]), view)
     if c2w is not None:
         c2w = torch.as_tensor(c2w, dtype=torch.float32, device=dev)
         if track and not retraw and hist.numel() == eng.hist_bin:
@@ -319,7 +336,10 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
             else:
                 o, d = get_rays(H, W, focal, c2w)
             return render(H, W, focal, chunk, rays=(o, d), ndc=ndc, near=near, far=far, use_viewdirs=use_viewdirs,
-                          img_idx=img_idx, **kwargs)
+                          img_idx=img_idx, ret_maps=map_list, **kwargs)
+        if map_list:
+            rgb, disp, acc, _, mp = eng.render_image_maps(c2w, int(H), int(W), float(focal), hist, Nc, Ni, near, far, maps=map_list)
+            return [rgb, disp, acc, mp]
         rgb, disp, acc = eng.render_image(c2w, int(H), int(W), float(focal), hist, Nc, Ni, near, far)
         return [rgb, disp, acc, {}]
     rays_o, rays_d = rays
@@ -336,10 +356,7 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         rgb, disp, acc = out[:3]
         extras = {'raw': out[3].reshape(lead + list(out[3].shape[1:]))} if retraw else {}
         return [rgb.reshape(lead + [3]), disp.reshape(lead), acc.reshape(lead), extras]
-    rgb, disp, acc, raw = eng.render_rays(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), hist, Nc, Ni, near, far,
-                                          retraw=retraw)
-    extras = {'raw': raw.reshape(lead + list(raw.shape[1:]))} if retraw else {}
-    return [rgb.reshape(lead + [3]), disp.reshape(lead), acc.reshape(lead), extras]
+    return _rays(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), hist, lead)
 
 
 def _write_png(path, arr8):

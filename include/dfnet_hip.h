@@ -179,6 +179,45 @@ int dfn_render_image(dfn_nerfh_t h, int prec, const float* c2w, int H, int W, fl
                      float* disp, float* acc, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ------------------------------------------------------------------ render maps
+ * The per-ray quantities raw2outputs_NeRFW forms beside rgb / disp / acc and render() drops at test time
+ * (models/rendering.py:196-241), with a = 1-exp(-delta (sigma_s+sigma_t)), a_s, a_t the static / transient alphas, T the
+ * exclusive product of 1-a and T_s that of 1-a_s:
+ *   depth         [n]    sum a T z                      rendering.py:241
+ *   depth_static  [n]    sum a_s T_s z                  rendering.py:218-228 (the numerator of disp)
+ *   beta          [n]    sum a_t T beta + beta_min      rendering.py:204-208 (beta_min = 0.1 in the whole-path entries)
+ *   rgb_static    [n,3]  sum a_s T_s c_s                rendering.py:218-227 (static_rgb_map_: the static field rendered alone)
+ *   rgb_transient [n,3]  sum a_t T c_t                  rendering.py:201-203 (transient_rgb_map)
+ * No white background.  Every member is optional (NULL = not wanted); the maps are not differentiated. */
+typedef struct {
+  float *depth, *depth_static, *beta, *rgb_static, *rgb_transient;
+} dfn_render_maps;
+
+/* Scratch needed by dfn_render_rays_maps / dfn_render_image_maps for up to n_rays rays: dfn_render_workspace_bytes with the
+ * 16-float segment records that carry the sums of rendering.py:196-241 out of the fine kernel. */
+size_t dfn_render_maps_workspace_bytes(size_t n_rays, int Nc, int Ni);
+
+/* dfn_render_rays (rendering.py:245-337 at test time) that also writes the requested maps (rendering.py:196-241, table above).
+ * Where the compositing is fused into the fine kernel, the kernel's maps flavour accumulates them in registers: `raw` never
+ * reaches HBM.  maps == NULL or five NULL members: exactly dfn_render_rays (same launches, same bits); rgb / disp / acc are
+ * the same bits either way. */
+int dfn_render_rays_maps(dfn_nerfh_t h, int prec, const float* rays_o, const float* rays_d,
+                         const float* viewdirs, const float* hist, size_t hist_rows, size_t n_rays,
+                         int Nc, int Ni, float near, float far, float* rgb, float* disp, float* acc,
+                         float* raw, void* workspace, size_t workspace_bytes, const dfn_render_maps* maps, void* stream);
+
+/* dfn_render_image (rendering.py:353-400, render(c2w=...)) with the maps of rendering.py:196-241: depth, depth_static, beta
+ * [H,W]; rgb_static, rgb_transient [H,W,3].  maps == NULL or five NULL members: exactly dfn_render_image. */
+int dfn_render_image_maps(dfn_nerfh_t h, int prec, const float* c2w, int H, int W, float focal,
+                          float near, float far, int Nc, int Ni, const float* hist, float* rgb,
+                          float* disp, float* acc, void* workspace, size_t workspace_bytes,
+                          const dfn_render_maps* maps, void* stream);
+
+/* The stage on its own: the maps of rendering.py:196-241 from raw [n_rays, Nf, 9] and z [n_rays, Nf] (1 <= Nf <= 512), what
+ * raw2outputs_NeRFW(typ="fine", output_transient=True) computes before it returns. */
+int dfn_composite_fine_maps(const float* raw, const float* z, size_t n_rays, int Nf, float beta_min,
+                            const dfn_render_maps* maps, void* stream);
+
 /* ------------------------------------------------------------------ gradient of the render
  * What loss.backward() runs through render(c2w = pose) in the DFNet_dm step
  * (feature/direct_feature_matching.py:340-376): test-time render, NeRF weights frozen, no gradient through
@@ -572,6 +611,12 @@ int dfn_nerfh_generic_render_rays(dfn_nerfh_t h, const float* rays_o, const floa
 int dfn_nerfh_generic_render_rays_v(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs, const float* hist,
                                     size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far, float* rgb, float* disp,
                                     float* acc, float* raw, void* workspace, size_t workspace_bytes, void* stream);
+/* dfn_nerfh_generic_render_rays_v that also writes the requested maps (rendering.py:196-241, see dfn_render_maps) from the raw it
+ * leaves in HBM.  maps == NULL or five NULL members: exactly dfn_nerfh_generic_render_rays_v.  Same workspace. */
+int dfn_nerfh_generic_render_rays_maps(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs, const float* hist,
+                                       size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far, float* rgb, float* disp,
+                                       float* acc, float* raw, void* workspace, size_t workspace_bytes, const dfn_render_maps* maps,
+                                       void* stream);
 /* The gradient of that render for ANY even netwidth (what dfn_render_rays_backward is for netwidth 128): d L / d rays_o,
  * d L / d rays_d [n_rays, 3] from grad_rgb [n_rays, 3]; viewdirs == NULL: they are d/|d| and the normalisation is differentiated
  * into grad_rays_d, otherwise grad_viewdirs (optional) receives their gradient.  Exact fp32; recomputes the forward keeping the
