@@ -39,6 +39,12 @@ class RenderMaps(Structure):
                 ("rgb_transient", c_void_p)]
 
 
+class MapGrads(Structure):
+    """dfn_map_grads (include/dfnet_hip.h): upstream gradients of the compositor's outputs, NULL = zero"""
+    _fields_ = [("rgb", c_void_p), ("acc", c_void_p), ("depth", c_void_p), ("depth_static", c_void_p), ("disp", c_void_p),
+                ("beta", c_void_p), ("rgb_static", c_void_p), ("rgb_transient", c_void_p)]
+
+
 MAP_NAMES = tuple(n for n, _ in RenderMaps._fields_)   # trailing shape: () for the first three, (3,) for the rgb_* maps
 
 
@@ -84,6 +90,7 @@ SIGNATURES = {
                                       _P, _P, _P, _P, c_size_t, POINTER(RenderMaps), _P]),
     "dfn_composite_fine_maps": (c_int, [_P, _P, c_size_t, c_int, c_float, POINTER(RenderMaps), _P]),
     "dfn_composite_fine_backward": (c_int, [_P, _P, _P, c_size_t, c_int, _P, _P]),
+    "dfn_composite_fine_backward_maps": (c_int, [_P, _P, c_size_t, c_int, c_float, POINTER(MapGrads), _P, _P, _P]),
     "dfn_mlp_fine_backward": (c_int, [_P, c_int, _P, _P, _P, _P, c_size_t, c_size_t, _P, c_int, _P, _P, _P, _P]),
     "dfn_mlp_fine_mask_bytes": (c_size_t, [c_size_t]),
     "dfn_mlp_fine_saving": (c_int, [_P, c_int, _P, _P, _P, _P, c_size_t, c_size_t, _P, c_int, _P, _P, _P, _P]),
@@ -156,6 +163,8 @@ SIGNATURES = {
                                                c_size_t, _P]),
     "dfn_nerfh_generic_render_rays_backward_raw": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, c_float, c_float, _P, _P, _P, _P,
                                                    _P, _P, c_size_t, _P]),
+    "dfn_nerfh_generic_render_rays_backward_maps": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, c_float, c_float, _P, _P, _P,
+                                                    _P, _P, _P, c_size_t, POINTER(MapGrads), _P]),
     "dfn_pose_orthogonalize": (c_int, [_P, c_int, _P, _P]),
     "dfn_pose_orthogonalize_backward": (c_int, [_P, _P, c_int, _P, _P]),
     "dfn_conv_wgrad_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

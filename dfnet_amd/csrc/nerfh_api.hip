@@ -1074,6 +1074,21 @@ extern "C" int dfn_composite_fine_backward(const float* raw, const float* z, con
   return DFN_OK;
 }
 
+// Every output of the compositor (rgb, acc, depth, depth_static, disp, beta, rgb_static, rgb_transient): nerfh_maps_bwd.hip.
+extern "C" int dfn_composite_fine_backward_maps(const float* raw, const float* z, size_t n_rays, int Nf, float beta_min,
+                                                const dfn_map_grads* grads, const float* grad_raw_ext, float* grad_raw, void* stream) {
+  if (!raw || !z || !grad_raw || Nf < 1 || Nf > 512)
+    return set_error(DFN_ERR_ARG, "dfn_composite_fine_backward_maps: bad argument (1 <= Nf <= 512)");
+  const MapGrads g = grads ? MapGrads{grads->rgb, grads->acc, grads->depth, grads->depth_static, grads->disp, grads->beta,
+                                      grads->rgb_static, grads->rgb_transient}
+                           : MapGrads{};
+  if (!g.any() && !grad_raw_ext)
+    return set_error(DFN_ERR_ARG, "dfn_composite_fine_backward_maps: bad argument (no upstream gradient and no grad_raw_ext)");
+  CHECK_HIP(launch_composite_fine_backward_all(raw, z, n_rays, Nf, beta_min, g, grad_raw, HS(stream), grad_raw_ext),
+            "dfn_composite_fine_backward_maps");
+  return DFN_OK;
+}
+
 extern "C" int dfn_mlp_fine_backward(dfn_nerfh_t h, int prec, const float* rays_o, const float* rays_d, const float* viewdirs,
                                      const float* hist, size_t hist_rows, size_t n_rays, const float* z_fine, int Nf,
                                      const float* grad_raw, float* grad_pts, void* bias_ws, void* stream) {

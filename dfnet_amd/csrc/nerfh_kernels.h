@@ -116,6 +116,16 @@ hipError_t launch_mlp_fine_backward(int prec, const BwdArgs& a, int n_cu, hipStr
 // graw = grad_raw_ext and the scan is skipped.  Without it: the rgb-only kernel, unchanged.
 hipError_t launch_composite_fine_backward(const float* raw, const float* z, const float* grad_rgb, size_t n_rays, int Nf,
                                           float* graw, hipStream_t stream, const float* grad_raw_ext = nullptr);
+// Upstream gradients of every output of the fine compositor (dfn_map_grads), each optional (null = zero): rgb, rgb_static,
+// rgb_transient [n_rays,3]; the others [n_rays].
+struct MapGrads {
+  const float *rgb, *acc, *depth, *depth_static, *disp, *beta, *rgb_static, *rgb_transient;
+  bool any() const { return rgb || acc || depth || depth_static || disp || beta || rgb_static || rgb_transient; }
+};
+// d L / d raw summed over all of them (nerfh_maps_bwd.hip); grad_raw_ext as in launch_composite_fine_backward.  Every pointer of g null:
+// graw = grad_raw_ext (an error without it).  launch_composite_fine_backward and its kernel are not involved.
+hipError_t launch_composite_fine_backward_all(const float* raw, const float* z, size_t n_rays, int Nf, float beta_min, const MapGrads& g,
+                                              float* graw, hipStream_t stream, const float* grad_raw_ext = nullptr);
 // Per-ray reduction of the per-sample gradients: d o = sum g, d d = sum z g (+ viewdir normalisation when
 // `derive_viewdirs`), d viewdirs = sum gv (when grad_viewdirs != nullptr).  accumulate: add to what grad_o / grad_d hold.
 hipError_t launch_ray_grad_reduce(const float* gpts, const float* z, const float* rays_d, size_t n_rays, int Nf,

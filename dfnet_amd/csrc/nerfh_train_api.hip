@@ -600,15 +600,23 @@ extern "C" size_t dfn_nerfh_generic_backward_workspace_bytes(dfn_nerfh_t h, size
 namespace {
 // `entry`: the public name the messages carry.  grad_raw [n_rays, Nc+Ni, 9] (optional): d L / d of the RETURNED raw, added to the
 // compositor's d L / d raw inside the compositing-backward kernel, before the head derivatives.  rgb_required: the entry without
-// grad_raw, where grad_rgb is not optional.
+// grad_raw, where grad_rgb is not optional.  grads (optional, dfn_nerfh_generic_render_rays_backward_maps): upstream gradients of every
+// compositor output; non-NULL, the compositing backward is launch_composite_fine_backward_all with grad_rgb standing for grads->rgb.
 int generic_render_rays_backward_impl(const char* entry, dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
                                       const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
                                       const float* grad_rgb, const float* grad_raw, float* grad_rays_o, float* grad_rays_d,
-                                      float* grad_viewdirs, void* workspace, size_t workspace_bytes, void* stream, bool rgb_required) {
+                                      float* grad_viewdirs, void* workspace, size_t workspace_bytes, void* stream, bool rgb_required,
+                                      const dfn_map_grads* grads = nullptr) {
   if (int rc = check_train_args(h, Nc, Ni, entry)) return rc;
   if (!h->committed) return set_error(DFN_ERR_STATE, "%s: dfn_nerfh_commit() has not been called", entry);
   if (!n_rays) return DFN_OK;
-  if (!grad_rgb && !grad_raw && !rgb_required)
+  MapGrads mg{};
+  if (grads) {
+    if (grad_rgb && grads->rgb) return set_error(DFN_ERR_ARG, "%s: bad argument (grad_rgb and grads->rgb are both given)", entry);
+    mg = MapGrads{grads->rgb ? grads->rgb : grad_rgb, grads->acc, grads->depth, grads->depth_static, grads->disp, grads->beta,
+                  grads->rgb_static, grads->rgb_transient};
+  }
+  if (grads ? !mg.any() && !grad_raw : !grad_rgb && !grad_raw && !rgb_required)
     return set_error(DFN_ERR_ARG, "%s: bad argument (grad_rgb and grad_raw are both NULL: at least one is required)", entry);
   if (!rays_o || !rays_d || !hist || (rgb_required && !grad_rgb) || !grad_rays_o || !grad_rays_d || !workspace || (hist_rows != 1 && hist_rows != n_rays))
     return set_error(DFN_ERR_ARG, "%s: bad argument (hist_rows must be 1 or n_rays)", entry);
@@ -643,7 +651,10 @@ int generic_render_rays_backward_impl(const char* entry, dfn_nerfh_t h, const fl
   if (int rc = net_forward(nf, m, b, true, false, s)) return rc;
   // ---- d rgb -> d raw -> d pre-activation (in place)
   float* gpre = w.gpre_f;
-  CHECK_HIP(launch_composite_fine_backward(g.raw, w.z_f, grad_rgb, R, Nf, gpre, s, grad_raw), "generic render gradient: composite");
+  if (grads)
+    CHECK_HIP(launch_composite_fine_backward_all(g.raw, w.z_f, R, Nf, 0.1f, mg, gpre, s, grad_raw), "generic render gradient: composite (all outputs)");
+  else
+    CHECK_HIP(launch_composite_fine_backward(g.raw, w.z_f, grad_rgb, R, Nf, gpre, s, grad_raw), "generic render gradient: composite");
   CHECK_HIP(head_prime(g.raw, gpre, size_t(P), s), "generic render gradient: head derivatives");
   // ---- data gradients (the calls of net_backward, without the weight gradients)
   const int C = 9, ldw_dir = W + b.kd, ldw_te0 = W + m.nt;
@@ -701,6 +712,16 @@ extern "C" int dfn_nerfh_generic_render_rays_backward_raw(dfn_nerfh_t h, const f
   return generic_render_rays_backward_impl("dfn_nerfh_generic_render_rays_backward_raw", h, rays_o, rays_d, viewdirs, hist, hist_rows,
                                            n_rays, Nc, Ni, near, far, grad_rgb, grad_raw, grad_rays_o, grad_rays_d, grad_viewdirs,
                                            workspace, workspace_bytes, stream, false);
+}
+// From the upstream gradients of every compositor output (models/rendering.py:161-243: disp_map, acc_map and the render maps under autograd).
+extern "C" int dfn_nerfh_generic_render_rays_backward_maps(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                                           const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near,
+                                                           float far, const float* grad_rgb, const float* grad_raw, float* grad_rays_o,
+                                                           float* grad_rays_d, float* grad_viewdirs, void* workspace,
+                                                           size_t workspace_bytes, const dfn_map_grads* grads, void* stream) {
+  return generic_render_rays_backward_impl("dfn_nerfh_generic_render_rays_backward_maps", h, rays_o, rays_d, viewdirs, hist, hist_rows,
+                                           n_rays, Nc, Ni, near, far, grad_rgb, grad_raw, grad_rays_o, grad_rays_d, grad_viewdirs,
+                                           workspace, workspace_bytes, stream, false, grads);
 }
 
 // ------------------------------------------------------------------------------------------ the three products, for parity tests

@@ -73,6 +73,22 @@ def _maps_at(out, r0, m):
     return _lib.RenderMaps(**{k: t[r0:r0 + m].data_ptr() for k, t in out.items()})
 
 
+GRAD_NAMES = tuple(n for n, _ in _lib.MapGrads._fields_)   # rgb, acc, depth, depth_static, disp, beta, rgb_static, rgb_transient
+
+
+def _map_grads(grads, n):
+    """({name: contiguous fp32 tensor [n] / [n,3]} of the non-None entries of `grads`, kept alive by the caller) for dfn_map_grads."""
+    unknown = [k for k in grads if k not in GRAD_NAMES]
+    if unknown:
+        raise ValueError(f"unknown upstream gradient(s) {unknown}: the compositor's outputs are {list(GRAD_NAMES)}")
+    return {k: _f32c(t).reshape((n, 3) if k.startswith("rgb") else (n,)) for k, t in grads.items() if t is not None}
+
+
+def _map_grads_at(held, r0=0, m=None):
+    """The dfn_map_grads struct for rows [r0, r0 + m) of the tensors of _map_grads."""
+    return _lib.MapGrads(**{k: (t if m is None else t[r0:r0 + m]).data_ptr() for k, t in held.items()})
+
+
 class NerfHEngine:
     """NeRF-H coarse+fine networks resident on one GPU in MFMA-fragment layout."""
 
@@ -382,6 +398,10 @@ class NerfHEngine:
         """The maps from raw [n,Nf,9] and z [n,Nf] (the module-level composite_fine_maps)."""
         return composite_fine_maps(raw, z, beta_min, maps)
 
+    def composite_fine_backward_maps(self, raw, z, grads, beta_min=0.1, grad_raw=None):
+        """d L/d raw from the upstream gradients of every compositor output (the module-level composite_fine_backward_maps)."""
+        return composite_fine_backward_maps(raw, z, grads, beta_min, grad_raw)
+
     # ------------------------------------------------------------------ staged render that keeps what backward needs
     def render_rays_saving(self, rays_o, rays_d, viewdirs, hist, Nc, Ni, near, far, precision=None, with_masks=False):
         """render_rays composed from the stage entry points, returning (rgb, disp, acc, z_fine, raw[, masks]): the state
@@ -399,13 +419,20 @@ class NerfHEngine:
         return out["rgb"], out["disp"], out["acc"], z, raw
 
     def backward_from_saved(self, rays_o, rays_d, viewdirs, hist, z, raw, grad_rgb, derive_viewdirs=True, precision=None, masks=None,
-                            grad_raw=None):
+                            grad_raw=None, graw=None):
         """d L/d (rays_o, rays_d[, viewdirs]) from the saved (z_fine, raw[, masks]) of render_rays_saving().  grad_raw [n,Nf,9]: a
-        gradient that reaches `raw` directly (render(retraw=True) under autograd), added to the compositor's."""
+        gradient that reaches `raw` directly (render(retraw=True) under autograd), added to the compositor's.  graw [n,Nf,9]: the
+        FINISHED d L/d raw (composite_fine_backward_maps: every compositor output, grad_raw already inside) — the compositing backward
+        is skipped and grad_rgb / grad_raw are not read."""
         rays_o, rays_d, viewdirs = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3), _f32c(viewdirs).reshape(-1, 3)
-        graw = composite_fine_backward(raw, z, _f32c(grad_rgb).reshape(-1, 3))
-        if grad_raw is not None:
-            graw += _f32c(grad_raw).reshape(graw.shape)
+        if graw is not None:
+            if grad_raw is not None:
+                raise ValueError("backward_from_saved: graw is the finished d L/d raw, grad_raw belongs inside it")
+            graw = _f32c(graw).reshape(z.shape[0], z.shape[1], 9)
+        else:
+            graw = composite_fine_backward(raw, z, _f32c(grad_rgb).reshape(-1, 3))
+            if grad_raw is not None:
+                graw += _f32c(grad_raw).reshape(graw.shape)
         if masks is not None:
             gpts = self.mlp_fine_backward_saved(rays_o, rays_d, viewdirs, z, raw, masks, graw)
         else:
@@ -418,19 +445,30 @@ class NerfHEngine:
         return go, gd, gv
 
     # ------------------------------------------------------------------ gradient of the whole path
-    def render_rays_backward(self, rays_o, rays_d, hist, Nc, Ni, near, far, grad_rgb, viewdirs=None, precision=None, grad_raw=None):
+    def render_rays_backward(self, rays_o, rays_d, hist, Nc, Ni, near, far, grad_rgb, viewdirs=None, precision=None, grad_raw=None,
+                             grad_maps=None):
         """d L/d (rays_o, rays_d[, viewdirs]) of render_rays from d L/d rgb [n,3].  With viewdirs=None they are
         d/|d| and their gradient is folded into grad_rays_d (what autograd does for render(rays=...)).  grad_raw [n,Nc+Ni,9]
-        (generic-width path): d L/d of the returned raw, added to the compositor's; grad_rgb may then be None."""
+        (generic-width path): d L/d of the returned raw, added to the compositor's; grad_rgb may then be None.  grad_maps
+        (generic-width path): {name: d L/d output} over acc, depth, depth_static, disp, beta, rgb_static, rgb_transient (and rgb, when
+        grad_rgb is None) — the compositing backward for every output (dfn_nerfh_generic_render_rays_backward_maps)."""
         rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
         n, dev = rays_o.shape[0], rays_o.device
         generic = self.width != 128 or precision == "generic"
+        held = None
+        if grad_maps is not None:
+            if not generic:
+                raise NotImplementedError("render_rays_backward(grad_maps=...) on the register-resident netwidth-128 kernels: use "
+                                          "precision='generic' or composite_fine_backward_maps() + backward_from_saved(graw=...)")
+            held = _map_grads(grad_maps, n)
+            if grad_rgb is not None and "rgb" in held:
+                raise ValueError("render_rays_backward: d L/d rgb given twice (grad_rgb and grad_maps['rgb'])")
         if grad_raw is not None:
             if not generic:
                 raise NotImplementedError("render_rays_backward(grad_raw=...) on the register-resident netwidth-128 kernels: use "
                                           "precision='generic' or backward_from_saved(grad_raw=...)")
             grad_raw = _f32c(grad_raw).reshape(n, Nc + Ni, 9)
-        elif grad_rgb is None:
+        elif grad_rgb is None and not held:
             raise ValueError("render_rays_backward: grad_rgb and grad_raw are both None")
         if grad_rgb is not None:
             grad_rgb = _f32c(grad_rgb).reshape(n, 3)
@@ -448,6 +486,13 @@ class NerfHEngine:
             for r0 in range(0, n, C):
                 m = min(C, n - r0)
                 hh = hist if hist.shape[0] == 1 else hist[r0:r0 + m]
+                if held is not None:
+                    check(self.lib.dfn_nerfh_generic_render_rays_backward_maps(
+                        self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(cut(viewdirs, r0, m)), ptr(hh), hh.shape[0], m, Nc, Ni,
+                        float(near), float(far), ptr(cut(grad_rgb, r0, m)), ptr(cut(grad_raw, r0, m)), ptr(go[r0:r0 + m]), ptr(gd[r0:r0 + m]),
+                        ptr(cut(gv, r0, m)), ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.byref(_map_grads_at(held, r0, m)),
+                        current_stream()), "dfn_nerfh_generic_render_rays_backward_maps")
+                    continue
                 check(self.lib.dfn_nerfh_generic_render_rays_backward_raw(
                     self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(cut(viewdirs, r0, m)), ptr(hh), hh.shape[0], m, Nc, Ni,
                     float(near), float(far), ptr(cut(grad_rgb, r0, m)), ptr(cut(grad_raw, r0, m)), ptr(go[r0:r0 + m]), ptr(gd[r0:r0 + m]),
@@ -958,6 +1003,23 @@ def composite_fine_backward(raw, z, grad_rgb):
     graw = torch.empty(n, Nf, 9, device=raw.device)
     check(_lib.load().dfn_composite_fine_backward(ptr(raw), ptr(z), ptr(grad_rgb), n, Nf, ptr(graw), current_stream()),
           "dfn_composite_fine_backward")
+    return graw
+
+
+def composite_fine_backward_maps(raw, z, grads, beta_min=0.1, grad_raw=None):
+    """d L/d raw [n,Nf,9] through the fine compositing (models/rendering.py:161-243) from the upstream gradients of ALL its outputs:
+    grads = {name: tensor} over rgb, rgb_static, rgb_transient [n,3] and acc, depth, depth_static, disp, beta [n]; a missing name or
+    None is a zero gradient.  grad_raw [n,Nf,9]: a gradient that reaches raw directly, added in the same kernel
+    (dfn_composite_fine_backward_maps)."""
+    raw, z = _f32c(raw), _f32c(z)
+    n, Nf = z.shape
+    held = _map_grads(grads, n)
+    if grad_raw is not None:
+        grad_raw = _f32c(grad_raw).reshape(n, Nf, 9)
+    graw = torch.empty(n, Nf, 9, device=raw.device)
+    st = _map_grads_at(held)
+    check(_lib.load().dfn_composite_fine_backward_maps(ptr(raw), ptr(z), n, Nf, float(beta_min), ctypes.byref(st), ptr(grad_raw), ptr(graw),
+                                                       current_stream()), "dfn_composite_fine_backward_maps")
     return graw
 
 

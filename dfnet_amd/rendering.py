@@ -19,7 +19,9 @@ torch.autograd.Function wrappers: the forward is composed from the stage entry p
 the backward runs the HIP gradient kernels on that saved state (compositing backward, fused fine-MLP input
 gradient, ray / pose reductions) — the stateless dfn_render_image_backward / dfn_render_rays_backward compute
 the same thing with an internal re-render.  disp_map / acc_map are returned detached (the reference's losses use
-rgb only).  The MLP gradient kernel defaults to the exact-fp32 MFMA path (`GRAD_PRECISION`), see
+rgb only) unless render(..., diff_maps=True) is asked for: then disp_map, acc_map and the maps named by ret_maps come back attached
+too (as in the reference, where they are torch expressions of raw, rendering.py:161-243), through the compositing backward for every
+output (dfn_composite_fine_backward_maps) and the same network gradient.  The MLP gradient kernel defaults to the exact-fp32 MFMA path (`GRAD_PRECISION`), see
 tests/test_gpu_grad.py.
 """
 import os
@@ -170,6 +172,9 @@ def render_frames(H, W, focal, c2ws, img_idx, **kwargs):
     """rgb [B,H,W,3] of B frames at poses c2ws [B,3,4] with histogram vectors img_idx [B,bins] — render(c2w=...) per frame,
     batched into one launch per stage, differentiable w.r.t. c2ws.  Same option checks as render()."""
     near, far = kwargs.pop('near', 0.), kwargs.pop('far', 1.)
+    if kwargs.get('diff_maps', False):
+        raise NotImplementedError("dfnet_amd render_frames(): not implemented natively yet: diff_maps (render_frames returns rgb alone; use "
+                                  "render(c2w=..., diff_maps=True) per frame) — there is deliberately no CPU fallback")
     _check_test_time(kwargs, kwargs.get('ndc', False), None, kwargs.get('use_viewdirs', True), tracked=True)
     eng = _engine_of(kwargs)
     _set_options(eng, kwargs, near)
@@ -207,6 +212,55 @@ class _RenderRaysFn(torch.autograd.Function):
         return (go, gd) + (None,) * 7
 
 
+class _RenderRaysMapsFn(torch.autograd.Function):
+    """render(rays, diff_maps=True): (rgb, disp, acc, *maps[, raw]) with EVERY output attached — disp_map, acc_map and the maps named by
+    ret_maps are differentiable functions of raw in the reference (raw2outputs_NeRFW, rendering.py:161-243).  backward: the upstream
+    gradients of all of them go through the compositing backward for every output (composite_fine_backward_maps; d L/d raw of retraw is
+    added in the same kernel), then through the fine network's gradient exactly as _RenderRaysFn does.  Netwidth 128: the saved-state
+    route (two-pass or one-pass); other widths: the stateless generic-width gradient (dfn_nerfh_generic_render_rays_backward_maps)."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, eng, hist, Nc, Ni, near, far, retraw, names):
+        o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
+        v = d / torch.norm(d, dim=-1, keepdim=True)
+        if eng.width != 128:
+            prec = GRAD_FORWARD_PRECISION if eng.fast else None   # as _saving_forward
+            if names:
+                rgb, disp, acc, raw, mp = eng.render_rays_maps(o, d, hist, Nc, Ni, near, far, retraw=retraw, precision=prec, maps=names)
+            else:
+                (rgb, disp, acc, raw), mp = eng.render_rays(o, d, hist, Nc, Ni, near, far, retraw=retraw, precision=prec), {}
+            saved = (o, d, v, hist, torch.tensor([Nc, Ni, near, far, float(eng.lindisp)], dtype=torch.float64))
+        else:
+            rgb, disp, acc, saved = _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far)
+            mp = eng.composite_fine_maps(saved[5], saved[4], maps=names) if names else {}
+            raw = saved[5].clone() if retraw else None   # the caller's tensor: an in-place edit must not reach the saved state
+        ctx.eng, ctx.names, ctx.retraw = eng, names, retraw
+        ctx.save_for_backward(*saved)
+        ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None = a NULL upstream pointer
+        return (rgb, disp, acc) + tuple(mp[k] for k in names) + ((raw,) if retraw else ())
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_disp, g_acc, *rest):
+        eng, names, saved = ctx.eng, ctx.names, ctx.saved_tensors
+        grads = dict(zip(("rgb", "disp", "acc") + tuple(names), (g_rgb, g_disp, g_acc) + tuple(rest[:len(names)])))
+        grads = {k: g for k, g in grads.items() if g is not None}
+        g_raw = rest[len(names)] if ctx.retraw else None
+        if not grads and g_raw is None:
+            grads = dict(rgb=torch.zeros(saved[0].shape[0], 3, device=saved[0].device))
+        if len(saved) == 5:   # generic width (see _saved_backward)
+            o, d, _, hist, cfg = saved
+            Nc, Ni, near, far, lindisp = cfg.tolist()
+            eng.set_render_options(lindisp=bool(lindisp))
+            go, gd, _ = eng.render_rays_backward(o, d, hist, int(Nc), int(Ni), near, far, None, precision="generic",
+                                                 grad_raw=None if g_raw is None else g_raw.contiguous(), grad_maps=grads)
+        else:
+            o, d, v, hist, z, raw = saved[:6]
+            masks = saved[6] if len(saved) > 6 else None
+            graw = eng.composite_fine_backward_maps(raw, z, grads, grad_raw=g_raw)
+            go, gd, _ = eng.backward_from_saved(o, d, v, hist, z, raw, None, True, precision=GRAD_PRECISION, masks=masks, graw=graw)
+        return (go, gd) + (None,) * 8
+
+
 def _set_options(eng, kw, near):
     """The render_rays keyword options the handle carries (lindisp, rendering.py:272-273)."""
     lindisp = bool(kw.get('lindisp', False))
@@ -215,14 +269,16 @@ def _set_options(eng, kw, near):
     eng.set_render_options(lindisp=lindisp)
 
 
-def _check_test_time(kw, ndc, c2w_staticcam, use_viewdirs, training=False, tracked=False, ret_maps=False):
+def _check_test_time(kw, ndc, c2w_staticcam, use_viewdirs, training=False, tracked=False, ret_maps=False, diff_maps=False):
     bad = []
     if kw.get('white_bkgd', False):
         raise TypeError("render(): white_bkgd=True is not a working option of the NeRF-H path: the reference hands it to the coarse "
                         "compositor as output_transient (models/rendering.py:295) and fails the same way")
     if (ndc or c2w_staticcam is not None) and (training or tracked):
         bad.append("ndc / c2w_staticcam together with " + ("training-mode rendering" if training else "autograd"))
-    if ret_maps and (training or tracked):
+    if diff_maps and training:
+        bad.append("diff_maps together with training-mode rendering")
+    if ret_maps and (training or tracked) and not (diff_maps and not training):
         bad.append("ret_maps together with " + ("training-mode rendering" if training else "autograd (the maps are not differentiable)"))
     if not training:
         if not kw.get('test_time', False):
@@ -241,12 +297,16 @@ def _check_test_time(kw, ndc, c2w_staticcam, use_viewdirs, training=False, track
 
 
 def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
-           c2w_staticcam=None, img_idx=torch.Tensor(0), ret_maps=False, **kwargs):
+           c2w_staticcam=None, img_idx=torch.Tensor(0), ret_maps=False, diff_maps=False, **kwargs):
     """Drop-in for rendering.py:353-400.  Returns [rgb_map, disp_map, acc_map, extras].
 
-    ret_maps (beyond the reference, test time without autograd only): True, or an iterable of names out of depth, depth_static, beta,
+    ret_maps (beyond the reference, test time; under autograd only together with diff_maps): True, or an iterable of names out of depth, depth_static, beta,
     rgb_static, rgb_transient — the maps raw2outputs_NeRFW forms and the reference drops (rendering.py:196-241) are added to
     `extras` under those names, shaped like the rays ([H,W] / [H,W,3] for c2w).
+
+    diff_maps (opt-in, test time): under autograd (rays or c2w requiring grad) disp_map, acc_map and the maps of ret_maps come back attached
+    to the graph as well, as the reference's are (they are torch expressions of raw, rendering.py:161-243).  False: as ever, disp_map and
+    acc_map detached and ret_maps refused under autograd.  Without autograd it changes nothing.
 
     c2w given: full image, outputs [H,W,3], [H,W], [H,W].  Otherwise `rays` = (rays_o, rays_d) (a tuple
     or a stacked [2,N,3] tensor), outputs shaped like rays_d[..., :1].  `img_idx`: the 10-bin histogram
@@ -259,7 +319,7 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     if not kwargs.get('test_time', False) and trainer is not None:
         # training mode (rendering.py:245-337 with test_time=False): stratified depths, coarse rgb + noise, importance sampling
         # with random u, the training extras — on the exact-fp32 training kernels, attached to autograd (nerf_train.py)
-        _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, training=True, ret_maps=bool(map_list))
+        _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, training=True, ret_maps=bool(map_list), diff_maps=bool(diff_maps))
         # The reference's training render is differentiable w.r.t. its rays / pose too: rays that require grad make the autograd node
         # run the exact-fp32 step and return d L / d rays (nerf_train._RenderTrainFn); c2w reaches them through get_rays' own node.
         from . import nerf_train
@@ -291,7 +351,8 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
             return t.requires_grad
         return isinstance(t, (tuple, list)) and any(_needs_grad(u) for u in t)
     track = torch.is_grad_enabled() and (_needs_grad(c2w) or _needs_grad(rays))
-    _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, tracked=track, ret_maps=bool(map_list))
+    diff_maps = bool(diff_maps) and track   # nothing to attach to without autograd
+    _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, tracked=track, ret_maps=bool(map_list), diff_maps=diff_maps)
     Nc, Ni = int(kwargs['N_samples']), int(kwargs['N_importance'])
     retraw = bool(kwargs.get('retraw', False))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -326,17 +387,17 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         return _rays(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), hist, list(rays_d.shape[:-1]), view)
     if c2w is not None:
         c2w = torch.as_tensor(c2w, dtype=torch.float32, device=dev)
-        if track and not retraw and hist.numel() == eng.hist_bin:
+        if track and not retraw and not diff_maps and hist.numel() == eng.hist_bin:
             rgb, disp, acc = _RenderImageFn.apply(c2w[:3, :4], eng, int(H), int(W), float(focal), hist.reshape(-1), Nc, Ni,
                                                   float(near), float(far))
             return [rgb, disp, acc, {}]
-        if retraw or hist.numel() != eng.hist_bin:
+        if retraw or diff_maps or hist.numel() != eng.hist_bin:
             if track and c2w.requires_grad:    # the pose reaches the ray gradients through get_rays' own node
                 o, d = (t.reshape(int(H), int(W), 3) for t in _RaygenFn.apply(c2w[:3, :4].contiguous(), int(H), int(W), float(focal)))
             else:
                 o, d = get_rays(H, W, focal, c2w)
             return render(H, W, focal, chunk, rays=(o, d), ndc=ndc, near=near, far=far, use_viewdirs=use_viewdirs,
-                          img_idx=img_idx, ret_maps=map_list, **kwargs)
+                          img_idx=img_idx, ret_maps=map_list, diff_maps=diff_maps, **kwargs)
         if map_list:
             rgb, disp, acc, _, mp = eng.render_image_maps(c2w, int(H), int(W), float(focal), hist, Nc, Ni, near, far, maps=map_list)
             return [rgb, disp, acc, mp]
@@ -351,6 +412,13 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     if hist.shape[0] not in (1, n):
         raise ValueError(f"img_idx must have 1 or {n} rows of {eng.hist_bin} bins, got {tuple(hist.shape)}")
     lead = list(sh[:-1])
+    if diff_maps:
+        out = _RenderRaysMapsFn.apply(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), eng, hist, Nc, Ni, float(near), float(far), retraw,
+                                      tuple(map_list))
+        extras = {k: t.reshape(lead + list(t.shape[1:])) for k, t in zip(map_list, out[3:])}
+        if retraw:
+            extras['raw'] = out[-1].reshape(lead + list(out[-1].shape[1:]))
+        return [out[0].reshape(lead + [3]), out[1].reshape(lead), out[2].reshape(lead), extras]
     if track:
         out = _RenderRaysFn.apply(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), eng, hist, Nc, Ni, float(near), float(far), retraw)
         rgb, disp, acc = out[:3]

@@ -188,7 +188,7 @@ int dfn_render_image(dfn_nerfh_t h, int prec, const float* c2w, int H, int W, fl
  *   beta          [n]    sum a_t T beta + beta_min      rendering.py:204-208 (beta_min = 0.1 in the whole-path entries)
  *   rgb_static    [n,3]  sum a_s T_s c_s                rendering.py:218-227 (static_rgb_map_: the static field rendered alone)
  *   rgb_transient [n,3]  sum a_t T c_t                  rendering.py:201-203 (transient_rgb_map)
- * No white background.  Every member is optional (NULL = not wanted); the maps are not differentiated. */
+ * No white background.  Every member is optional (NULL = not wanted).  Their gradients: dfn_map_grads, dfn_composite_fine_backward_maps. */
 typedef struct {
   float *depth, *depth_static, *beta, *rgb_static, *rgb_transient;
 } dfn_render_maps;
@@ -222,11 +222,35 @@ int dfn_composite_fine_maps(const float* raw, const float* z, size_t n_rays, int
  * What loss.backward() runs through render(c2w = pose) in the DFNet_dm step
  * (feature/direct_feature_matching.py:340-376): test-time render, NeRF weights frozen, no gradient through
  * the importance sampler (z_samples.detach(), rendering.py:302) and hence none into the coarse net.
- * Only d L / d rgb is propagated (disp / acc are not differentiated); white_bkgd = False. */
+ * The whole-path entries propagate d L / d rgb only; d L / d of disp, acc and the render maps enter through
+ * dfn_composite_fine_backward_maps / dfn_nerfh_generic_render_rays_backward_maps (render(diff_maps=True)).  white_bkgd = False. */
 
 /* raw2outputs_NeRFW backward, rgb only: grad_raw [n_rays, Nf, 9] = d L / d raw from grad_rgb [n_rays, 3]. */
 int dfn_composite_fine_backward(const float* raw, const float* z, const float* grad_rgb, size_t n_rays,
                                 int Nf, float* grad_raw, void* stream);
+
+/* Upstream gradients of every output of the fine compositor (raw2outputs_NeRFW, rendering.py:161-243; under autograd the
+ * reference's disp_map / acc_map and the maps of dfn_render_maps are plain torch expressions of raw).  Per ray:
+ *   rgb           [n,3]  sum T (a_s c_s + a_t c_t)                 (joint transmittance T)
+ *   acc           [n]    sum a T
+ *   depth         [n]    sum a T z
+ *   depth_static  [n]    sum a_s T_s z                             (T_s: the static field's own transmittance)
+ *   disp          [n]    1 / max(1e-10, depth_static / acc)        (folded into depth_static and acc; zero where the clamp is active)
+ *   beta          [n]    sum a_t T beta + beta_min
+ *   rgb_static    [n,3]  sum a_s T_s c_s
+ *   rgb_transient [n,3]  sum a_t T c_t
+ * Every member is optional: NULL = a zero gradient (bit for bit what a tensor of zeros gives). */
+typedef struct {
+  const float *rgb, *acc, *depth, *depth_static, *disp, *beta, *rgb_static, *rgb_transient;
+} dfn_map_grads;
+
+/* raw2outputs_NeRFW backward for all of those outputs (rendering.py:161-243): grad_raw [n_rays, Nf, 9] = d L / d raw summed over
+ * the given upstream gradients, plus grad_raw_ext [n_rays, Nf, 9] (optional: a gradient that reaches raw directly).  z carries no
+ * gradient (rendering.py:302 detaches the fine depths).  beta (channel 8) receives g_beta a_t T.  No division by 1 - alpha: opaque
+ * samples give finite gradients.  1 <= Nf <= 512.  DFN_ERR_ARG when grads is NULL or holds eight NULLs and grad_raw_ext is NULL
+ * too; n_rays == 0 is DFN_OK.  dfn_composite_fine_backward and its kernel are not involved. */
+int dfn_composite_fine_backward_maps(const float* raw, const float* z, size_t n_rays, int Nf, float beta_min,
+                                     const dfn_map_grads* grads, const float* grad_raw_ext, float* grad_raw, void* stream);
 /* Fine-network input gradient: from grad_raw [n_rays, Nf, 9] to grad_pts [n_rays, Nf, 6] =
  * [d L / d sample point (3), d L / d viewdir through this sample (3)].  Other arguments as dfn_mlp_fine. */
 int dfn_mlp_fine_backward(dfn_nerfh_t h, int prec, const float* rays_o, const float* rays_d,
@@ -638,6 +662,17 @@ int dfn_nerfh_generic_render_rays_backward_raw(dfn_nerfh_t h, const float* rays_
                                                float far, const float* grad_rgb, const float* grad_raw, float* grad_rays_o,
                                                float* grad_rays_d, float* grad_viewdirs, void* workspace, size_t workspace_bytes,
                                                void* stream);
+/* That gradient from the upstream gradients of EVERY compositor output (dfn_map_grads; rendering.py:161-243: disp_map, acc_map and
+ * the maps are differentiable functions of raw): the arguments of dfn_nerfh_generic_render_rays_backward_raw plus `grads`.
+ * grad_rgb is d L / d rgb as before and stands for grads->rgb (giving both is DFN_ERR_ARG).  With grads != NULL the compositing
+ * backward is dfn_composite_fine_backward_maps's kernel; everything after it is the same.  grads == NULL: exactly
+ * dfn_nerfh_generic_render_rays_backward_raw (same launches).  No upstream gradient at all and no grad_raw is DFN_ERR_ARG.  Same
+ * workspace (dfn_nerfh_generic_backward_workspace_bytes). */
+int dfn_nerfh_generic_render_rays_backward_maps(dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                                const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near,
+                                                float far, const float* grad_rgb, const float* grad_raw, float* grad_rays_o,
+                                                float* grad_rays_d, float* grad_viewdirs, void* workspace, size_t workspace_bytes,
+                                                const dfn_map_grads* grads, void* stream);
 
 /* The three fp32-MFMA products of the training path, for parity tests (torch.nn.functional.linear and its autograd):
  *   y[p, n]  = act(sum_k x[p / x_row_div, k] w[n, wcol + k] + b[n])   act: 0 none, 1 ReLU, 2 Sigmoid, 3 Softplus
