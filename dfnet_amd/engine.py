@@ -3,6 +3,10 @@ stage and whole-path entry points of libdfnet_hip.so.
 
 All tensors are fp32 CUDA tensors owned by torch (device memory + streams are torch's job; the
 arithmetic is the HIP library's).  Work is enqueued on torch's current stream.
+
+The test-time render has one implementation per shape of call, `_render_rays` (a ray batch, generic-width chunk loop included) and
+`_render_image` (a pose), with the render maps as an option; `render_rays`, `generic_render_rays`, `render_image` and their `_maps`
+forms are front ends of the two.  Without maps a call goes to the plain library entry with the plain entry's workspace.
 """
 import ctypes
 import os
@@ -232,167 +236,111 @@ class NerfHEngine:
     GENERIC_GRAD_CHUNK = 8192   # rays per pass of the generic-width gradient (every fine activation is kept: ~1.3 MB per ray at 64+128, netwidth 256)
     GENERIC_CHUNK = 4096   # rays per pass of the generic path (its activations live in HBM: ~1.2 MB per ray at 64+128, W=128)
 
-    def generic_render_rays(self, rays_o, rays_d, hist, Nc, Ni, near, far, retraw=False, viewdirs=None):
-        """Test-time render on the generic-width path (dfn_nerfh_generic_render_rays_v): exact fp32, any netwidth.  viewdirs [n,3]:
-        the fine network's view directions, used as given (None: d/|d|)."""
+    def _ray_batch(self, rays_o, rays_d, hist, viewdirs):
+        """What every ray-batch render starts from: contiguous fp32 rays [n,3], view directions [n,3] (None: d/|d|, formed by the
+        library), histograms [rows, hist_bin] and the (rgb [n,3], disp [n], acc [n]) to render into."""
         rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
         n, dev = rays_o.shape[0], rays_o.device
         if viewdirs is not None:
             viewdirs = _f32c(viewdirs).reshape(-1, 3)
-            if viewdirs.shape[0] != n:
+            if viewdirs.shape[0] != n:   # the kernels read one row per ray
                 raise ValueError(f"viewdirs must have {n} rows, got {tuple(viewdirs.shape)}")
         hist = _f32c(hist).reshape(-1, self.hist_bin)
-        rgb, disp, acc = torch.empty(n, 3, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev)
-        Nf = Nc + Ni
-        raw_all = torch.empty(n, Nf, 9, device=dev) if retraw else None
-        C = self.GENERIC_CHUNK
-        ws = self._workspace(self.lib.dfn_nerfh_generic_workspace_bytes(self.handle, min(n, C), Nc, Ni), dev)
-        raw_tmp = None if retraw else torch.empty(min(n, C), Nf, 9, device=dev)
-        for r0 in range(0, n, C):
-            m = min(C, n - r0)
-            h = hist if hist.shape[0] == 1 else hist[r0:r0 + m]
-            raw = raw_all[r0:r0 + m] if retraw else raw_tmp[:m]
-            v = None if viewdirs is None else viewdirs[r0:r0 + m]
-            check(self.lib.dfn_nerfh_generic_render_rays_v(self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(v), ptr(h),
-                                                           h.shape[0], m, Nc, Ni, float(near), float(far), ptr(rgb[r0:r0 + m]),
-                                                           ptr(disp[r0:r0 + m]), ptr(acc[r0:r0 + m]), ptr(raw),
-                                                           ctypes.c_void_p(ws.data_ptr()), ws.numel(), current_stream()),
-                  "dfn_nerfh_generic_render_rays_v")
-        return rgb, disp, acc, raw_all
+        return rays_o, rays_d, viewdirs, hist, (torch.empty(n, 3, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev))
 
-    def render_rays(self, rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs=None, retraw=False, precision=None):
-        """Test-time render of a ray batch -> (rgb [n,3], disp [n], acc [n], raw|None)."""
-        if not self.fast or precision == "generic":
-            return self.generic_render_rays(rays_o, rays_d, hist, Nc, Ni, near, far, retraw, viewdirs=viewdirs)
-        rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
-        n = rays_o.shape[0]
-        dev = rays_o.device
-        hist = _f32c(hist).reshape(-1, self.hist_bin)
-        if viewdirs is not None:
-            viewdirs = _f32c(viewdirs).reshape(-1, 3)
-        rgb = torch.empty(n, 3, device=dev)
-        disp = torch.empty(n, device=dev)
-        acc = torch.empty(n, device=dev)
-        raw = torch.empty(n, Nc + Ni, 9, device=dev) if retraw else None
-        nbytes = self.lib.dfn_render_workspace_bytes(n, Nc, Ni)
-        ws = self._workspace(nbytes, dev)
-        check(self.lib.dfn_render_rays(self.handle, self._prec(precision), ptr(rays_o), ptr(rays_d), ptr(viewdirs),
-                                       ptr(hist), hist.shape[0], n, Nc, Ni, float(near), float(far), ptr(rgb),
-                                       ptr(disp), ptr(acc), ptr(raw), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                       current_stream()), "dfn_render_rays")
-        return rgb, disp, acc, raw
-
-    def render_image(self, c2w, H, W, focal, hist, Nc, Ni, near, far, precision=None, out=None):
-        """Test-time render of a full image from a [3,4] (or [4,4]) c2w -> (rgb [H,W,3], disp, acc [H,W])."""
-        c2w = _f32c(c2w)[:3, :4].contiguous()
-        dev = c2w.device
-        hist = _f32c(hist).reshape(-1)[: self.hist_bin].contiguous()
-        if not self.fast or precision == "generic":
-            o, d, _ = raygen(H, W, focal, c2w, want_viewdirs=False)
-            rgb, disp, acc, _ = self.generic_render_rays(o.reshape(-1, 3), d.reshape(-1, 3), hist, Nc, Ni, near, far)
-            res = (rgb.reshape(H, W, 3), disp.reshape(H, W), acc.reshape(H, W))
-            if out is not None:
-                for dst, src in zip(out, res):
-                    dst.copy_(src)
-                return out
-            return res
-        if out is None:
-            out = (torch.empty(H, W, 3, device=dev), torch.empty(H, W, device=dev), torch.empty(H, W, device=dev))
-        rgb, disp, acc = out
-        nbytes = self.lib.dfn_render_workspace_bytes(H * W, Nc, Ni)
-        ws = self._workspace(nbytes, dev)
-        check(self.lib.dfn_render_image(self.handle, self._prec(precision), ptr(c2w), H, W, float(focal), float(near),
-                                        float(far), Nc, Ni, ptr(hist), ptr(rgb), ptr(disp), ptr(acc),
-                                        ctypes.c_void_p(ws.data_ptr()), ws.numel(), current_stream()),
-              "dfn_render_image")
-        return rgb, disp, acc
-
-
-    # ------------------------------------------------------------------ render maps
-    def generic_render_rays_maps(self, rays_o, rays_d, hist, Nc, Ni, near, far, retraw=False, viewdirs=None, maps=MAP_NAMES):
-        """generic_render_rays with the requested maps (dfn_nerfh_generic_render_rays_maps), chunked the same way:
-        (rgb, disp, acc, raw|None, {name: map})."""
-        names = map_names(maps)
-        rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
+    def _render_rays(self, rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs=None, retraw=False, precision=None, names=()):
+        """The test-time render of a ray batch behind render_rays, generic_render_rays and their _maps forms ->
+        (rgb [n,3], disp [n], acc [n], raw|None, {name: map}).  names: the maps wanted, in the library's order (map_names()); with none
+        of them the call is the plain entry's, with the plain entry's workspace.  precision "generic" (and every netwidth without
+        register-resident kernels): exact fp32 layer by layer, GENERIC_CHUNK rays per pass."""
+        rays_o, rays_d, viewdirs, hist, (rgb, disp, acc) = self._ray_batch(rays_o, rays_d, hist, viewdirs)
         n, dev = rays_o.shape[0], rays_o.device
-        if viewdirs is not None:
-            viewdirs = _f32c(viewdirs).reshape(-1, 3)
-            if viewdirs.shape[0] != n:
-                raise ValueError(f"viewdirs must have {n} rows, got {tuple(viewdirs.shape)}")
-        hist = _f32c(hist).reshape(-1, self.hist_bin)
-        rgb, disp, acc = torch.empty(n, 3, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev)
-        out, _ = _alloc_maps(names, n, dev)
-        Nf = Nc + Ni
-        raw_all = torch.empty(n, Nf, 9, device=dev) if retraw else None
+        raw = torch.empty(n, Nc + Ni, 9, device=dev) if retraw else None
+        mp, st = _alloc_maps(names, n, dev)
+        if self.fast and precision != "generic":
+            entry = "dfn_render_rays_maps" if names else "dfn_render_rays"
+            size = self.lib.dfn_render_maps_workspace_bytes if names else self.lib.dfn_render_workspace_bytes
+            ws = self._workspace(size(n, Nc, Ni), dev)
+            args = [self.handle, self._prec(precision), ptr(rays_o), ptr(rays_d), ptr(viewdirs), ptr(hist), hist.shape[0], n, Nc, Ni,
+                    float(near), float(far), ptr(rgb), ptr(disp), ptr(acc), ptr(raw), ctypes.c_void_p(ws.data_ptr()), ws.numel()]
+            if names:
+                args.append(ctypes.byref(st))
+            check(getattr(self.lib, entry)(*args, current_stream()), entry)
+            return rgb, disp, acc, raw, mp
+        entry = "dfn_nerfh_generic_render_rays_maps" if names else "dfn_nerfh_generic_render_rays_v"
         C = self.GENERIC_CHUNK
         ws = self._workspace(self.lib.dfn_nerfh_generic_workspace_bytes(self.handle, min(n, C), Nc, Ni), dev)
-        raw_tmp = None if retraw else torch.empty(min(n, C), Nf, 9, device=dev)
+        raw_tmp = None if retraw else torch.empty(min(n, C), Nc + Ni, 9, device=dev)
         for r0 in range(0, n, C):
             m = min(C, n - r0)
-            h = hist if hist.shape[0] == 1 else hist[r0:r0 + m]
-            raw = raw_all[r0:r0 + m] if retraw else raw_tmp[:m]
-            v = None if viewdirs is None else viewdirs[r0:r0 + m]
-            st = _maps_at(out, r0, m)
-            check(self.lib.dfn_nerfh_generic_render_rays_maps(self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(v), ptr(h),
-                                                              h.shape[0], m, Nc, Ni, float(near), float(far), ptr(rgb[r0:r0 + m]),
-                                                              ptr(disp[r0:r0 + m]), ptr(acc[r0:r0 + m]), ptr(raw),
-                                                              ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.byref(st),
-                                                              current_stream()),
-                  "dfn_nerfh_generic_render_rays_maps")
-        return rgb, disp, acc, raw_all, out
+            cut = lambda t: None if t is None else t[r0:r0 + m]
+            h = hist if hist.shape[0] == 1 else cut(hist)
+            args = [self.handle, ptr(cut(rays_o)), ptr(cut(rays_d)), ptr(cut(viewdirs)), ptr(h), h.shape[0], m, Nc, Ni, float(near), float(far),
+                    ptr(cut(rgb)), ptr(cut(disp)), ptr(cut(acc)), ptr(cut(raw) if retraw else raw_tmp[:m]),
+                    ctypes.c_void_p(ws.data_ptr()), ws.numel()]
+            if names:
+                args.append(ctypes.byref(_maps_at(mp, r0, m)))
+            check(getattr(self.lib, entry)(*args, current_stream()), entry)
+        return rgb, disp, acc, raw, mp
 
-    def render_rays_maps(self, rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs=None, retraw=False, precision=None, maps=MAP_NAMES):
-        """render_rays that also returns the maps the compositor forms and the plain render drops (models/rendering.py:196-241):
-        (rgb [n,3], disp [n], acc [n], raw|None, {name: map}) with depth, depth_static, beta [n] and rgb_static, rgb_transient [n,3].
-        maps: an iterable of those names (default: all five).  rgb / disp / acc are the bits render_rays returns."""
-        if not self.fast or precision == "generic":
-            return self.generic_render_rays_maps(rays_o, rays_d, hist, Nc, Ni, near, far, retraw, viewdirs=viewdirs, maps=maps)
-        names = map_names(maps)
-        rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
-        n = rays_o.shape[0]
-        dev = rays_o.device
-        hist = _f32c(hist).reshape(-1, self.hist_bin)
-        if viewdirs is not None:
-            viewdirs = _f32c(viewdirs).reshape(-1, 3)
-        rgb = torch.empty(n, 3, device=dev)
-        disp = torch.empty(n, device=dev)
-        acc = torch.empty(n, device=dev)
-        raw = torch.empty(n, Nc + Ni, 9, device=dev) if retraw else None
-        out, st = _alloc_maps(names, n, dev)
-        ws = self._workspace(self.lib.dfn_render_maps_workspace_bytes(n, Nc, Ni), dev)
-        check(self.lib.dfn_render_rays_maps(self.handle, self._prec(precision), ptr(rays_o), ptr(rays_d), ptr(viewdirs),
-                                            ptr(hist), hist.shape[0], n, Nc, Ni, float(near), float(far), ptr(rgb),
-                                            ptr(disp), ptr(acc), ptr(raw), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                            ctypes.byref(st), current_stream()), "dfn_render_rays_maps")
-        return rgb, disp, acc, raw, out
-
-    def render_image_maps(self, c2w, H, W, focal, hist, Nc, Ni, near, far, precision=None, out=None, maps=MAP_NAMES):
-        """render_image with the maps of render_rays_maps, shaped like the image: (rgb [H,W,3], disp, acc [H,W], None,
-        {name: [H,W] or [H,W,3]})."""
-        names = map_names(maps)
+    def _render_image(self, c2w, H, W, focal, hist, Nc, Ni, near, far, precision=None, out=None, names=()):
+        """The test-time render of a full image behind render_image and render_image_maps -> (rgb [H,W,3], disp [H,W], acc [H,W],
+        {name: [H,W] or [H,W,3]}), into the three tensors of `out` when given.  names as in _render_rays."""
         c2w = _f32c(c2w)[:3, :4].contiguous()
         dev = c2w.device
         hist = _f32c(hist).reshape(-1)[: self.hist_bin].contiguous()
-        shaped = lambda d: {k: v.reshape(H, W, *v.shape[1:]) for k, v in d.items()}
-        if not self.fast or precision == "generic":
+        if self.fast and precision != "generic":
+            res = rgb, disp, acc = tuple(out) if out is not None else (torch.empty(H, W, 3, device=dev), torch.empty(H, W, device=dev),
+                                                                        torch.empty(H, W, device=dev))
+            mp, st = _alloc_maps(names, H * W, dev)
+            entry = "dfn_render_image_maps" if names else "dfn_render_image"
+            size = self.lib.dfn_render_maps_workspace_bytes if names else self.lib.dfn_render_workspace_bytes
+            ws = self._workspace(size(H * W, Nc, Ni), dev)
+            args = [self.handle, self._prec(precision), ptr(c2w), H, W, float(focal), float(near), float(far), Nc, Ni, ptr(hist),
+                    ptr(rgb), ptr(disp), ptr(acc), ctypes.c_void_p(ws.data_ptr()), ws.numel()]
+            if names:
+                args.append(ctypes.byref(st))
+            check(getattr(self.lib, entry)(*args, current_stream()), entry)
+        else:   # get_rays, then the generic-width ray batch
             o, d, _ = raygen(H, W, focal, c2w, want_viewdirs=False)
-            rgb, disp, acc, _, mp = self.generic_render_rays_maps(o.reshape(-1, 3), d.reshape(-1, 3), hist, Nc, Ni, near, far, maps=names)
+            rgb, disp, acc, _, mp = self._render_rays(o.reshape(-1, 3), d.reshape(-1, 3), hist, Nc, Ni, near, far, precision="generic",
+                                                      names=names)
             res = (rgb.reshape(H, W, 3), disp.reshape(H, W), acc.reshape(H, W))
             if out is not None:
                 for dst, src in zip(out, res):
                     dst.copy_(src)
                 res = tuple(out)
-            return res + (None, shaped(mp))
-        if out is None:
-            out = (torch.empty(H, W, 3, device=dev), torch.empty(H, W, device=dev), torch.empty(H, W, device=dev))
-        rgb, disp, acc = out
-        mp, st = _alloc_maps(names, H * W, dev)
-        ws = self._workspace(self.lib.dfn_render_maps_workspace_bytes(H * W, Nc, Ni), dev)
-        check(self.lib.dfn_render_image_maps(self.handle, self._prec(precision), ptr(c2w), H, W, float(focal), float(near),
-                                             float(far), Nc, Ni, ptr(hist), ptr(rgb), ptr(disp), ptr(acc),
-                                             ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.byref(st), current_stream()),
-              "dfn_render_image_maps")
-        return rgb, disp, acc, None, shaped(mp)
+        return res + ({k: v.reshape(H, W, *v.shape[1:]) for k, v in mp.items()},)
+
+    def render_rays(self, rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs=None, retraw=False, precision=None):
+        """Test-time render of a ray batch -> (rgb [n,3], disp [n], acc [n], raw|None).  viewdirs [n,3]: the fine network's view
+        directions, used as given (None: d/|d|)."""
+        return self._render_rays(rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs, retraw, precision)[:4]
+
+    def generic_render_rays(self, rays_o, rays_d, hist, Nc, Ni, near, far, retraw=False, viewdirs=None):
+        """render_rays on the generic-width path whatever the netwidth: exact fp32."""
+        return self._render_rays(rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs, retraw, "generic")[:4]
+
+    def render_image(self, c2w, H, W, focal, hist, Nc, Ni, near, far, precision=None, out=None):
+        """Test-time render of a full image from a [3,4] (or [4,4]) c2w -> (rgb [H,W,3], disp, acc [H,W])."""
+        return self._render_image(c2w, H, W, focal, hist, Nc, Ni, near, far, precision, out)[:3]
+
+    # ------------------------------------------------------------------ render maps
+    def render_rays_maps(self, rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs=None, retraw=False, precision=None, maps=MAP_NAMES):
+        """render_rays that also returns the maps the compositor forms and the plain render drops (models/rendering.py:196-241):
+        (rgb [n,3], disp [n], acc [n], raw|None, {name: map}) with depth, depth_static, beta [n] and rgb_static, rgb_transient [n,3].
+        maps: an iterable of those names (default: all five; none: render_rays).  rgb / disp / acc are the bits render_rays returns."""
+        return self._render_rays(rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs, retraw, precision, map_names(maps))
+
+    def generic_render_rays_maps(self, rays_o, rays_d, hist, Nc, Ni, near, far, retraw=False, viewdirs=None, maps=MAP_NAMES):
+        """generic_render_rays with the requested maps, chunked the same way: (rgb, disp, acc, raw|None, {name: map})."""
+        return self._render_rays(rays_o, rays_d, hist, Nc, Ni, near, far, viewdirs, retraw, "generic", map_names(maps))
+
+    def render_image_maps(self, c2w, H, W, focal, hist, Nc, Ni, near, far, precision=None, out=None, maps=MAP_NAMES):
+        """render_image with the maps of render_rays_maps, shaped like the image: (rgb [H,W,3], disp, acc [H,W], None,
+        {name: [H,W] or [H,W,3]})."""
+        res = self._render_image(c2w, H, W, focal, hist, Nc, Ni, near, far, precision, out, map_names(maps))
+        return res[:3] + (None, res[3])
 
     def composite_fine_maps(self, raw, z, beta_min=0.1, maps=MAP_NAMES):
         """The maps from raw [n,Nf,9] and z [n,Nf] (the module-level composite_fine_maps)."""
@@ -480,24 +428,19 @@ class NerfHEngine:
             gv = torch.empty(n, 3, device=dev)
         if generic:
             # the register-resident gradient kernels are netwidth 128; every other width takes the layer-by-layer exact-fp32 path
+            entry = "dfn_nerfh_generic_render_rays_backward_raw" if held is None else "dfn_nerfh_generic_render_rays_backward_maps"
             C = self.GENERIC_GRAD_CHUNK
             ws = self._workspace(self.lib.dfn_nerfh_generic_backward_workspace_bytes(self.handle, min(n, C), Nc, Ni), dev)
-            cut = lambda t, r0, m: None if t is None else t[r0:r0 + m]
             for r0 in range(0, n, C):
                 m = min(C, n - r0)
-                hh = hist if hist.shape[0] == 1 else hist[r0:r0 + m]
+                cut = lambda t: None if t is None else t[r0:r0 + m]
+                hh = hist if hist.shape[0] == 1 else cut(hist)
+                args = [self.handle, ptr(cut(rays_o)), ptr(cut(rays_d)), ptr(cut(viewdirs)), ptr(hh), hh.shape[0], m, Nc, Ni, float(near),
+                        float(far), ptr(cut(grad_rgb)), ptr(cut(grad_raw)), ptr(cut(go)), ptr(cut(gd)), ptr(cut(gv)),
+                        ctypes.c_void_p(ws.data_ptr()), ws.numel()]
                 if held is not None:
-                    check(self.lib.dfn_nerfh_generic_render_rays_backward_maps(
-                        self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(cut(viewdirs, r0, m)), ptr(hh), hh.shape[0], m, Nc, Ni,
-                        float(near), float(far), ptr(cut(grad_rgb, r0, m)), ptr(cut(grad_raw, r0, m)), ptr(go[r0:r0 + m]), ptr(gd[r0:r0 + m]),
-                        ptr(cut(gv, r0, m)), ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.byref(_map_grads_at(held, r0, m)),
-                        current_stream()), "dfn_nerfh_generic_render_rays_backward_maps")
-                    continue
-                check(self.lib.dfn_nerfh_generic_render_rays_backward_raw(
-                    self.handle, ptr(rays_o[r0:r0 + m]), ptr(rays_d[r0:r0 + m]), ptr(cut(viewdirs, r0, m)), ptr(hh), hh.shape[0], m, Nc, Ni,
-                    float(near), float(far), ptr(cut(grad_rgb, r0, m)), ptr(cut(grad_raw, r0, m)), ptr(go[r0:r0 + m]), ptr(gd[r0:r0 + m]),
-                    ptr(cut(gv, r0, m)), ctypes.c_void_p(ws.data_ptr()), ws.numel(), current_stream()),
-                    "dfn_nerfh_generic_render_rays_backward_raw")
+                    args.append(ctypes.byref(_map_grads_at(held, r0, m)))
+                check(getattr(self.lib, entry)(*args, current_stream()), entry)
             return go, gd, gv
         ws = self._workspace(self.lib.dfn_render_backward_workspace_bytes(n, Nc, Ni), dev)
         check(self.lib.dfn_render_rays_backward(self.handle, self._prec(precision), ptr(rays_o), ptr(rays_d), ptr(viewdirs),

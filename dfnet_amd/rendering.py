@@ -23,6 +23,10 @@ rgb only) unless render(..., diff_maps=True) is asked for: then disp_map, acc_ma
 too (as in the reference, where they are torch expressions of raw, rendering.py:161-243), through the compositing backward for every
 output (dfn_composite_fine_backward_maps) and the same network gradient.  The MLP gradient kernel defaults to the exact-fp32 MFMA path (`GRAD_PRECISION`), see
 tests/test_gpu_grad.py.
+
+There is one tracked forward (`_tracked_forward`) and one tracked backward (`_tracked_backward`) under all three Functions (`_RenderImageFn`,
+`_RenderFramesFn`, `_RenderRaysFn`; diff_maps is a mode of the last).  The forward notes its route on ctx — generic width, one-pass or two-pass —
+with Nc, Ni, near, far and lindisp as plain Python values; only tensors go through save_for_backward.
 """
 import os
 import time
@@ -66,38 +70,53 @@ def _two_pass():
     return GRAD_TWO_PASS and GRAD_PRECISION == "f16x3"
 
 
-def _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far, retraw=False):
-    """(rgb, disp, acc, saved tensors for the backward); with retraw at a generic width: (rgb, disp, acc, saved, raw)."""
+def _tracked_forward(ctx, eng, o, d, v, hist, Nc, Ni, near, far, retraw=False, names=()):
+    """The forward of every tracked render -> (rgb, disp, acc, {name: map} for `names`, raw if retraw else None).  Leaves on ctx
+    what _tracked_backward starts from: the engine, the route taken and the render options as plain Python state, the tensors
+    through save_for_backward."""
+    ctx.eng, ctx.opts = eng, (Nc, Ni, near, far, eng.lindisp)
     if eng.width != 128:
         # the register-resident gradient kernels (and their saved state) are netwidth 128: other widths render as usual and the
         # backward is the stateless generic-width gradient, which recomputes the forward layer by layer in exact fp32.  At
         # netwidth 256 (fast render kernels) GRAD_FORWARD_PRECISION, when set, names the arithmetic of this tracked forward.
+        ctx.route = "generic"
         prec = GRAD_FORWARD_PRECISION if eng.fast else None
-        rgb, disp, acc, raw = eng.render_rays(o, d, hist, Nc, Ni, near, far, retraw=retraw, precision=prec)
-        saved = (o, d, v, hist, torch.tensor([Nc, Ni, near, far, float(eng.lindisp)], dtype=torch.float64))
-        return (rgb, disp, acc, saved, raw) if retraw else (rgb, disp, acc, saved)
-    if _two_pass():
-        rgb, disp, acc, z, raw, masks = eng.render_rays_saving(o, d, v, hist, Nc, Ni, near, far, precision=GRAD_FORWARD_PRECISION,
-                                                             with_masks=True)
-        return rgb, disp, acc, (o, d, v, hist, z, raw, masks)
-    rgb, disp, acc, z, raw = eng.render_rays_saving(o, d, v, hist, Nc, Ni, near, far, precision=GRAD_FORWARD_PRECISION)
-    return rgb, disp, acc, (o, d, v, hist, z, raw)
+        rgb, disp, acc, raw, maps = eng.render_rays_maps(o, d, hist, Nc, Ni, near, far, retraw=retraw, precision=prec, maps=names)
+        ctx.save_for_backward(o, d, hist)
+        return rgb, disp, acc, maps, raw   # no raw is kept (the gradient recomputes it): the rendered tensor is the caller's own
+    ctx.route = "two_pass" if _two_pass() else "one_pass"
+    rgb, disp, acc, z, raw, *masks = eng.render_rays_saving(o, d, v, hist, Nc, Ni, near, far, precision=GRAD_FORWARD_PRECISION,
+                                                           with_masks=ctx.route == "two_pass")
+    ctx.save_for_backward(o, d, v, hist, z, raw, *masks)
+    maps = eng.composite_fine_maps(raw, z, maps=names) if names else {}
+    # the caller's raw is a copy: an in-place edit of it must not reach the state the backward reads
+    return rgb, disp, acc, maps, (raw.clone() if retraw else None)
 
 
-def _saved_backward(eng, saved, g_rgb, g_raw=None):
-    if len(saved) == 5:   # generic width: (rays, viewdirs = d / |d|, histograms, [Nc, Ni, near, far])
-        o, d, _, hist, cfg = saved
-        Nc, Ni, near, far, lindisp = cfg.tolist()
-        eng.set_render_options(lindisp=bool(lindisp))
-        if g_rgb is None and g_raw is None:
-            g_rgb = torch.zeros(o.shape[0], 3, device=o.device)
-        return eng.render_rays_backward(o, d, hist, int(Nc), int(Ni), near, far, None if g_rgb is None else g_rgb.contiguous(),
-                                        precision="generic", grad_raw=None if g_raw is None else g_raw.contiguous())
-    if g_rgb is None:
-        g_rgb = torch.zeros(saved[0].shape[0], 3, device=saved[0].device)
+def _tracked_backward(ctx, g_rgb, g_raw=None, g_maps=None):
+    """(d L/d rays_o, d L/d rays_d, None) from the state _tracked_forward left on ctx.  g_raw: d L/d of the raw that retraw returned.
+    g_maps None: d L/d rgb alone (never None: autograd materialises an unused output's gradient as zeros), through the rgb-only
+    compositing backward (composite_fine_backward; g_raw is added afterwards).
+    g_maps = {name: d L/d output or None} (diff_maps): with g_rgb, the upstream gradients of every compositor output, through
+    composite_fine_backward_maps (g_raw is added in that kernel); an output the loss does not use is None = a NULL pointer.
+    The two compositing backwards are different kernels with different rounding."""
+    eng, saved = ctx.eng, ctx.saved_tensors
+    Nc, Ni, near, far, lindisp = ctx.opts
+    if g_maps is not None:
+        g_maps = {k: g for k, g in dict(g_maps, rgb=g_rgb).items() if g is not None}
+        g_rgb = None
+        if not g_maps and g_raw is None:
+            g_maps = dict(rgb=torch.zeros(saved[0].shape[0], 3, device=saved[0].device))
+    if ctx.route == "generic":
+        o, d, hist = saved
+        eng.set_render_options(lindisp=lindisp)
+        return eng.render_rays_backward(o, d, hist, Nc, Ni, near, far, g_rgb, precision="generic", grad_raw=g_raw, grad_maps=g_maps)
     o, d, v, hist, z, raw = saved[:6]
-    masks = saved[6] if len(saved) > 6 else None
-    return eng.backward_from_saved(o, d, v, hist, z, raw, g_rgb.contiguous(), True, precision=GRAD_PRECISION, masks=masks, grad_raw=g_raw)
+    masks = saved[6] if ctx.route == "two_pass" else None
+    if g_maps is None:
+        return eng.backward_from_saved(o, d, v, hist, z, raw, g_rgb, True, precision=GRAD_PRECISION, masks=masks, grad_raw=g_raw)
+    graw = eng.composite_fine_backward_maps(raw, z, g_maps, grad_raw=g_raw)
+    return eng.backward_from_saved(o, d, v, hist, z, raw, None, True, precision=GRAD_PRECISION, masks=masks, graw=graw)
 
 
 class _RenderImageFn(torch.autograd.Function):
@@ -109,9 +128,8 @@ class _RenderImageFn(torch.autograd.Function):
     def forward(ctx, c2w, eng, H, W, focal, hist, Nc, Ni, near, far):
         from . import engine as _e
         o, d, v = _e.raygen(H, W, focal, c2w.detach())
-        rgb, disp, acc, saved = _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far)
-        ctx.save_for_backward(*saved)
-        ctx.cfg = (eng, H, W, focal)
+        rgb, disp, acc, _, _ = _tracked_forward(ctx, eng, o, d, v, hist, Nc, Ni, near, far)
+        ctx.cfg = (H, W, focal)
         disp, acc = disp.reshape(H, W), acc.reshape(H, W)
         ctx.mark_non_differentiable(disp, acc)
         return rgb.reshape(H, W, 3), disp, acc
@@ -119,9 +137,8 @@ class _RenderImageFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rgb, _g_disp, _g_acc):
         from . import engine as _e
-        eng, H, W, focal = ctx.cfg
-        go, gd, _ = _saved_backward(eng, ctx.saved_tensors, g_rgb)
-        return (_e.raygen_backward(H, W, focal, go, gd),) + (None,) * 9
+        go, gd, _ = _tracked_backward(ctx, g_rgb)
+        return (_e.raygen_backward(*ctx.cfg, go, gd),) + (None,) * 9
 
 
 class _RaygenFn(torch.autograd.Function):
@@ -154,16 +171,15 @@ class _RenderFramesFn(torch.autograd.Function):
         B = c2ws.shape[0]
         o, d, v = (t.reshape(-1, 3) for t in _e.raygen_frames(H, W, focal, c2ws.detach()))
         hist = hists.reshape(B, 1, -1).expand(B, H * W, hists.shape[-1]).reshape(B * H * W, -1).contiguous()   # one row per ray
-        rgb, _, _, saved = _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far)
-        ctx.save_for_backward(*saved)
-        ctx.cfg = (eng, B, H, W, focal)
+        rgb = _tracked_forward(ctx, eng, o, d, v, hist, Nc, Ni, near, far)[0]
+        ctx.cfg = (B, H, W, focal)
         return rgb.reshape(B, H, W, 3)
 
     @staticmethod
     def backward(ctx, g_rgb):
         from . import engine as _e
-        eng, B, H, W, focal = ctx.cfg
-        go, gd, _ = _saved_backward(eng, ctx.saved_tensors, g_rgb)
+        B, H, W, focal = ctx.cfg
+        go, gd, _ = _tracked_backward(ctx, g_rgb)
         gc = _e.raygen_frames_backward(H, W, focal, go.reshape(B, H * W, 3), gd.reshape(B, H * W, 3))
         return (gc,) + (None,) * 9
 
@@ -185,79 +201,32 @@ def render_frames(H, W, focal, c2ws, img_idx, **kwargs):
 
 
 class _RenderRaysFn(torch.autograd.Function):
-    """rgb/disp/acc[/raw] = render(rays); backward: d L/d rays_o, d L/d rays_d (viewdirs = d/|d| differentiated) from d L/d rgb and,
-    with retraw, d L/d raw [n,Nf,9] (rendering.py:353-400 with retraw=True under autograd: `raw` is a function of the sample points and
-    view directions, the depths are detached).  The fine network's backward is a full vector-Jacobian product of all nine raw channels,
-    so an external d L/d raw is ADDED to the compositor's d L/d raw before it."""
+    """(rgb, disp, acc, *maps[, raw]) = render(rays); backward: d L/d rays_o, d L/d rays_d (viewdirs = d/|d| differentiated).
+    With retraw, `raw` [n,Nf,9] is attached too (rendering.py:353-400 with retraw=True under autograd: a function of the sample points and
+    view directions, the depths are detached): the fine network's backward is a full vector-Jacobian product of all nine raw channels,
+    so an external d L/d raw is ADDED to the compositor's d L/d raw before it.
+    names None: rgb (and raw) alone are differentiable, disp and acc come back detached and there are no maps.
+    names a tuple (render(diff_maps=True)): EVERY output is attached - disp_map, acc_map and the maps named by ret_maps are differentiable
+    functions of raw in the reference (raw2outputs_NeRFW, rendering.py:161-243) - and their upstream gradients go through the compositing
+    backward for every output (_tracked_backward)."""
 
     @staticmethod
-    def forward(ctx, rays_o, rays_d, eng, hist, Nc, Ni, near, far, retraw=False):
+    def forward(ctx, rays_o, rays_d, eng, hist, Nc, Ni, near, far, retraw=False, names=None):
         o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
         v = d / torch.norm(d, dim=-1, keepdim=True)
-        rgb, disp, acc, saved, *gen_raw = _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far, retraw=retraw)
-        ctx.eng = eng
-        ctx.mark_non_differentiable(disp, acc)
-        if retraw:
-            # the caller's tensor: an in-place edit of it must not reach the state the backward reads (generic widths keep no raw: the
-            # stateless gradient recomputes it, so the rendered tensor is the caller's own)
-            raw = gen_raw[0] if len(saved) == 5 else saved[5].clone()
-            ctx.save_for_backward(*saved)
-            return rgb, disp, acc, raw
-        ctx.save_for_backward(*saved)
-        return rgb, disp, acc
-
-    @staticmethod
-    def backward(ctx, g_rgb, _g_disp, _g_acc, g_raw=None):
-        go, gd, _ = _saved_backward(ctx.eng, ctx.saved_tensors, g_rgb, g_raw)
-        return (go, gd) + (None,) * 7
-
-
-class _RenderRaysMapsFn(torch.autograd.Function):
-    """render(rays, diff_maps=True): (rgb, disp, acc, *maps[, raw]) with EVERY output attached — disp_map, acc_map and the maps named by
-    ret_maps are differentiable functions of raw in the reference (raw2outputs_NeRFW, rendering.py:161-243).  backward: the upstream
-    gradients of all of them go through the compositing backward for every output (composite_fine_backward_maps; d L/d raw of retraw is
-    added in the same kernel), then through the fine network's gradient exactly as _RenderRaysFn does.  Netwidth 128: the saved-state
-    route (two-pass or one-pass); other widths: the stateless generic-width gradient (dfn_nerfh_generic_render_rays_backward_maps)."""
-
-    @staticmethod
-    def forward(ctx, rays_o, rays_d, eng, hist, Nc, Ni, near, far, retraw, names):
-        o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
-        v = d / torch.norm(d, dim=-1, keepdim=True)
-        if eng.width != 128:
-            prec = GRAD_FORWARD_PRECISION if eng.fast else None   # as _saving_forward
-            if names:
-                rgb, disp, acc, raw, mp = eng.render_rays_maps(o, d, hist, Nc, Ni, near, far, retraw=retraw, precision=prec, maps=names)
-            else:
-                (rgb, disp, acc, raw), mp = eng.render_rays(o, d, hist, Nc, Ni, near, far, retraw=retraw, precision=prec), {}
-            saved = (o, d, v, hist, torch.tensor([Nc, Ni, near, far, float(eng.lindisp)], dtype=torch.float64))
+        ctx.names, ctx.retraw = names, retraw
+        rgb, disp, acc, maps, raw = _tracked_forward(ctx, eng, o, d, v, hist, Nc, Ni, near, far, retraw, names or ())
+        if names is None:
+            ctx.mark_non_differentiable(disp, acc)
         else:
-            rgb, disp, acc, saved = _saving_forward(eng, o, d, v, hist, Nc, Ni, near, far)
-            mp = eng.composite_fine_maps(saved[5], saved[4], maps=names) if names else {}
-            raw = saved[5].clone() if retraw else None   # the caller's tensor: an in-place edit must not reach the saved state
-        ctx.eng, ctx.names, ctx.retraw = eng, names, retraw
-        ctx.save_for_backward(*saved)
-        ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None = a NULL upstream pointer
-        return (rgb, disp, acc) + tuple(mp[k] for k in names) + ((raw,) if retraw else ())
+            ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None = a NULL upstream pointer
+        return (rgb, disp, acc) + tuple(maps[k] for k in names or ()) + ((raw,) if retraw else ())
 
     @staticmethod
     def backward(ctx, g_rgb, g_disp, g_acc, *rest):
-        eng, names, saved = ctx.eng, ctx.names, ctx.saved_tensors
-        grads = dict(zip(("rgb", "disp", "acc") + tuple(names), (g_rgb, g_disp, g_acc) + tuple(rest[:len(names)])))
-        grads = {k: g for k, g in grads.items() if g is not None}
-        g_raw = rest[len(names)] if ctx.retraw else None
-        if not grads and g_raw is None:
-            grads = dict(rgb=torch.zeros(saved[0].shape[0], 3, device=saved[0].device))
-        if len(saved) == 5:   # generic width (see _saved_backward)
-            o, d, _, hist, cfg = saved
-            Nc, Ni, near, far, lindisp = cfg.tolist()
-            eng.set_render_options(lindisp=bool(lindisp))
-            go, gd, _ = eng.render_rays_backward(o, d, hist, int(Nc), int(Ni), near, far, None, precision="generic",
-                                                 grad_raw=None if g_raw is None else g_raw.contiguous(), grad_maps=grads)
-        else:
-            o, d, v, hist, z, raw = saved[:6]
-            masks = saved[6] if len(saved) > 6 else None
-            graw = eng.composite_fine_backward_maps(raw, z, grads, grad_raw=g_raw)
-            go, gd, _ = eng.backward_from_saved(o, d, v, hist, z, raw, None, True, precision=GRAD_PRECISION, masks=masks, graw=graw)
+        g_raw = rest[-1] if ctx.retraw else None
+        g_maps = None if ctx.names is None else dict(zip(("disp", "acc") + ctx.names, (g_disp, g_acc) + rest))
+        go, gd, _ = _tracked_backward(ctx, g_rgb, g_raw, g_maps)
         return (go, gd) + (None,) * 8
 
 
@@ -294,6 +263,11 @@ def _check_test_time(kw, ndc, c2w_staticcam, use_viewdirs, training=False, track
     if bad:
         raise NotImplementedError("dfnet_amd render(): not implemented natively yet: " + "; ".join(bad) +
                                   " — there is deliberately no CPU fallback")
+
+
+def _shaped(lead, rgb, disp, acc, extras):
+    """render()'s return value from per-ray outputs: every tensor with its leading dimension reshaped to `lead`."""
+    return [rgb.reshape(lead + [3]), disp.reshape(lead), acc.reshape(lead), {k: v.reshape(lead + list(v.shape[1:])) for k, v in extras.items()}]
 
 
 def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
@@ -341,11 +315,11 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
                                                          int(kwargs['N_importance']), near, far, float(kwargs.get('perturb', 0.) or 0.),
                                                          float(kwargs.get('raw_noise_std', 0.) or 0.), bool(kwargs.get('retraw', False)),
                                                          draws=kwargs.get('draws'))
-        extras = {k: v.reshape(lead + list(v.shape[1:])) for k, v in extras.items()}
         # (no `stale` mark here: a render does not move the weights; HipQuery.refresh() sees optimizer steps through the tensors'
         #  version counters, and the training loop marks them itself)
-        return [rgb.reshape(lead + [3]), disp.reshape(lead), acc.reshape(lead), extras]
-    kwargs.get('network_query_fn').refresh() if hasattr(kwargs.get('network_query_fn'), 'refresh') else None
+        return _shaped(lead, rgb, disp, acc, extras)
+    if hasattr(kwargs.get('network_query_fn'), 'refresh'):
+        kwargs.get('network_query_fn').refresh()
     def _needs_grad(t):
         if torch.is_tensor(t):
             return t.requires_grad
@@ -359,16 +333,11 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     hist = torch.as_tensor(img_idx, dtype=torch.float32, device=dev)
 
     def _rays(o, d, h, lead, view=None):
-        """The untracked ray render; with ret_maps through the maps entry (the same rgb / disp / acc bits)."""
-        if map_list:
-            rgb, disp, acc, raw, mp = eng.render_rays_maps(o, d, h, Nc, Ni, near, far, viewdirs=view, retraw=retraw, maps=map_list)
-            extras = {k: v.reshape(lead + list(v.shape[1:])) for k, v in mp.items()}
-        else:
-            rgb, disp, acc, raw = eng.render_rays(o, d, h, Nc, Ni, near, far, viewdirs=view, retraw=retraw)
-            extras = {}
+        """The untracked ray render; the maps of ret_maps come with the same rgb / disp / acc bits."""
+        rgb, disp, acc, raw, extras = eng.render_rays_maps(o, d, h, Nc, Ni, near, far, viewdirs=view, retraw=retraw, maps=map_list)
         if retraw:
-            extras['raw'] = raw.reshape(lead + list(raw.shape[1:]))
-        return [rgb.reshape(lead + [3]), disp.reshape(lead), acc.reshape(lead), extras]
+            extras['raw'] = raw
+        return _shaped(lead, rgb, disp, acc, extras)
 
     if ndc or c2w_staticcam is not None:
         # rendering.py:364-376: the view directions come from the given rays / pose; the rays themselves are then replaced by the
@@ -387,22 +356,20 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         return _rays(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), hist, list(rays_d.shape[:-1]), view)
     if c2w is not None:
         c2w = torch.as_tensor(c2w, dtype=torch.float32, device=dev)
-        if track and not retraw and not diff_maps and hist.numel() == eng.hist_bin:
-            rgb, disp, acc = _RenderImageFn.apply(c2w[:3, :4], eng, int(H), int(W), float(focal), hist.reshape(-1), Nc, Ni,
-                                                  float(near), float(far))
-            return [rgb, disp, acc, {}]
-        if retraw or diff_maps or hist.numel() != eng.hist_bin:
+        if retraw or diff_maps or hist.numel() != eng.hist_bin:   # what the image entries do not do: through the image's rays
             if track and c2w.requires_grad:    # the pose reaches the ray gradients through get_rays' own node
                 o, d = (t.reshape(int(H), int(W), 3) for t in _RaygenFn.apply(c2w[:3, :4].contiguous(), int(H), int(W), float(focal)))
             else:
                 o, d = get_rays(H, W, focal, c2w)
             return render(H, W, focal, chunk, rays=(o, d), ndc=ndc, near=near, far=far, use_viewdirs=use_viewdirs,
                           img_idx=img_idx, ret_maps=map_list, diff_maps=diff_maps, **kwargs)
-        if map_list:
-            rgb, disp, acc, _, mp = eng.render_image_maps(c2w, int(H), int(W), float(focal), hist, Nc, Ni, near, far, maps=map_list)
-            return [rgb, disp, acc, mp]
-        rgb, disp, acc = eng.render_image(c2w, int(H), int(W), float(focal), hist, Nc, Ni, near, far)
-        return [rgb, disp, acc, {}]
+        if track:   # (ret_maps was refused above: the maps are differentiable only with diff_maps)
+            rgb, disp, acc = _RenderImageFn.apply(c2w[:3, :4], eng, int(H), int(W), float(focal), hist.reshape(-1), Nc, Ni,
+                                                  float(near), float(far))
+            extras = {}
+        else:
+            rgb, disp, acc, _, extras = eng.render_image_maps(c2w, int(H), int(W), float(focal), hist, Nc, Ni, near, far, maps=map_list)
+        return [rgb, disp, acc, extras]   # the image entries shape their outputs [H,W,...] themselves
     rays_o, rays_d = rays
     rays_o = torch.as_tensor(rays_o, dtype=torch.float32, device=dev)
     rays_d = torch.as_tensor(rays_d, dtype=torch.float32, device=dev)
@@ -412,19 +379,15 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     if hist.shape[0] not in (1, n):
         raise ValueError(f"img_idx must have 1 or {n} rows of {eng.hist_bin} bins, got {tuple(hist.shape)}")
     lead = list(sh[:-1])
-    if diff_maps:
-        out = _RenderRaysMapsFn.apply(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), eng, hist, Nc, Ni, float(near), float(far), retraw,
-                                      tuple(map_list))
-        extras = {k: t.reshape(lead + list(t.shape[1:])) for k, t in zip(map_list, out[3:])}
-        if retraw:
-            extras['raw'] = out[-1].reshape(lead + list(out[-1].shape[1:]))
-        return [out[0].reshape(lead + [3]), out[1].reshape(lead), out[2].reshape(lead), extras]
-    if track:
-        out = _RenderRaysFn.apply(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), eng, hist, Nc, Ni, float(near), float(far), retraw)
-        rgb, disp, acc = out[:3]
-        extras = {'raw': out[3].reshape(lead + list(out[3].shape[1:]))} if retraw else {}
-        return [rgb.reshape(lead + [3]), disp.reshape(lead), acc.reshape(lead), extras]
-    return _rays(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), hist, lead)
+    o, d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
+    if not track:
+        return _rays(o, d, hist, lead)
+    # diff_maps: every output attached, the maps of ret_maps among them; otherwise rgb (and raw) alone, and ret_maps was refused above
+    out = _RenderRaysFn.apply(o, d, eng, hist, Nc, Ni, float(near), float(far), retraw, tuple(map_list) if diff_maps else None)
+    extras = dict(zip(map_list, out[3:]))
+    if retraw:
+        extras['raw'] = out[-1]
+    return _shaped(lead, *out[:3], extras)
 
 
 def _write_png(path, arr8):

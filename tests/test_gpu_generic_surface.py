@@ -290,6 +290,19 @@ def test_explicit_viewdirs_on_the_generic_forward():
         assert rel_l2(x, y) < 1e-3, name
 
 
+def test_viewdirs_need_one_row_per_ray():
+    """The kernels read one view direction per ray: a shorter tensor is refused by every ray render, plain and with maps, on the
+    register-resident kernels (netwidth 128) as on the generic path, before anything is launched."""
+    Nc, Ni, n = 16, 32, 77
+    _, o, d, hist = ray_batch(n, 5)
+    args = (dev(o), dev(d), dev(hist), Nc, Ni, NEAR, FAR)
+    short = dev(rotated_viewdirs(d)[:n - 1])
+    for E in (engine(128, 4), engine(32, SEEDS[32])):
+        for call in (E.render_rays, E.render_rays_maps, E.generic_render_rays, E.generic_render_rays_maps):
+            with pytest.raises(ValueError, match=f"viewdirs must have {n} rows"):
+                call(*args, viewdirs=short)
+
+
 # ---------------------------------------------------------------------------------------------- 5. ndc / c2w_staticcam at test time
 def test_ndc_and_staticcam_at_netwidth_32(gold):
     """render(ndc=True) and render(c2w_staticcam=...) at a generic width against orc.render on the G14 fixture's pose and intrinsics
