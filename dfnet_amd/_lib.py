@@ -45,6 +45,12 @@ class MapGrads(Structure):
                 ("beta", c_void_p), ("rgb_static", c_void_p), ("rgb_transient", c_void_p)]
 
 
+class TrainMapGrads(Structure):
+    """dfn_train_map_grads (include/dfnet_hip.h): upstream gradients of every output of the training render, NULL = zero"""
+    _fields_ = [("rgb", c_void_p), ("disp", c_void_p), ("acc", c_void_p), ("depth", c_void_p), ("beta", c_void_p), ("rgb0", c_void_p),
+                ("disp0", c_void_p), ("acc0", c_void_p), ("depth0", c_void_p)]
+
+
 MAP_NAMES = tuple(n for n, _ in RenderMaps._fields_)   # trailing shape: () for the first three, (3,) for the rgb_* maps
 
 
@@ -151,6 +157,13 @@ SIGNATURES = {
     "dfn_nerfw_loss": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_int, c_float, c_float, _P, _P, _P, _P, _P]),
     "dfn_nerfh_train_backward": (c_int, [_P, POINTER(c_void_p), _P, c_size_t, c_size_t, c_int, c_int, _P, c_float, _P, _P, _P, _P,
                                          c_float, _P, POINTER(c_void_p), _P, c_size_t, _P]),
+    "dfn_composite_coarse_train_backward_maps": (c_int, [_P, _P, _P, c_float, c_size_t, c_int, POINTER(TrainMapGrads), _P, _P]),
+    "dfn_composite_fine_train_backward_maps": (c_int, [_P, _P, c_size_t, c_int, POINTER(TrainMapGrads), c_float, _P, _P, _P]),
+    "dfn_nerfh_train_depths": (c_int, [_P, c_size_t, c_int, c_int, _P, _P, c_size_t, _P, _P, _P]),
+    "dfn_nerfh_train_backward_maps": (c_int, [_P, POINTER(c_void_p), _P, c_size_t, c_size_t, c_int, c_int, _P, c_float, _P,
+                                              POINTER(TrainMapGrads), c_float, _P, POINTER(c_void_p), _P, c_size_t, _P]),
+    "dfn_nerfh_train_backward_rays_maps": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, _P, c_float, _P,
+                                                   POINTER(TrainMapGrads), c_float, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
     "dfn_nerfh_generic_workspace_bytes": (c_size_t, [_P, c_size_t, c_int, c_int]),
     "dfn_nerfh_generic_render_rays": (c_int, [_P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, c_float, c_float, _P, _P, _P, _P,
                                               _P, c_size_t, _P]),

@@ -407,6 +407,7 @@ struct NetWs {
 };
 struct Ws {
   float *view, *dir_c, *dir_f, *t_in, *raw_c, *gsum_f, *gsum_c, *gray, *wscratch, *partial;
+  float* depth0;   // per ray: the coarse depth sum w z (dfn_nerfh_train_depths)
   NetWs net[2];
   size_t partial_floats, total;
 };
@@ -511,6 +512,7 @@ Ws carve(char* base, const dfn_nerfh_desc& d, size_t R, int Nc, int Ni, bool spl
     w.partial_floats = floats;
     w.partial = takef(floats);
   }
+  w.depth0 = takef(R);   // (last: every other buffer stays where it was)
   w.total = off;
   return w;
 }
@@ -591,7 +593,7 @@ int train_forward(dfn_nerfh_s* h, const float* const* params, const float* rays_
     a.raw_out = w.raw_c;
     CHECK_HIP(launch_train_forward_chain(false, planes_of(false, h->train_split_fine), a, n_cu, s), "train forward: coarse chain");
   }
-  CHECK_HIP(sample_fine_train(w.raw_c, w.net[0].z, noise, raw_noise_std, u, R, Nc, Ni, w.net[1].z, rgb0, disp0, acc0, z_std, s),
+  CHECK_HIP(sample_fine_train(w.raw_c, w.net[0].z, noise, raw_noise_std, u, R, Nc, Ni, w.net[1].z, rgb0, disp0, acc0, z_std, s, w.depth0),
             "train forward: coarse composite + sampling");
   {
     ChainArgs a = chain_args(h, st, true, 0, w.net[1], rays_o, rays_d, R, Nf);
@@ -602,9 +604,20 @@ int train_forward(dfn_nerfh_s* h, const float* const* params, const float* rays_
   return DFN_OK;
 }
 
+int train_depth_state(dfn_nerfh_s* h, size_t R, int Nc, int Ni, void* workspace, size_t workspace_bytes_, const float** z_fine,
+                      const float** depth0) {
+  if (!h->fused) return set_error(DFN_ERR_STATE, "dfn_nerfh_train_depths: no forward pass on this handle");
+  const Ws w = carve(static_cast<char*>(workspace), h->desc, R, Nc, Ni, h->train_split_fine);
+  if (w.total > workspace_bytes_) return set_error(DFN_ERR_ARG, "dfn_nerfh_train_depths: workspace too small (%zu < %zu)", workspace_bytes_, w.total);
+  *z_fine = w.net[1].z;
+  *depth0 = w.depth0;
+  return DFN_OK;
+}
+
 int train_backward(dfn_nerfh_s* h, const float* const* params, const float* hist, size_t hist_rows, size_t R, int Nc, int Ni,
                    const float* noise, float raw_noise_std, const float* raw, const float* g_rgb, const float* g_rgb0, const float* g_beta,
-                   float g_tsigma, const float* g_tsigma_dense, float* const* grads, void* workspace, size_t workspace_bytes_, hipStream_t s) {
+                   float g_tsigma, const float* g_tsigma_dense, float* const* grads, void* workspace, size_t workspace_bytes_, hipStream_t s,
+                   const train::TrainMapGrads* maps, const float* raw_ext) {
   if (!h->fused) return set_error(DFN_ERR_STATE, "dfn_nerfh_train_backward: no forward pass on this handle");
   const State& st = *static_cast<State*>(h->fused);
   const Ws w = carve(static_cast<char*>(workspace), h->desc, R, Nc, Ni, h->train_split_fine);
@@ -619,11 +632,18 @@ int train_backward(dfn_nerfh_s* h, const float* const* params, const float* hist
   float* g_emb_a = grads[kCoarseParams + kFineParams];
   float* g_emb_t = grads[kCoarseParams + kFineParams + 1];
   const int n_cu = device_cu_count();
+  if (maps) {   // every output's upstream gradient (nerfh_train_maps.hip); the embedding gradients are zeroed by two memsets here
+    CHECK_HIP(hipMemsetAsync(g_emb_a, 0, size_t(d.n_vocab) * d.dim_a * sizeof(float), s), "train backward: zero embedding_a grad");
+    CHECK_HIP(hipMemsetAsync(g_emb_t, 0, size_t(d.n_vocab) * d.dim_t * sizeof(float), s), "train backward: zero embedding_t grad");
+    CHECK_HIP(composite_fine_backward_train_maps(raw, w.net[1].z, *maps, g_tsigma, raw_ext, R, Nf, w.net[1].gpre, s), "train backward: fine composite (maps)");
+    CHECK_HIP(composite_coarse_backward_maps(w.raw_c, w.net[0].z, noise, raw_noise_std, *maps, R, Nc, w.net[0].gpre, s), "train backward: coarse composite (maps)");
+  } else {
   CHECK_HIP(composite_fine_backward_train(raw, w.net[1].z, g_rgb, g_beta, g_tsigma, g_tsigma_dense, R, Nf, w.net[1].gpre, s), "train backward: fine composite");
   // (the coarse compositor also zeroes the two embedding gradients that the scatter kernels at the end of the pass accumulate into)
   CHECK_HIP(composite_coarse_backward(w.raw_c, w.net[0].z, noise, raw_noise_std, g_rgb0, R, Nc, w.net[0].gpre, s, g_emb_a,
                                       size_t(d.n_vocab) * d.dim_a, g_emb_t, size_t(d.n_vocab) * d.dim_t),
             "train backward: coarse composite");
+  }
   // data-gradient chains: every pre-activation gradient stored once, in the operand layout the weight-gradient stream reads
   // (the two networks' chains are independent — the coarse loss alone reaches the coarse network, rendering.py:302 detaches the
   // samples — and run as the two halves of ONE grid, the coarse chain's workgroups starting on the CUs the fine chain leaves first:

@@ -31,6 +31,12 @@
 struct dfn_nerfh_s;
 
 namespace dfn {
+namespace train {
+struct TrainMapGrads;   // nerfh_train.h
+}
+}
+
+namespace dfn {
 namespace fused {
 
 constexpr int kTilePoints = 256;   // points per workgroup tile of the chain kernels (8 waves x 32)
@@ -166,7 +172,13 @@ int train_forward(dfn_nerfh_s* h, const float* const* params, const float* rays_
                   float* beta, void* workspace, size_t workspace_bytes, hipStream_t s);
 int train_backward(dfn_nerfh_s* h, const float* const* params, const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni,
                    const float* noise, float raw_noise_std, const float* raw, const float* g_rgb, const float* g_rgb0, const float* g_beta,
-                   float g_tsigma, const float* g_tsigma_dense, float* const* grads, void* workspace, size_t workspace_bytes, hipStream_t s);
+                   float g_tsigma, const float* g_tsigma_dense, float* const* grads, void* workspace, size_t workspace_bytes, hipStream_t s,
+                   const train::TrainMapGrads* maps = nullptr, const float* raw_ext = nullptr);
+// maps != nullptr (dfn_nerfh_train_backward_maps): the compositing backward is nerfh_train_maps.hip's pair of kernels, from the upstream
+// gradients of every output (g_rgb / g_rgb0 / g_beta / g_tsigma_dense unused) + raw_ext; everything after it is the same.
+// Where the forward left the fine depths and the coarse depth sum w z in its workspace (dfn_nerfh_train_depths).
+int train_depth_state(dfn_nerfh_s* h, size_t n_rays, int Nc, int Ni, void* workspace, size_t workspace_bytes, const float** z_fine,
+                      const float** depth0);
 void destroy_state(dfn_nerfh_s* h);
 
 }  // namespace fused

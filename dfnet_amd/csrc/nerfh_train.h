@@ -69,9 +69,11 @@ hipError_t ray_inputs(const float* viewdirs, const float* hist, size_t hist_rows
                       hipStream_t s);
 // Coarse training composite + importance sampling + merge (rendering.py:295-304 with raw2outputs_NeRFW typ="coarse",
 // test_time=False): raw_c [R,Nc,4] = (rgb, sigma), z_c [R,Nc]; noise (nullable) x noise_std added to sigma before the
-// relu; u (nullable -> linspace) [R,Ni].  Outputs z_fine [R,Nc+Ni], rgb0 [R,3], disp0, acc0, z_std [R].
+// relu; u (nullable -> linspace) [R,Ni].  Outputs z_fine [R,Nc+Ni], rgb0 [R,3], disp0, acc0, z_std [R]; depth0 [R] (nullable):
+// the coarse depth sum w z of rendering.py:241 that disp0 is formed from (dfn_nerfh_train_depths reads it back from the workspace).
 hipError_t sample_fine_train(const float* raw_c, const float* z_c, const float* noise, float noise_std, const float* u, size_t R,
-                             int Nc, int Ni, float* z_fine, float* rgb0, float* disp0, float* acc0, float* z_std, hipStream_t s);
+                             int Nc, int Ni, float* z_fine, float* rgb0, float* disp0, float* acc0, float* z_std, hipStream_t s,
+                             float* depth0 = nullptr);
 // d L / d (pre-activation coarse outputs) [R,Nc,4] from d L / d rgb0 [R,3].
 hipError_t composite_coarse_backward(const float* raw_c, const float* z_c, const float* noise, float noise_std, const float* g_rgb0,
                                      size_t R, int Nc, float* gpre, hipStream_t s, float* zero0 = nullptr, size_t n0 = 0,
@@ -80,6 +82,21 @@ hipError_t composite_coarse_backward(const float* raw_c, const float* z_c, const
 // transient_sigma per sample (training compositing: joint rgb, beta = sum w_t beta_t + beta_min).
 hipError_t composite_fine_backward_train(const float* raw, const float* z, const float* g_rgb, const float* g_beta, float g_tsigma,
                                          const float* g_ts /* nullable dense [R,Nf] */, size_t R, int Nf, float* gpre, hipStream_t s);
+// Upstream gradients of EVERY output of the two training compositors (dfn_train_map_grads; nerfh_train_maps.hip), each optional
+// (null = zero): rgb, rgb0 [R,3]; the others [R].
+struct TrainMapGrads {
+  const float *rgb, *disp, *acc, *depth, *beta, *rgb0, *disp0, *acc0, *depth0;
+  bool any_fine() const { return rgb || disp || acc || depth || beta; }
+  bool any_coarse() const { return rgb0 || disp0 || acc0 || depth0; }
+};
+// composite_coarse_backward for all four outputs of the coarse pass: rgb0, acc0, depth0 = sum w z, disp0 = 1 / max(1e-10, depth0 / acc0).
+// rgb0 by composite_coarse_backward itself (bit for bit the default step's term), the other three written or added by a second kernel.
+hipError_t composite_coarse_backward_maps(const float* raw_c, const float* z_c, const float* noise, float noise_std,
+                                          const TrainMapGrads& g, size_t R, int Nc, float* gpre, hipStream_t s);
+// composite_fine_backward_train for all five outputs of the fine pass (rgb, beta, acc, depth = sum a T z, disp = 1 / max(1e-10, depth /
+// acc)), the constant d L / d transient_sigma and gext [R,Nf,9] (nullable): a gradient that reaches the post-activation raw directly.
+hipError_t composite_fine_backward_train_maps(const float* raw, const float* z, const TrainMapGrads& g, float g_tsigma,
+                                              const float* gext, size_t R, int Nf, float* gpre, hipStream_t s);
 // out[r, 0..C) = sum_s g[(r * Ns + s) * ld + c]
 hipError_t sum_over_samples(const float* g, int ld, int C, size_t R, int Ns, float* out, int ldo, hipStream_t s);
 // embedding-table gradients: grad_emb[idx(hist[r, b]), j] += g_in[r * ld + off + b * dim + j] (atomic fp32 adds).

@@ -1067,7 +1067,7 @@ __global__ __launch_bounds__(256) void sample_fine_train_kernel(const float* __r
                                                                 const float* __restrict__ u, size_t R, int Nc, int Ni,
                                                                 float* __restrict__ z_fine, float* __restrict__ rgb0,
                                                                 float* __restrict__ disp0, float* __restrict__ acc0,
-                                                                float* __restrict__ z_std) {
+                                                                float* __restrict__ z_std, float* __restrict__ depth0) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int Nf = Nc + Ni;
@@ -1109,6 +1109,7 @@ __global__ __launch_bounds__(256) void sample_fine_train_kernel(const float* __r
       for (int c = 0; c < 3; ++c) rgb0[ray * 3 + c] = c3[c];
       acc0[ray] = sa;
       disp0[ray] = 1.f / fmaxf(1e-10f, sd / sa);
+      if (depth0) depth0[ray] = sd;
     }
     // inverse-CDF sampling on the interior weights
     {
@@ -1200,11 +1201,12 @@ __global__ __launch_bounds__(256) void sample_fine_train_kernel(const float* __r
   }
 }
 hipError_t sample_fine_train(const float* raw_c, const float* z_c, const float* noise, float noise_std, const float* u, size_t R,
-                             int Nc, int Ni, float* z_fine, float* rgb0, float* disp0, float* acc0, float* z_std, hipStream_t s) {
+                             int Nc, int Ni, float* z_fine, float* rgb0, float* disp0, float* acc0, float* z_std, hipStream_t s,
+                             float* depth0) {
   if (!R) return hipSuccess;
   const int per = 4 * Nc + 2 * (Nc + Ni) + Ni;
   hipLaunchKernelGGL(sample_fine_train_kernel, dim3(grid_for((R + 3) / 4, 1)), dim3(256), size_t(4) * per * 4, s, raw_c, z_c, noise,
-                     noise_std, u, R, Nc, Ni, z_fine, rgb0, disp0, acc0, z_std);
+                     noise_std, u, R, Nc, Ni, z_fine, rgb0, disp0, acc0, z_std, depth0);
   return hipGetLastError();
 }
 

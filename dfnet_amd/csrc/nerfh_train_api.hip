@@ -98,6 +98,7 @@ struct TrainWs {
   float *z_f, *pe_f, *h_f[8], *fin_f, *dirh_f, *te[4];  // fine, per point
   float *gpre_f, *gpre_c, *gA, *gB, *gfin, *gt0, *gt1, *gsum, *gray, *wscratch;  // backward
   float *gA_c, *gB_c, *gfin_c, *gt0_c, *gsum_c, *gray_c, *wscratch_c;             // the coarse net's own scratch (it runs beside the fine one)
+  float* depth0;   // per ray: the coarse depth sum w z (dfn_nerfh_train_depths)
   size_t total;
 };
 TrainWs carve_train(float* base, const Dims& m, size_t R, int Nc, int Ni, bool with_backward) {
@@ -151,6 +152,7 @@ TrainWs carve_train(float* base, const Dims& m, size_t R, int Nc, int Ni, bool w
     w.gsum_c = take(R * m.W2);
     w.gray_c = take(R * size_t(m.ld_dc));
     w.wscratch_c = take(wscratch_floats((long long)Pc));
+    w.depth0 = take(R);   // (last: every other buffer stays where it was)
   }
   w.total = off * sizeof(float);
   return w;
@@ -300,6 +302,31 @@ NetBufs bufs_of(const TrainWs& w, const Dims& m, bool fine, float* raw_f, size_t
   return b;
 }
 
+// What the compositing-backward stage of a step starts from: the operands of NerfWLoss (dfn_nerfh_train_backward: maps == nullptr, the
+// two kernels of nerfh_train.hip) or the upstream gradients of every output (the *_maps entries: the two kernels of nerfh_train_maps.hip).
+// Everything downstream consumes the gpre it writes.
+struct CompGrads {
+  const float *g_rgb, *g_rgb0, *g_beta;
+  float g_tsigma;
+  const float* g_ts_dense;
+  const TrainMapGrads* maps;
+  const float* raw_ext;
+};
+TrainMapGrads map_grads_of(const dfn_train_map_grads* g) {
+  return g ? TrainMapGrads{g->rgb, g->disp, g->acc, g->depth, g->beta, g->rgb0, g->disp0, g->acc0, g->depth0} : TrainMapGrads{};
+}
+int composite_backward(const char* fn, const CompGrads& cg, const float* raw, const float* z_f, const float* raw_c, const float* z_c,
+                       const float* noise, float noise_std, size_t R, int Nc, int Nf, float* gpre_f, float* gpre_c, hipStream_t s) {
+  if (cg.maps) {
+    CHECK_HIP(composite_fine_backward_train_maps(raw, z_f, *cg.maps, cg.g_tsigma, cg.raw_ext, R, Nf, gpre_f, s), fn);
+    CHECK_HIP(composite_coarse_backward_maps(raw_c, z_c, noise, noise_std, *cg.maps, R, Nc, gpre_c, s), fn);
+    return DFN_OK;
+  }
+  CHECK_HIP(composite_fine_backward_train(raw, z_f, cg.g_rgb, cg.g_beta, cg.g_tsigma, cg.g_ts_dense, R, Nf, gpre_f, s), fn);
+  CHECK_HIP(composite_coarse_backward(raw_c, z_c, noise, noise_std, cg.g_rgb0, R, Nc, gpre_c, s), fn);
+  return DFN_OK;
+}
+
 int check_train_args(dfn_nerfh_t h, int Nc, int Ni, const char* fn) {
   if (!h) return set_error(DFN_ERR_ARG, "%s: null handle", fn);
   if (Nc < 3 || Ni < 1 || Nc + Ni > 512) return set_error(DFN_ERR_UNSUPPORTED, "%s: need 3 <= N_samples, 1 <= N_importance, sum <= 512", fn);
@@ -365,7 +392,7 @@ extern "C" int dfn_nerfh_train_forward(dfn_nerfh_t h, const float* const* params
   CHECK_HIP(stratified_z(t_rand, R, Nc, near, far, w.z_c, s, h->render_flags & DFN_RENDER_LINDISP), "train forward: stratified z");
   CHECK_HIP(posenc_points(rays_o, rays_d, w.z_c, R, Nc, w.pe_c, s), "train forward: coarse encoding");
   if (int rc = net_forward(nc, m, bufs_of(w, m, false, nullptr, R, Nc, Ni), false, false, s)) return rc;
-  CHECK_HIP(sample_fine_train(w.raw_c, w.z_c, noise, raw_noise_std, u, R, Nc, Ni, w.z_f, rgb0, disp0, acc0, z_std, s),
+  CHECK_HIP(sample_fine_train(w.raw_c, w.z_c, noise, raw_noise_std, u, R, Nc, Ni, w.z_f, rgb0, disp0, acc0, z_std, s, w.depth0),
             "train forward: coarse composite + sampling");
   CHECK_HIP(posenc_points(rays_o, rays_d, w.z_f, R, Nf, w.pe_f, s), "train forward: fine encoding");
   if (int rc = net_forward(nf, m, bufs_of(w, m, true, raw, R, Nc, Ni), true, false, s)) return rc;
@@ -383,31 +410,34 @@ extern "C" int dfn_nerfw_loss(const float* rgb, const float* rgb0, const float* 
   return DFN_OK;
 }
 
-extern "C" int dfn_nerfh_train_backward(dfn_nerfh_t h, const float* const* params, const float* hist, size_t hist_rows, size_t n_rays,
-                                        int Nc, int Ni, const float* noise, float raw_noise_std, const float* raw, const float* g_rgb,
-                                        const float* g_rgb0, const float* g_beta, float g_tsigma, const float* g_tsigma_dense, float* const* grads, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_backward")) return rc;
-  if (!n_rays) return DFN_OK;
-  if (!params || !grads || !hist || !raw || !g_rgb || !g_rgb0 || !g_beta || !workspace || (hist_rows != 1 && hist_rows != n_rays))
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward: bad argument");
-  for (int i = 0; i < kParamCount; ++i)
-    if (!params[i] || !grads[i]) return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward: params[%d] / grads[%d] is null", i, i);
-  // the workspace was laid out by the implementation that ran the forward: the other one's carve() would read foreign bytes
+namespace {
+// the workspace was laid out by the implementation that ran the forward: the other one's carve() would read foreign bytes
+int check_train_state(dfn_nerfh_t h, const char* fn) {
   if (h->train_forward_exact != !use_fused(h))
-    return set_error(DFN_ERR_STATE, "dfn_nerfh_train_backward: the last dfn_nerfh_train_forward ran the %s step, the handle is now in the %s "
-                     "mode (dfn_nerfh_set_train_mode between forward and backward)", h->train_forward_exact ? "exact" : "fused",
+    return set_error(DFN_ERR_STATE, "%s: the last dfn_nerfh_train_forward ran the %s step, the handle is now in the %s "
+                     "mode (dfn_nerfh_set_train_mode between forward and backward)", fn, h->train_forward_exact ? "exact" : "fused",
                      use_fused(h) ? "fused" : "exact");
   if (use_fused(h) && h->train_forward_split != h->train_split_fine)
-    return set_error(DFN_ERR_STATE, "dfn_nerfh_train_backward: DFN_TRAIN_FUSED / DFN_TRAIN_FUSED_SPLIT changed between forward and backward "
-                     "(dfn_nerfh_set_train_mode between forward and backward): the stored operands have the other layout");
+    return set_error(DFN_ERR_STATE, "%s: DFN_TRAIN_FUSED / DFN_TRAIN_FUSED_SPLIT changed between forward and backward "
+                     "(dfn_nerfh_set_train_mode between forward and backward): the stored operands have the other layout", fn);
+  return DFN_OK;
+}
+
+// dfn_nerfh_train_backward and dfn_nerfh_train_backward_maps: they differ in the compositing-backward stage alone (CompGrads)
+int train_backward_impl(const char* fn, dfn_nerfh_t h, const float* const* params, const float* hist, size_t hist_rows, size_t n_rays, int Nc,
+                        int Ni, const float* noise, float raw_noise_std, const float* raw, const CompGrads& cg, float* const* grads,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  if (!params || !grads || !hist || !raw || !workspace || (hist_rows != 1 && hist_rows != n_rays))
+    return set_error(DFN_ERR_ARG, "%s: bad argument", fn);
+  for (int i = 0; i < kParamCount; ++i)
+    if (!params[i] || !grads[i]) return set_error(DFN_ERR_ARG, "%s: params[%d] / grads[%d] is null", fn, i, i);
+  if (int rc = check_train_state(h, fn)) return rc;
   if (use_fused(h))
-    return fused::train_backward(h, params, hist, hist_rows, n_rays, Nc, Ni, noise, raw_noise_std, raw, g_rgb, g_rgb0, g_beta, g_tsigma,
-                                 g_tsigma_dense, grads, workspace, workspace_bytes, HS(stream));
+    return fused::train_backward(h, params, hist, hist_rows, n_rays, Nc, Ni, noise, raw_noise_std, raw, cg.g_rgb, cg.g_rgb0, cg.g_beta,
+                                 cg.g_tsigma, cg.g_ts_dense, grads, workspace, workspace_bytes, HS(stream), cg.maps, cg.raw_ext);
   const Dims m = dims_of(h->desc);
   const TrainWs w = carve_train(static_cast<float*>(workspace), m, n_rays, Nc, Ni, true);
-  if (w.total > workspace_bytes)
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+  if (w.total > workspace_bytes) return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.total);
   hipStream_t s = HS(stream);
   const size_t R = n_rays;
   const int Nf = Nc + Ni;
@@ -415,8 +445,9 @@ extern "C" int dfn_nerfh_train_backward(dfn_nerfh_t h, const float* const* param
   float* g_emb_t = grads[kCoarseParams + kFineParams + 1];
   CHECK_HIP(hipMemsetAsync(g_emb_a, 0, size_t(m.n_vocab) * m.dim_a * 4, s), "train backward: zero embedding_a grad");
   CHECK_HIP(hipMemsetAsync(g_emb_t, 0, size_t(m.n_vocab) * m.dim_t * 4, s), "train backward: zero embedding_t grad");
-  CHECK_HIP(composite_fine_backward_train(raw, w.z_f, g_rgb, g_beta, g_tsigma, g_tsigma_dense, R, Nf, w.gpre_f, s), "train backward: fine composite");
-  CHECK_HIP(composite_coarse_backward(w.raw_c, w.z_c, noise, raw_noise_std, g_rgb0, R, Nc, w.gpre_c, s), "train backward: coarse composite");
+  if (int rc = composite_backward("train backward: composite", cg, raw, w.z_f, w.raw_c, w.z_c, noise, raw_noise_std, R, Nc, Nf, w.gpre_f,
+                                  w.gpre_c, s))
+    return rc;
   BwdBufs gf{w.gpre_f, w.gA, w.gB, w.gfin, w.gt0, w.gt1, w.gsum, w.gray, w.wscratch};
   BwdBufs gc{w.gpre_c, w.gA_c, w.gB_c, w.gfin_c, w.gt0_c, nullptr, w.gsum_c, w.gray_c, w.wscratch_c};
   // The two networks' backward passes share nothing (z_samples.detach(), rendering.py:302): the coarse one — a third of the points,
@@ -437,6 +468,85 @@ extern "C" int dfn_nerfh_train_backward(dfn_nerfh_t h, const float* const* param
   CHECK_HIP(hipStreamWaitEvent(s, h->side_ev[1], 0), "train backward: join");
   return DFN_OK;
 }
+}  // namespace
+
+extern "C" int dfn_nerfh_train_backward(dfn_nerfh_t h, const float* const* params, const float* hist, size_t hist_rows, size_t n_rays,
+                                        int Nc, int Ni, const float* noise, float raw_noise_std, const float* raw, const float* g_rgb,
+                                        const float* g_rgb0, const float* g_beta, float g_tsigma, const float* g_tsigma_dense, float* const* grads, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_backward")) return rc;
+  if (!n_rays) return DFN_OK;
+  if (!g_rgb || !g_rgb0 || !g_beta) return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward: bad argument");
+  return train_backward_impl("dfn_nerfh_train_backward", h, params, hist, hist_rows, n_rays, Nc, Ni, noise, raw_noise_std, raw,
+                             CompGrads{g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense, nullptr, nullptr}, grads, workspace, workspace_bytes,
+                             stream);
+}
+
+extern "C" int dfn_nerfh_train_backward_maps(dfn_nerfh_t h, const float* const* params, const float* hist, size_t hist_rows, size_t n_rays,
+                                             int Nc, int Ni, const float* noise, float raw_noise_std, const float* raw,
+                                             const dfn_train_map_grads* grads, float g_tsigma, const float* grad_raw_ext,
+                                             float* const* grads_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_backward_maps")) return rc;
+  if (!n_rays) return DFN_OK;
+  const TrainMapGrads g = map_grads_of(grads);
+  if (!g.any_fine() && !g.any_coarse() && !grad_raw_ext && g_tsigma == 0.f)
+    return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward_maps: bad argument (no upstream gradient, no grad_raw_ext and no g_tsigma)");
+  return train_backward_impl("dfn_nerfh_train_backward_maps", h, params, hist, hist_rows, n_rays, Nc, Ni, noise, raw_noise_std, raw,
+                             CompGrads{nullptr, nullptr, nullptr, g_tsigma, nullptr, &g, grad_raw_ext}, grads_out, workspace,
+                             workspace_bytes, stream);
+}
+
+// ---- the stages on caller arrays, and the two depths of the forward
+extern "C" int dfn_composite_coarse_train_backward_maps(const float* raw_c, const float* z_c, const float* noise, float noise_std,
+                                                        size_t n_rays, int Nc, const dfn_train_map_grads* grads, float* gpre, void* stream) {
+  if (!n_rays) return DFN_OK;
+  if (!raw_c || !z_c || !gpre || Nc < 3 || Nc > 512)
+    return set_error(DFN_ERR_ARG, "dfn_composite_coarse_train_backward_maps: bad argument (3 <= Nc <= 512)");
+  const TrainMapGrads g = map_grads_of(grads);
+  if (!g.any_coarse())
+    return set_error(DFN_ERR_ARG, "dfn_composite_coarse_train_backward_maps: bad argument (none of rgb0, disp0, acc0, depth0 is given)");
+  CHECK_HIP(composite_coarse_backward_maps(raw_c, z_c, noise, noise_std, g, n_rays, Nc, gpre, HS(stream)),
+            "dfn_composite_coarse_train_backward_maps");
+  return DFN_OK;
+}
+
+extern "C" int dfn_composite_fine_train_backward_maps(const float* raw, const float* z, size_t n_rays, int Nf,
+                                                      const dfn_train_map_grads* grads, float g_tsigma, const float* grad_raw_ext,
+                                                      float* gpre, void* stream) {
+  if (!n_rays) return DFN_OK;
+  if (!raw || !z || !gpre || Nf < 1 || Nf > 512)
+    return set_error(DFN_ERR_ARG, "dfn_composite_fine_train_backward_maps: bad argument (1 <= Nf <= 512)");
+  const TrainMapGrads g = map_grads_of(grads);
+  if (!g.any_fine() && !grad_raw_ext && g_tsigma == 0.f)
+    return set_error(DFN_ERR_ARG, "dfn_composite_fine_train_backward_maps: bad argument (none of rgb, disp, acc, depth, beta, no "
+                                  "grad_raw_ext and no g_tsigma is given)");
+  CHECK_HIP(composite_fine_backward_train_maps(raw, z, g, g_tsigma, grad_raw_ext, n_rays, Nf, gpre, HS(stream)),
+            "dfn_composite_fine_train_backward_maps");
+  return DFN_OK;
+}
+
+extern "C" int dfn_nerfh_train_depths(dfn_nerfh_t h, size_t n_rays, int Nc, int Ni, const float* raw, void* workspace,
+                                      size_t workspace_bytes, float* depth, float* depth0, void* stream) {
+  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_depths")) return rc;
+  if (!n_rays) return DFN_OK;
+  if (!raw || !workspace || (!depth && !depth0)) return set_error(DFN_ERR_ARG, "dfn_nerfh_train_depths: bad argument");
+  if (int rc = check_train_state(h, "dfn_nerfh_train_depths")) return rc;
+  const float *z_f = nullptr, *d0 = nullptr;
+  if (use_fused(h)) {
+    if (int rc = fused::train_depth_state(h, n_rays, Nc, Ni, workspace, workspace_bytes, &z_f, &d0)) return rc;
+  } else {
+    const TrainWs w = carve_train(static_cast<float*>(workspace), dims_of(h->desc), n_rays, Nc, Ni, true);
+    if (w.total > workspace_bytes)
+      return set_error(DFN_ERR_ARG, "dfn_nerfh_train_depths: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+    z_f = w.z_f;
+    d0 = w.depth0;
+  }
+  if (depth)   // rendering.py:241 with the joint weights: the `depth` map of the fine compositor
+    CHECK_HIP(launch_composite_fine_maps(raw, z_f, n_rays, Nc + Ni, 0.1f, MapPtrs{depth, nullptr, nullptr, nullptr, nullptr}, HS(stream)),
+              "dfn_nerfh_train_depths: fine depth");
+  if (depth0) CHECK_HIP(hipMemcpyAsync(depth0, d0, n_rays * sizeof(float), hipMemcpyDeviceToDevice, HS(stream)), "dfn_nerfh_train_depths: coarse depth");
+  return DFN_OK;
+}
 
 // The reference's training render is differentiable with respect to its rays as well (models/rendering.py:245-337 under autograd:
 // pts = o + d z enter both networks; z itself carries no gradient — near / far bounds, z_samples.detach()).  d L / d rays from the
@@ -447,24 +557,22 @@ extern "C" size_t dfn_nerfh_train_backward_rays_scratch_bytes(size_t n_rays, int
   const size_t Pf = (n_rays ? n_rays : 1) * (size_t(Nc) + Ni);
   return (al64(Pf * 64) + al64(Pf * 28) + al64(Pf * 6)) * sizeof(float);
 }
-extern "C" int dfn_nerfh_train_backward_rays(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
-                                             const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise,
-                                             float raw_noise_std, const float* raw, const float* g_rgb, const float* g_rgb0,
-                                             const float* g_beta, float g_tsigma, const float* g_tsigma_dense, float* grad_rays_o,
-                                             float* grad_rays_d, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
-                                             void* stream) {
-  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_backward_rays")) return rc;
-  if (!n_rays) return DFN_OK;
-  if (!params || !rays_o || !rays_d || !hist || !raw || !g_rgb || !g_rgb0 || !g_beta || !grad_rays_o || !grad_rays_d || !workspace || !scratch ||
+namespace {
+// dfn_nerfh_train_backward_rays and dfn_nerfh_train_backward_rays_maps: they differ in the compositing-backward stage alone (CompGrads)
+int train_backward_rays_impl(const char* fn, dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                             const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise, float raw_noise_std,
+                             const float* raw, const CompGrads& cg, float* grad_rays_o, float* grad_rays_d, void* workspace,
+                             size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!params || !rays_o || !rays_d || !hist || !raw || !grad_rays_o || !grad_rays_d || !workspace || !scratch ||
       (hist_rows != 1 && hist_rows != n_rays))
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward_rays: bad argument");
+    return set_error(DFN_ERR_ARG, "%s: bad argument", fn);
   if (!h->train_forward_exact)
-    return set_error(DFN_ERR_STATE, "dfn_nerfh_train_backward_rays: the last dfn_nerfh_train_forward of this handle ran the fused chain, which keeps no "
-                                    "activations: call dfn_nerfh_set_train_mode(h, DFN_TRAIN_EXACT) before the forward");
+    return set_error(DFN_ERR_STATE, "%s: the last dfn_nerfh_train_forward of this handle ran the fused chain, which keeps no "
+                                    "activations: call dfn_nerfh_set_train_mode(h, DFN_TRAIN_EXACT) before the forward", fn);
   const Dims m = dims_of(h->desc);
   const TrainWs w = carve_train(static_cast<float*>(workspace), m, n_rays, Nc, Ni, true);
   if (w.total > workspace_bytes || dfn_nerfh_train_backward_rays_scratch_bytes(n_rays, Nc, Ni) > scratch_bytes)
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward_rays: workspace / scratch too small");
+    return set_error(DFN_ERR_ARG, "%s: workspace / scratch too small", fn);
   hipStream_t s = HS(stream);
   const size_t R = n_rays;
   const int Nf = Nc + Ni;
@@ -472,8 +580,9 @@ extern "C" int dfn_nerfh_train_backward_rays(dfn_nerfh_t h, const float* const* 
   float* g_pe = static_cast<float*>(scratch);
   float* g_dpe = g_pe + al64(Pf * 64);
   float* gpts = g_dpe + al64(Pf * 28);
-  CHECK_HIP(composite_fine_backward_train(raw, w.z_f, g_rgb, g_beta, g_tsigma, g_tsigma_dense, R, Nf, w.gpre_f, s), "train backward (rays): fine composite");
-  CHECK_HIP(composite_coarse_backward(w.raw_c, w.z_c, noise, raw_noise_std, g_rgb0, R, Nc, w.gpre_c, s), "train backward (rays): coarse composite");
+  if (int rc = composite_backward("train backward (rays): composite", cg, raw, w.z_f, w.raw_c, w.z_c, noise, raw_noise_std, R, Nc, Nf,
+                                  w.gpre_f, w.gpre_c, s))
+    return rc;
   BwdBufs gf{w.gpre_f, w.gA, w.gB, w.gfin, w.gt0, w.gt1, w.gsum, w.gray, w.wscratch};
   BwdBufs gc{w.gpre_c, w.gA_c, w.gB_c, w.gfin_c, w.gt0_c, nullptr, w.gsum_c, w.gray_c, w.wscratch_c};
   if (int rc = net_backward(net_of(params, nullptr, true), m, bufs_of(w, m, true, const_cast<float*>(raw), R, Nc, Ni), gf, true, hist, hist_rows,
@@ -487,6 +596,36 @@ extern "C" int dfn_nerfh_train_backward_rays(dfn_nerfh_t h, const float* const* 
   CHECK_HIP(posenc_backward(rays_o, rays_d, w.view, w.z_c, g_pe, g_dpe, 28, R, Nc, gpts, s), "train backward (rays): coarse encodings");
   CHECK_HIP(launch_ray_grad_reduce(gpts, w.z_c, rays_d, R, Nc, 1, grad_rays_o, grad_rays_d, nullptr, s, 1), "train backward (rays): coarse reduction");
   return DFN_OK;
+}
+}  // namespace
+
+extern "C" int dfn_nerfh_train_backward_rays(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                                             const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise,
+                                             float raw_noise_std, const float* raw, const float* g_rgb, const float* g_rgb0,
+                                             const float* g_beta, float g_tsigma, const float* g_tsigma_dense, float* grad_rays_o,
+                                             float* grad_rays_d, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                                             void* stream) {
+  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_backward_rays")) return rc;
+  if (!n_rays) return DFN_OK;
+  if (!g_rgb || !g_rgb0 || !g_beta) return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward_rays: bad argument");
+  return train_backward_rays_impl("dfn_nerfh_train_backward_rays", h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni, noise,
+                                  raw_noise_std, raw, CompGrads{g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense, nullptr, nullptr},
+                                  grad_rays_o, grad_rays_d, workspace, workspace_bytes, scratch, scratch_bytes, stream);
+}
+
+extern "C" int dfn_nerfh_train_backward_rays_maps(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                                                  const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise,
+                                                  float raw_noise_std, const float* raw, const dfn_train_map_grads* grads, float g_tsigma,
+                                                  const float* grad_raw_ext, float* grad_rays_o, float* grad_rays_d, void* workspace,
+                                                  size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_backward_rays_maps")) return rc;
+  if (!n_rays) return DFN_OK;
+  const TrainMapGrads g = map_grads_of(grads);
+  if (!g.any_fine() && !g.any_coarse() && !grad_raw_ext && g_tsigma == 0.f)
+    return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward_rays_maps: bad argument (no upstream gradient, no grad_raw_ext and no g_tsigma)");
+  return train_backward_rays_impl("dfn_nerfh_train_backward_rays_maps", h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni, noise,
+                                  raw_noise_std, raw, CompGrads{nullptr, nullptr, nullptr, g_tsigma, nullptr, &g, grad_raw_ext},
+                                  grad_rays_o, grad_rays_d, workspace, workspace_bytes, scratch, scratch_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------ generic-width test-time render

@@ -966,6 +966,47 @@ def composite_fine_backward_maps(raw, z, grads, beta_min=0.1, grad_raw=None):
     return graw
 
 
+TRAIN_GRAD_NAMES = tuple(n for n, _ in _lib.TrainMapGrads._fields_)   # rgb, disp, acc, depth, beta, rgb0, disp0, acc0, depth0
+
+
+def train_map_grads(grads, n):
+    """({name: contiguous fp32 tensor [n] / [n,3]} of the non-None entries of `grads`, kept alive by the caller; the dfn_train_map_grads
+    struct pointing at them): the upstream gradients of the outputs of the training render, a missing name or None = zero."""
+    grads = grads or {}
+    unknown = [k for k in grads if k not in TRAIN_GRAD_NAMES]
+    if unknown:
+        raise ValueError(f"unknown upstream gradient(s) {unknown}: the outputs of the training render are {list(TRAIN_GRAD_NAMES)}")
+    held = {k: _f32c(t).reshape((n, 3) if k.startswith("rgb") else (n,)) for k, t in grads.items() if t is not None}
+    return held, _lib.TrainMapGrads(**{k: t.data_ptr() for k, t in held.items()})
+
+
+def composite_coarse_train_backward_maps(raw_c, z_c, grads, noise=None, noise_std=0.):
+    """d L/d (pre-activation coarse outputs) [n,Nc,4] through the coarse pass of the training render (models/rendering.py:161-193,231-243)
+    from grads = {name: tensor} over rgb0 [n,3] and disp0, acc0, depth0 [n] (dfn_composite_coarse_train_backward_maps)."""
+    raw_c, z_c = _f32c(raw_c), _f32c(z_c)
+    n, Nc = z_c.shape
+    held, st = train_map_grads(grads, n)
+    noise = None if noise is None else _f32c(noise).reshape(n, Nc)
+    gpre = torch.empty(n, Nc, 4, device=raw_c.device)
+    check(_lib.load().dfn_composite_coarse_train_backward_maps(ptr(raw_c), ptr(z_c), ptr(noise), float(noise_std), n, Nc, ctypes.byref(st),
+                                                               ptr(gpre), current_stream()), "dfn_composite_coarse_train_backward_maps")
+    return gpre
+
+
+def composite_fine_train_backward_maps(raw, z, grads, g_tsigma=0., grad_raw=None):
+    """d L/d (pre-activation fine outputs) [n,Nf,9] through the training compositor (models/rendering.py:168-209,241-242 with
+    test_time=False) from grads = {name: tensor} over rgb [n,3] and disp, acc, depth, beta [n], the constant d L/d transient_sigma and
+    grad_raw [n,Nf,9], a gradient that reaches raw directly (dfn_composite_fine_train_backward_maps)."""
+    raw, z = _f32c(raw), _f32c(z)
+    n, Nf = z.shape
+    held, st = train_map_grads(grads, n)
+    grad_raw = None if grad_raw is None else _f32c(grad_raw).reshape(n, Nf, 9)
+    gpre = torch.empty(n, Nf, 9, device=raw.device)
+    check(_lib.load().dfn_composite_fine_train_backward_maps(ptr(raw), ptr(z), n, Nf, ctypes.byref(st), float(g_tsigma), ptr(grad_raw),
+                                                             ptr(gpre), current_stream()), "dfn_composite_fine_train_backward_maps")
+    return gpre
+
+
 def frame_prep(rgb_u8, H, W, hist_bins=10):
     """Dataset front-end of one frame on the device (dfn_frame_prep; seven_scenes.py:324-352): rgb_u8 CUDA uint8
     [h, w, 3] -> (img fp32 [3, H, W] in [0, 1], INTER_AREA-downscaled; hist fp32 [hist_bins], NeRF-H's histogram index

@@ -10,7 +10,9 @@ validation render is asked for (`HipQuery.refresh`).
 Two equivalent surfaces:
   * NerfHTrainer.train_step(...)  — forward + fused NerfWLoss + backward, three library calls (run_nerf.py uses this);
   * rendering.render(..., **render_kwargs_train) — returns tensors attached to autograd (`_RenderTrainFn`), so the
-    reference's own loop shape (loss_func(results, target); loss.backward()) runs unchanged.
+    reference's own loop shape (loss_func(results, target); loss.backward()) runs unchanged.  With diff_maps=True
+    (`_RenderTrainMapsFn`) EVERY output is attached, as in the reference — disp_map, acc_map, raw, disp0, acc0 and the two depths
+    of rendering.py:241 — through dfn_nerfh_train_backward_maps: a depth, disparity or opacity term is the caller's torch code.
 The reference's random draws (stratified jitter, coarse-density noise, importance-sampling u) are drawn with torch on
 the device and handed to the library as inputs, which is what makes the path checkable against the reference.
 """
@@ -21,10 +23,28 @@ import torch
 
 from . import _lib
 from ._lib import check, current_stream, ptr
+from .engine import TRAIN_GRAD_NAMES, train_map_grads
 
 
 def _f32c(t):
     return t.contiguous().float()
+
+
+TRAIN_MAP_NAMES = ("depth", "depth0")   # what ret_maps may name in training mode (rendering.py:241, fine and coarse pass)
+
+
+def train_map_names(maps):
+    """The maps a training-mode render(diff_maps=True, ret_maps=...) is asked for: True = both depths, False / None = none, or names."""
+    if maps is True:
+        return TRAIN_MAP_NAMES
+    if maps is False or maps is None:
+        return ()
+    maps = (maps,) if isinstance(maps, str) else tuple(maps)
+    unknown = [m for m in maps if m not in TRAIN_MAP_NAMES]
+    if unknown:
+        raise ValueError(f"render(): ret_maps {unknown} in training mode: the maps of the training render are {list(TRAIN_MAP_NAMES)} "
+                         "(depth_static, rgb_static and rgb_transient are test-time maps; beta is already an extra)")
+    return tuple(m for m in TRAIN_MAP_NAMES if m in maps)
 
 
 class NerfHTrainer:
@@ -97,9 +117,10 @@ class NerfHTrainer:
         exact fp32, activations kept: what backward_rays() needs)."""
         check(self.lib.dfn_nerfh_set_train_mode(self.engine.handle, 1 if exact else (2 if self.fused_split else 0)), "dfn_nerfh_set_train_mode")
 
-    def forward(self, rays_o, rays_d, hist, Nc, Ni, near, far, t_rand=None, noise=None, raw_noise_std=0., u=None, exact=None):
+    def forward(self, rays_o, rays_d, hist, Nc, Ni, near, far, t_rand=None, noise=None, raw_noise_std=0., u=None, exact=None, maps=False):
         """Training-mode render_rays -> dict(rgb_map, disp_map, acc_map, raw, rgb0, disp0, acc0, z_std, beta,
-        transient_sigmas); keeps what backward() needs.  exact: force the layer-by-layer exact-fp32 step (None: `self.exact`)."""
+        transient_sigmas); keeps what backward() needs.  exact: force the layer-by-layer exact-fp32 step (None: `self.exact`).
+        maps: also depth and depth0 [n], the sums w z of rendering.py:241 in the fine and the coarse pass (dfn_nerfh_train_depths)."""
         exact = self.exact if exact is None else bool(exact)
         self.set_mode(exact)
         exact = exact or self.engine.width != 128    # what RAN: only netwidth 128 has the fused chains, any other width is the exact step
@@ -122,6 +143,10 @@ class NerfHTrainer:
                                                ptr(out["beta"]), ctypes.c_void_p(ws.data_ptr()), ws.numel(), current_stream()),
               "dfn_nerfh_train_forward")
         out["transient_sigmas"] = out["raw"][..., 7]
+        if maps:
+            out["depth"], out["depth0"] = torch.empty(n, device=dev), torch.empty(n, device=dev)
+            check(self.lib.dfn_nerfh_train_depths(self.engine.handle, n, Nc, Ni, ptr(out["raw"]), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                                  ptr(out["depth"]), ptr(out["depth0"]), current_stream()), "dfn_nerfh_train_depths")
         self._saved = dict(hist=hist, n=n, Nc=Nc, Ni=Ni, noise=noise, raw_noise_std=float(raw_noise_std), raw=out["raw"], ws=ws, exact=exact,
                            rays_o=rays_o, rays_d=rays_d)
         return out
@@ -140,9 +165,21 @@ class NerfHTrainer:
               "dfn_nerfw_loss")
         return loss5, (g_rgb, g_rgb0, g_beta), float(coef) * float(lambda_u) / (n * Nf)
 
-    def backward(self, g_rgb, g_rgb0, g_beta, g_tsigma=0., g_tsigma_dense=None, grads=None, saved=None):
+    def _map_operands(self, s, g_rgb, g_rgb0, g_beta, g_tsigma_dense, g_maps, g_raw):
+        """(held tensors, dfn_train_map_grads struct, grad_raw_ext) of a backward(g_maps=..., g_raw=...) call."""
+        if g_rgb is not None or g_rgb0 is not None or g_beta is not None or g_tsigma_dense is not None:
+            raise ValueError("g_maps / g_raw stand in the place of g_rgb, g_rgb0, g_beta and g_tsigma_dense (a gradient given twice): name them "
+                             "in g_maps (rgb, rgb0, beta) and put a dense transient_sigma gradient into channel 7 of g_raw")
+        held, st = train_map_grads(g_maps, s["n"])
+        ext = None if g_raw is None else _f32c(g_raw).reshape(s["n"], s["Nc"] + s["Ni"], 9)
+        return held, st, ext
+
+    def backward(self, g_rgb=None, g_rgb0=None, g_beta=None, g_tsigma=0., g_tsigma_dense=None, grads=None, saved=None, g_maps=None, g_raw=None):
         """Gradients of every parameter from the last forward() (or from `saved`, the state an autograd node took from its own
-        forward).  grads=None: written into (freshly allocated) p.grad."""
+        forward).  grads=None: written into (freshly allocated) p.grad.
+        g_maps = {name: d L / d output} over rgb, disp, acc, depth, beta, rgb0, disp0, acc0, depth0 (a missing name or None: zero) and / or
+        g_raw [n, Nf, 9] = a gradient that reaches `raw` directly: the upstream gradients of EVERY output of the training render
+        (dfn_nerfh_train_backward_maps), in the place of g_rgb, g_rgb0, g_beta and g_tsigma_dense.  Given neither, dfn_nerfh_train_backward."""
         s = self._saved if saved is None else saved
         if s is None:
             raise RuntimeError("NerfHTrainer.backward() without a forward()")
@@ -151,6 +188,15 @@ class NerfHTrainer:
                 if p.grad is None or not p.grad.is_contiguous():
                     p.grad = torch.empty_like(p)
             grads = [p.grad for p in self.params]
+        if g_maps is not None or g_raw is not None:
+            held, st, ext = self._map_operands(s, g_rgb, g_rgb0, g_beta, g_tsigma_dense, g_maps, g_raw)
+            self.set_mode(s["exact"])
+            check(self.lib.dfn_nerfh_train_backward_maps(self.engine.handle, self._ptr_array(self.params), ptr(s["hist"]), s["hist"].shape[0],
+                                                         s["n"], s["Nc"], s["Ni"], ptr(s["noise"]), s["raw_noise_std"], ptr(s["raw"]),
+                                                         ctypes.byref(st), float(g_tsigma), ptr(ext), self._ptr_array(grads),
+                                                         ctypes.c_void_p(s["ws"].data_ptr()), s["ws"].numel(), current_stream()),
+                  "dfn_nerfh_train_backward_maps")
+            return grads
         g_rgb, g_rgb0, g_beta = _f32c(g_rgb).reshape(-1, 3), _f32c(g_rgb0).reshape(-1, 3), _f32c(g_beta).reshape(-1)
         gd = None if g_tsigma_dense is None else _f32c(g_tsigma_dense).reshape(s["n"], s["Nc"] + s["Ni"])
         self.set_mode(s["exact"])   # the workspace was laid out by the forward's implementation
@@ -161,18 +207,28 @@ class NerfHTrainer:
               "dfn_nerfh_train_backward")
         return grads
 
-    def backward_rays(self, g_rgb, g_rgb0, g_beta, g_tsigma=0., g_tsigma_dense=None, saved=None):
+    def backward_rays(self, g_rgb=None, g_rgb0=None, g_beta=None, g_tsigma=0., g_tsigma_dense=None, saved=None, g_maps=None, g_raw=None):
         """(d L / d rays_o, d L / d rays_d) [n,3] of the last forward(exact=True): the reference's training render is differentiable
-        w.r.t. its rays under autograd (rendering.py:245-337); both networks contribute."""
+        w.r.t. its rays under autograd (rendering.py:245-337); both networks contribute.  g_maps / g_raw as in backward()
+        (dfn_nerfh_train_backward_rays_maps)."""
         s = self._saved if saved is None else saved
         if s is None or not s["exact"]:
             raise RuntimeError("NerfHTrainer.backward_rays() needs a forward(exact=True): the fused chain keeps no activations")
-        g_rgb, g_rgb0, g_beta = _f32c(g_rgb).reshape(-1, 3), _f32c(g_rgb0).reshape(-1, 3), _f32c(g_beta).reshape(-1)
-        gd = None if g_tsigma_dense is None else _f32c(g_tsigma_dense).reshape(s["n"], s["Nc"] + s["Ni"])
         dev = s["raw"].device
         go, gdir = torch.empty(s["n"], 3, device=dev), torch.empty(s["n"], 3, device=dev)
         nb = self.lib.dfn_nerfh_train_backward_rays_scratch_bytes(s["n"], s["Nc"], s["Ni"])
         scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+        if g_maps is not None or g_raw is not None:
+            held, st, ext = self._map_operands(s, g_rgb, g_rgb0, g_beta, g_tsigma_dense, g_maps, g_raw)
+            check(self.lib.dfn_nerfh_train_backward_rays_maps(self.engine.handle, self._ptr_array(self.params), ptr(s["rays_o"]), ptr(s["rays_d"]),
+                                                              ptr(s["hist"]), s["hist"].shape[0], s["n"], s["Nc"], s["Ni"], ptr(s["noise"]),
+                                                              s["raw_noise_std"], ptr(s["raw"]), ctypes.byref(st), float(g_tsigma), ptr(ext),
+                                                              ptr(go), ptr(gdir), ctypes.c_void_p(s["ws"].data_ptr()), s["ws"].numel(),
+                                                              ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), current_stream()),
+                  "dfn_nerfh_train_backward_rays_maps")
+            return go, gdir
+        g_rgb, g_rgb0, g_beta = _f32c(g_rgb).reshape(-1, 3), _f32c(g_rgb0).reshape(-1, 3), _f32c(g_beta).reshape(-1)
+        gd = None if g_tsigma_dense is None else _f32c(g_tsigma_dense).reshape(s["n"], s["Nc"] + s["Ni"])
         check(self.lib.dfn_nerfh_train_backward_rays(self.engine.handle, self._ptr_array(self.params), ptr(s["rays_o"]), ptr(s["rays_d"]),
                                                      ptr(s["hist"]), s["hist"].shape[0], s["n"], s["Nc"], s["Ni"], ptr(s["noise"]),
                                                      s["raw_noise_std"], ptr(s["raw"]), ptr(g_rgb), ptr(g_rgb0), ptr(g_beta), float(g_tsigma), ptr(gd),
@@ -320,25 +376,80 @@ class _RenderTrainFn(torch.autograd.Function):
             g_o, g_d = tr.backward_rays(*gs, 0., g_ts, saved=ctx.saved)
         if any(ctx.needs_input_grad[12:]):
             tr.backward(*gs, 0., g_ts, grads=grads, saved=ctx.saved)
-            if not ctx.saved["exact"] and tr.range_check == "skip":
-                tr._post_flag_read(dev)           # found out without a drain, acted on by the next train_step / flush_range_check
-            elif not ctx.saved["exact"] and tr.range_check:
-                flags = tr.engine.range_flags()   # an autograd node cannot repeat its forward: fail loudly instead of clamped gradients
-                if flags:
-                    raise _lib.DfnError(f"render(): the fused training step left the split-f16 operand range (flags {flags:#x}); call "
-                                        "trainer.recommit() (weights outgrew the committed scale) or set trainer.exact = True")
+            _after_node_backward(tr, ctx.saved, dev)
         else:
             grads = [None] * len(tr.params)
         return (None, g_o if ctx.needs_input_grad[1] else None, g_d if ctx.needs_input_grad[2] else None) + (None,) * 9 + tuple(grads)
 
 
-def render_train(trainer, rays_o, rays_d, hist, Nc, Ni, near, far, perturb, raw_noise_std, retraw, draws=None):
-    """The training branch of rendering.render(): [rgb, disp, acc, extras] with the reference's extras keys."""
+def _after_node_backward(tr, saved, dev):
+    """What an autograd node does about the range flag of a fused step's backward."""
+    if not saved["exact"] and tr.range_check == "skip":
+        tr._post_flag_read(dev)           # found out without a drain, acted on by the next train_step / flush_range_check
+    elif not saved["exact"] and tr.range_check:
+        flags = tr.engine.range_flags()   # an autograd node cannot repeat its forward: fail loudly instead of clamped gradients
+        if flags:
+            raise _lib.DfnError(f"render(): the fused training step left the split-f16 operand range (flags {flags:#x}); call "
+                                "trainer.recommit() (weights outgrew the committed scale) or set trainer.exact = True")
+
+
+class _RenderTrainMapsFn(torch.autograd.Function):
+    """render_rays in training mode with EVERY output attached (render(test_time=False, diff_maps=True)): outputs (rgb, disp, acc, raw,
+    rgb0, disp0, acc0, z_std, beta, transient_sigmas, depth, depth0); all but z_std (a function of the detached z_samples,
+    rendering.py:302,327) are differentiable, as the reference's are (rendering.py:161-243, :295-331).  An output the loss does not use
+    arrives as None = a NULL upstream pointer.  Forward values are the bits of _RenderTrainFn's."""
+
+    NAMES = ("rgb", "disp", "acc", None, "rgb0", "disp0", "acc0", None, "beta", None, "depth", "depth0")   # outputs -> dfn_train_map_grads
+
+    @staticmethod
+    def forward(ctx, trainer, rays_o, rays_d, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, *params):
+        ctx.want_rays = bool(ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        out = trainer.forward(rays_o, rays_d, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, exact=True if ctx.want_rays else None,
+                              maps=True)
+        ctx.trainer = trainer
+        ctx.saved = trainer._saved
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(out["z_std"])
+        # the caller's raw is a copy: an in-place edit of it must not reach the state the backward reads
+        return (out["rgb_map"], out["disp_map"], out["acc_map"], out["raw"].clone(), out["rgb0"], out["disp0"], out["acc0"], out["z_std"],
+                out["beta"], out["transient_sigmas"].contiguous(), out["depth"], out["depth0"])
+
+    @staticmethod
+    def backward(ctx, *gs):
+        tr = ctx.trainer
+        if tr._saved is not ctx.saved:
+            raise RuntimeError("render(): backward through a training render after another forward reused its workspace")
+        s = ctx.saved
+        n, dev = s["n"], s["raw"].device
+        g_maps = {k: g for k, g in zip(_RenderTrainMapsFn.NAMES, gs) if k is not None and g is not None}
+        g_raw, g_ts = gs[3], gs[9]
+        if g_ts is not None:   # transient_sigmas = raw[..., 7]
+            g_raw = torch.zeros(n, s["Nc"] + s["Ni"], 9, device=dev) if g_raw is None else g_raw.clone()
+            g_raw[..., 7] += g_ts
+        if not g_maps and g_raw is None:
+            g_maps = dict(rgb=torch.zeros(n, 3, device=dev))
+        g_o = g_d = None
+        if ctx.want_rays:   # before the weight gradients: they reuse the gradient buffers of the workspace
+            g_o, g_d = tr.backward_rays(g_maps=g_maps, g_raw=g_raw, saved=s)
+        if any(ctx.needs_input_grad[12:]):
+            grads = [torch.empty_like(p) for p in tr.params]
+            tr.backward(g_maps=g_maps, g_raw=g_raw, grads=grads, saved=s)
+            _after_node_backward(tr, s, dev)
+        else:
+            grads = [None] * len(tr.params)
+        return (None, g_o if ctx.needs_input_grad[1] else None, g_d if ctx.needs_input_grad[2] else None) + (None,) * 9 + tuple(grads)
+
+
+def render_train(trainer, rays_o, rays_d, hist, Nc, Ni, near, far, perturb, raw_noise_std, retraw, draws=None, diff_maps=False, maps=()):
+    """The training branch of rendering.render(): [rgb, disp, acc, extras] with the reference's extras keys.  diff_maps: every output
+    attached (_RenderTrainMapsFn), and the depths named by `maps` (out of depth, depth0) among the extras."""
     n = rays_o.reshape(-1, 3).shape[0]
     t_rand, noise, u = draws if draws is not None else NerfHTrainer.draw(n, Nc, Ni, float(perturb), rays_o.device)
-    (rgb, disp, acc, raw, rgb0, disp0, acc0, z_std, beta, ts) = _RenderTrainFn.apply(
+    fn = _RenderTrainMapsFn if diff_maps else _RenderTrainFn
+    (rgb, disp, acc, raw, rgb0, disp0, acc0, z_std, beta, ts, *depths) = fn.apply(
         trainer, rays_o, rays_d, hist, int(Nc), int(Ni), float(near), float(far), t_rand, noise, float(raw_noise_std), u, *trainer.params)
     extras = {'rgb0': rgb0, 'disp0': disp0, 'acc0': acc0, 'z_std': z_std, 'transient_sigmas': ts, 'beta': beta}
     if retraw:
         extras['raw'] = raw
+    extras.update({k: v for k, v in zip(TRAIN_MAP_NAMES, depths) if k in maps})
     return [rgb, disp, acc, extras]

@@ -245,10 +245,9 @@ def _check_test_time(kw, ndc, c2w_staticcam, use_viewdirs, training=False, track
                         "compositor as output_transient (models/rendering.py:295) and fails the same way")
     if (ndc or c2w_staticcam is not None) and (training or tracked):
         bad.append("ndc / c2w_staticcam together with " + ("training-mode rendering" if training else "autograd"))
-    if diff_maps and training:
-        bad.append("diff_maps together with training-mode rendering")
-    if ret_maps and (training or tracked) and not (diff_maps and not training):
-        bad.append("ret_maps together with " + ("training-mode rendering" if training else "autograd (the maps are not differentiable)"))
+    if ret_maps and (training or tracked) and not diff_maps:
+        bad.append("ret_maps together with " + ("training-mode rendering without diff_maps" if training else
+                                                "autograd (the maps are not differentiable)"))
     if not training:
         if not kw.get('test_time', False):
             bad.append("test_time=False without a trainer (render kwargs must come from create_nerf with gradient updates enabled)")
@@ -278,6 +277,11 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     rgb_static, rgb_transient — the maps raw2outputs_NeRFW forms and the reference drops (rendering.py:196-241) are added to
     `extras` under those names, shaped like the rays ([H,W] / [H,W,3] for c2w).
 
+    Training mode (test_time=False) with diff_maps=True: disp_map, acc_map, disp0, acc0 (and raw with retraw) come back attached as well, as the
+    reference's are (rendering.py:161-243, :295-331; z_std stays detached, rendering.py:302), and ret_maps names depth / depth0 (True:
+    both), the sums w z of rendering.py:241 in the fine and the coarse pass, attached too.  Without diff_maps the training render is
+    what it was: gradients through rgb, rgb0, beta and transient_sigmas, ret_maps refused.
+
     diff_maps (opt-in, test time): under autograd (rays or c2w requiring grad) disp_map, acc_map and the maps of ret_maps come back attached
     to the graph as well, as the reference's are (they are torch expressions of raw, rendering.py:161-243).  False: as ever, disp_map and
     acc_map detached and ret_maps refused under autograd.  Without autograd it changes nothing.
@@ -288,9 +292,12 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     eng = _engine_of(kwargs)
     _set_options(eng, kwargs, near)
     from .engine import map_names
-    map_list = map_names(ret_maps)
     trainer = getattr(kwargs.get('network_query_fn'), 'trainer', None)
-    if not kwargs.get('test_time', False) and trainer is not None:
+    training = not kwargs.get('test_time', False) and trainer is not None
+    if training and diff_maps:
+        from .nerf_train import train_map_names as map_names   # depth, depth0: what the training render forms at rendering.py:241
+    map_list = map_names(ret_maps)
+    if training:
         # training mode (rendering.py:245-337 with test_time=False): stratified depths, coarse rgb + noise, importance sampling
         # with random u, the training extras — on the exact-fp32 training kernels, attached to autograd (nerf_train.py)
         _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, training=True, ret_maps=bool(map_list), diff_maps=bool(diff_maps))
@@ -314,7 +321,7 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         rgb, disp, acc, extras = nerf_train.render_train(trainer, rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), hist, int(kwargs['N_samples']),
                                                          int(kwargs['N_importance']), near, far, float(kwargs.get('perturb', 0.) or 0.),
                                                          float(kwargs.get('raw_noise_std', 0.) or 0.), bool(kwargs.get('retraw', False)),
-                                                         draws=kwargs.get('draws'))
+                                                         draws=kwargs.get('draws'), diff_maps=bool(diff_maps), maps=map_list)
         # (no `stale` mark here: a render does not move the weights; HipQuery.refresh() sees optimizer steps through the tensors'
         #  version counters, and the training loop marks them itself)
         return _shaped(lead, rgb, disp, acc, extras)

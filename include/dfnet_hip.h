@@ -621,6 +621,64 @@ int dfn_nerfh_train_backward_rays(dfn_nerfh_t h, const float* const* params, con
                                   const float* g_tsigma_dense, float* grad_rays_o, float* grad_rays_d, void* workspace,
                                   size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- the training render with EVERY output attached (render(test_time=False, diff_maps=True))
+ * In the reference render(**render_kwargs_train) returns rgb_map, disp_map, acc_map, raw, rgb0, disp0, acc0, beta and transient_sigmas as
+ * torch expressions of the two networks' outputs (models/rendering.py:161-243, :295-331): a depth or disparity term, an opacity
+ * regulariser on acc / acc0 or any loss on raw reaches every parameter.  Upstream gradients of all of them, per ray:
+ *   rgb    [n,3]  sum T (a_s c_s + a_t c_t)            rendering.py:196-203   (joint transmittance T, a = 1 - exp(-delta (sigma_s + sigma_t)))
+ *   acc    [n]    sum a T                              rendering.py:185-186
+ *   depth  [n]    sum a T z                            rendering.py:241       (test_time=False: the joint weights)
+ *   disp   [n]    1 / max(1e-10, depth / acc)          rendering.py:242       (folded into depth and acc; zero where the clamp is active)
+ *   beta   [n]    sum a_t T beta + beta_min            rendering.py:204-208
+ *   rgb0   [n,3]  sum w c, w = alpha T, alpha = 1 - exp(-delta relu(sigma + noise std))   rendering.py:173-193 (coarse pass)
+ *   acc0   [n]    sum w                                rendering.py:185-186
+ *   depth0 [n]    sum w z                              rendering.py:241
+ *   disp0  [n]    1 / max(1e-10, depth0 / acc0)        rendering.py:242
+ * Every member is optional: NULL = a zero gradient (bit for bit what a tensor of zeros gives). */
+typedef struct {
+  const float *rgb, *disp, *acc, *depth, *beta, *rgb0, *disp0, *acc0, *depth0;
+} dfn_train_map_grads;
+
+/* raw2outputs_NeRFW backward, typ="coarse", test_time=False (rendering.py:161-193,231-243) for rgb0, disp0, acc0, depth0 of `grads`:
+ * raw_c [n,Nc,4] = (rgb, sigma), z_c [n,Nc], noise [n,Nc] (x noise_std, added to sigma before the relu; NULL = none) ->
+ * gpre [n,Nc,4] = d L / d (PRE-activation network outputs): x c (1 - c) on the colours, x (1 - exp(-sigma)) on sigma; exactly 0 where
+ * the relu gate is closed.  z carries no gradient.  No division by 1 - alpha: opaque samples give finite gradients.  Deterministic.
+ * 3 <= Nc <= 512.  DFN_ERR_ARG when none of the four is given; n_rays == 0 is DFN_OK. */
+int dfn_composite_coarse_train_backward_maps(const float* raw_c, const float* z_c, const float* noise, float noise_std, size_t n_rays,
+                                             int Nc, const dfn_train_map_grads* grads, float* gpre, void* stream);
+/* raw2outputs_NeRFW backward, typ="fine", test_time=False (rendering.py:168-209,241-242) for rgb, disp, acc, depth, beta of `grads`,
+ * the constant d L / d transient_sigma g_tsigma and grad_raw_ext [n,Nf,9] (optional: a gradient that reaches the post-activation raw
+ * directly, e.g. of a loss on `raw`; it generalises g_tsigma_dense of dfn_nerfh_train_backward): raw [n,Nf,9], z [n,Nf] ->
+ * gpre [n,Nf,9] = d L / d (PRE-activation network outputs).  1 <= Nf <= 512.  DFN_ERR_ARG when none of the five, no grad_raw_ext and
+ * g_tsigma == 0 are given; n_rays == 0 is DFN_OK.  dfn_nerfh_train_backward's own compositing kernels are not involved. */
+int dfn_composite_fine_train_backward_maps(const float* raw, const float* z, size_t n_rays, int Nf, const dfn_train_map_grads* grads,
+                                           float g_tsigma, const float* grad_raw_ext, float* gpre, void* stream);
+
+/* The two depths raw2outputs_NeRFW forms at rendering.py:241 in both passes of the training render and render_rays drops: depth [n] =
+ * sum a T z of the fine pass (from `raw`, dfn_nerfh_train_forward's output, and the fine depths in the workspace) and depth0 [n] =
+ * sum w z of the coarse pass (kept in the workspace by the forward).  Either may be NULL.  Must follow dfn_nerfh_train_forward on the
+ * same workspace; every train mode (DFN_ERR_STATE after a mode switch). */
+int dfn_nerfh_train_depths(dfn_nerfh_t h, size_t n_rays, int Nc, int Ni, const float* raw, void* workspace, size_t workspace_bytes,
+                           float* depth, float* depth0, void* stream);
+
+/* dfn_nerfh_train_backward (run_nerf.py:65, loss.backward()) from the upstream gradients of EVERY output of the training render
+ * (rendering.py:161-243, :295-331 under autograd): `grads` (dfn_train_map_grads), the constant g_tsigma and grad_raw_ext [n,Nc+Ni,9] in
+ * the place of g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense.  The compositing backward is the pair of kernels behind
+ * dfn_composite_{coarse,fine}_train_backward_maps; everything after it (data-gradient chains, weight-gradient stream, embedding
+ * scatter) is dfn_nerfh_train_backward's, in all three train modes.  Same state rules (DFN_ERR_STATE after a mode switch); DFN_ERR_ARG
+ * when no gradient at all is given. */
+int dfn_nerfh_train_backward_maps(dfn_nerfh_t h, const float* const* params, const float* hist, size_t hist_rows, size_t n_rays,
+                                  int Nc, int Ni, const float* noise, float raw_noise_std, const float* raw,
+                                  const dfn_train_map_grads* grads, float g_tsigma, const float* grad_raw_ext, float* const* grads_out,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+/* dfn_nerfh_train_backward_rays from the same upstream gradients (rendering.py:245-337 under autograd: the depths, disparities and
+ * opacities of both passes are functions of the rays through pts = o + d z as well).  Needs a DFN_TRAIN_EXACT forward, as that entry. */
+int dfn_nerfh_train_backward_rays_maps(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                                       const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise,
+                                       float raw_noise_std, const float* raw, const dfn_train_map_grads* grads, float g_tsigma,
+                                       const float* grad_raw_ext, float* grad_rays_o, float* grad_rays_d, void* workspace,
+                                       size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Test-time render_rays for ANY netwidth on the same layer-by-layer exact-fp32 path (the register-resident kernels
  * behind dfn_render_rays exist for netwidth 128 and 256): models/rendering.py:245-337 with test_time=True, from
  * the handle's committed parameters.  raw [n_rays, Nc+Ni, 9] is required (output and scratch). */
