@@ -614,14 +614,13 @@ int train_depth_state(dfn_nerfh_s* h, size_t R, int Nc, int Ni, void* workspace,
   return DFN_OK;
 }
 
-int train_backward(dfn_nerfh_s* h, const float* const* params, const float* hist, size_t hist_rows, size_t R, int Nc, int Ni,
-                   const float* noise, float raw_noise_std, const float* raw, const float* g_rgb, const float* g_rgb0, const float* g_beta,
-                   float g_tsigma, const float* g_tsigma_dense, float* const* grads, void* workspace, size_t workspace_bytes_, hipStream_t s,
-                   const train::TrainMapGrads* maps, const float* raw_ext) {
-  if (!h->fused) return set_error(DFN_ERR_STATE, "dfn_nerfh_train_backward: no forward pass on this handle");
+int train_backward(const char* fn, dfn_nerfh_s* h, const float* const* params, const float* hist, size_t hist_rows, size_t R, int Nc, int Ni,
+                   const float* noise, float raw_noise_std, const float* raw, const train::CompGrads& cg, float* const* grads, void* workspace,
+                   size_t workspace_bytes_, hipStream_t s) {
+  if (!h->fused) return set_error(DFN_ERR_STATE, "%s: no forward pass on this handle", fn);
   const State& st = *static_cast<State*>(h->fused);
   const Ws w = carve(static_cast<char*>(workspace), h->desc, R, Nc, Ni, h->train_split_fine);
-  if (w.total > workspace_bytes_) return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward: workspace too small (%zu < %zu)", workspace_bytes_, w.total);
+  if (w.total > workspace_bytes_) return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes_, w.total);
   const Geo g = geo_of(h->desc);
   const dfn_nerfh_desc& d = h->desc;
   const int Nf = Nc + Ni, W = kWidth, W2 = kWidth / 2;
@@ -632,18 +631,10 @@ int train_backward(dfn_nerfh_s* h, const float* const* params, const float* hist
   float* g_emb_a = grads[kCoarseParams + kFineParams];
   float* g_emb_t = grads[kCoarseParams + kFineParams + 1];
   const int n_cu = device_cu_count();
-  if (maps) {   // every output's upstream gradient (nerfh_train_maps.hip); the embedding gradients are zeroed by two memsets here
-    CHECK_HIP(hipMemsetAsync(g_emb_a, 0, size_t(d.n_vocab) * d.dim_a * sizeof(float), s), "train backward: zero embedding_a grad");
-    CHECK_HIP(hipMemsetAsync(g_emb_t, 0, size_t(d.n_vocab) * d.dim_t * sizeof(float), s), "train backward: zero embedding_t grad");
-    CHECK_HIP(composite_fine_backward_train_maps(raw, w.net[1].z, *maps, g_tsigma, raw_ext, R, Nf, w.net[1].gpre, s), "train backward: fine composite (maps)");
-    CHECK_HIP(composite_coarse_backward_maps(w.raw_c, w.net[0].z, noise, raw_noise_std, *maps, R, Nc, w.net[0].gpre, s), "train backward: coarse composite (maps)");
-  } else {
-  CHECK_HIP(composite_fine_backward_train(raw, w.net[1].z, g_rgb, g_beta, g_tsigma, g_tsigma_dense, R, Nf, w.net[1].gpre, s), "train backward: fine composite");
-  // (the coarse compositor also zeroes the two embedding gradients that the scatter kernels at the end of the pass accumulate into)
-  CHECK_HIP(composite_coarse_backward(w.raw_c, w.net[0].z, noise, raw_noise_std, g_rgb0, R, Nc, w.net[0].gpre, s, g_emb_a,
-                                      size_t(d.n_vocab) * d.dim_a, g_emb_t, size_t(d.n_vocab) * d.dim_t),
-            "train backward: coarse composite");
-  }
+  // (the stage also zeroes the two embedding gradients that the scatter kernels at the end of the pass accumulate into)
+  if (int rc = composite_backward("train backward: composite", cg, raw, w.net[1].z, w.raw_c, w.net[0].z, noise, raw_noise_std, R, Nc, Nf,
+                                  w.net[1].gpre, w.net[0].gpre, s, g_emb_a, size_t(d.n_vocab) * d.dim_a, g_emb_t, size_t(d.n_vocab) * d.dim_t))
+    return rc;
   // data-gradient chains: every pre-activation gradient stored once, in the operand layout the weight-gradient stream reads
   // (the two networks' chains are independent — the coarse loss alone reaches the coarse network, rendering.py:302 detaches the
   // samples — and run as the two halves of ONE grid, the coarse chain's workgroups starting on the CUs the fine chain leaves first:

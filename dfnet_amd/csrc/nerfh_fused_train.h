@@ -32,7 +32,7 @@ struct dfn_nerfh_s;
 
 namespace dfn {
 namespace train {
-struct TrainMapGrads;   // nerfh_train.h
+struct CompGrads;   // nerfh_train.h
 }
 }
 
@@ -170,12 +170,11 @@ int train_forward(dfn_nerfh_s* h, const float* const* params, const float* rays_
                   size_t n_rays, int Nc, int Ni, float near, float far, const float* t_rand, const float* noise, float raw_noise_std,
                   const float* u, float* rgb, float* disp, float* acc, float* raw, float* rgb0, float* disp0, float* acc0, float* z_std,
                   float* beta, void* workspace, size_t workspace_bytes, hipStream_t s);
-int train_backward(dfn_nerfh_s* h, const float* const* params, const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni,
-                   const float* noise, float raw_noise_std, const float* raw, const float* g_rgb, const float* g_rgb0, const float* g_beta,
-                   float g_tsigma, const float* g_tsigma_dense, float* const* grads, void* workspace, size_t workspace_bytes, hipStream_t s,
-                   const train::TrainMapGrads* maps = nullptr, const float* raw_ext = nullptr);
-// maps != nullptr (dfn_nerfh_train_backward_maps): the compositing backward is nerfh_train_maps.hip's pair of kernels, from the upstream
-// gradients of every output (g_rgb / g_rgb0 / g_beta / g_tsigma_dense unused) + raw_ext; everything after it is the same.
+// fn: the calling entry's name (messages); cg: what the compositing-backward stage starts from (train::composite_backward) — everything
+// after that stage is the same for dfn_nerfh_train_backward and dfn_nerfh_train_backward_maps.
+int train_backward(const char* fn, dfn_nerfh_s* h, const float* const* params, const float* hist, size_t hist_rows, size_t n_rays, int Nc,
+                   int Ni, const float* noise, float raw_noise_std, const float* raw, const train::CompGrads& cg, float* const* grads,
+                   void* workspace, size_t workspace_bytes, hipStream_t s);
 // Where the forward left the fine depths and the coarse depth sum w z in its workspace (dfn_nerfh_train_depths).
 int train_depth_state(dfn_nerfh_s* h, size_t n_rays, int Nc, int Ni, void* workspace, size_t workspace_bytes, const float** z_fine,
                       const float** depth0);

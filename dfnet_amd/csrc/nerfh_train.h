@@ -97,6 +97,22 @@ hipError_t composite_coarse_backward_maps(const float* raw_c, const float* z_c, 
 // acc)), the constant d L / d transient_sigma and gext [R,Nf,9] (nullable): a gradient that reaches the post-activation raw directly.
 hipError_t composite_fine_backward_train_maps(const float* raw, const float* z, const TrainMapGrads& g, float g_tsigma,
                                               const float* gext, size_t R, int Nf, float* gpre, hipStream_t s);
+// What the compositing-backward stage of a step starts from: the operands of NerfWLoss (dfn_nerfh_train_backward: maps == nullptr, the
+// two kernels of nerfh_train.hip) or the upstream gradients of every output (the *_maps entries: the two kernels of nerfh_train_maps.hip).
+// Everything downstream consumes the gpre it writes.
+struct CompGrads {
+  const float *g_rgb, *g_rgb0, *g_beta;
+  float g_tsigma;
+  const float* g_ts_dense;
+  const TrainMapGrads* maps;
+  const float* raw_ext;
+};
+// That stage, for the exact and the fused step (host code, nerfh_train_api.hip; returns a DFN_* code, `what` labels a launch failure).
+// zero_a / zero_t (n_a / n_t floats; null: zero nothing here): the embedding gradients the scatters at the end of a step accumulate
+// into — zeroed inside composite_coarse_backward's launch, or by two memsets in front of the maps pair.
+int composite_backward(const char* what, const CompGrads& cg, const float* raw, const float* z_f, const float* raw_c, const float* z_c,
+                       const float* noise, float noise_std, size_t R, int Nc, int Nf, float* gpre_f, float* gpre_c, hipStream_t s,
+                       float* zero_a = nullptr, size_t n_a = 0, float* zero_t = nullptr, size_t n_t = 0);
 // out[r, 0..C) = sum_s g[(r * Ns + s) * ld + c]
 hipError_t sum_over_samples(const float* g, int ld, int C, size_t R, int Ns, float* out, int ldo, hipStream_t s);
 // embedding-table gradients: grad_emb[idx(hist[r, b]), j] += g_in[r * ld + off + b * dim + j] (atomic fp32 adds).

@@ -302,37 +302,36 @@ NetBufs bufs_of(const TrainWs& w, const Dims& m, bool fine, float* raw_f, size_t
   return b;
 }
 
-// What the compositing-backward stage of a step starts from: the operands of NerfWLoss (dfn_nerfh_train_backward: maps == nullptr, the
-// two kernels of nerfh_train.hip) or the upstream gradients of every output (the *_maps entries: the two kernels of nerfh_train_maps.hip).
-// Everything downstream consumes the gpre it writes.
-struct CompGrads {
-  const float *g_rgb, *g_rgb0, *g_beta;
-  float g_tsigma;
-  const float* g_ts_dense;
-  const TrainMapGrads* maps;
-  const float* raw_ext;
-};
+BwdBufs bwd_bufs_of(const TrainWs& w, bool fine) {
+  return fine ? BwdBufs{w.gpre_f, w.gA, w.gB, w.gfin, w.gt0, w.gt1, w.gsum, w.gray, w.wscratch}
+              : BwdBufs{w.gpre_c, w.gA_c, w.gB_c, w.gfin_c, w.gt0_c, nullptr, w.gsum_c, w.gray_c, w.wscratch_c};
+}
+
 TrainMapGrads map_grads_of(const dfn_train_map_grads* g) {
   return g ? TrainMapGrads{g->rgb, g->disp, g->acc, g->depth, g->beta, g->rgb0, g->disp0, g->acc0, g->depth0} : TrainMapGrads{};
 }
-int composite_backward(const char* fn, const CompGrads& cg, const float* raw, const float* z_f, const float* raw_c, const float* z_c,
-                       const float* noise, float noise_std, size_t R, int Nc, int Nf, float* gpre_f, float* gpre_c, hipStream_t s) {
-  if (cg.maps) {
-    CHECK_HIP(composite_fine_backward_train_maps(raw, z_f, *cg.maps, cg.g_tsigma, cg.raw_ext, R, Nf, gpre_f, s), fn);
-    CHECK_HIP(composite_coarse_backward_maps(raw_c, z_c, noise, noise_std, *cg.maps, R, Nc, gpre_c, s), fn);
-    return DFN_OK;
-  }
-  CHECK_HIP(composite_fine_backward_train(raw, z_f, cg.g_rgb, cg.g_beta, cg.g_tsigma, cg.g_ts_dense, R, Nf, gpre_f, s), fn);
-  CHECK_HIP(composite_coarse_backward(raw_c, z_c, noise, noise_std, cg.g_rgb0, R, Nc, gpre_c, s), fn);
-  return DFN_OK;
-}
-
 int check_train_args(dfn_nerfh_t h, int Nc, int Ni, const char* fn) {
   if (!h) return set_error(DFN_ERR_ARG, "%s: null handle", fn);
   if (Nc < 3 || Ni < 1 || Nc + Ni > 512) return set_error(DFN_ERR_UNSUPPORTED, "%s: need 3 <= N_samples, 1 <= N_importance, sum <= 512", fn);
   return DFN_OK;
 }
 }  // namespace
+
+// nerfh_train.h: the compositing-backward stage of the exact and of the fused step
+int dfn::train::composite_backward(const char* what, const CompGrads& cg, const float* raw, const float* z_f, const float* raw_c,
+                                   const float* z_c, const float* noise, float noise_std, size_t R, int Nc, int Nf, float* gpre_f,
+                                   float* gpre_c, hipStream_t s, float* zero_a, size_t n_a, float* zero_t, size_t n_t) {
+  if (cg.maps) {
+    if (zero_a) CHECK_HIP(hipMemsetAsync(zero_a, 0, n_a * sizeof(float), s), "train backward: zero embedding_a grad");
+    if (zero_t) CHECK_HIP(hipMemsetAsync(zero_t, 0, n_t * sizeof(float), s), "train backward: zero embedding_t grad");
+    CHECK_HIP(composite_fine_backward_train_maps(raw, z_f, *cg.maps, cg.g_tsigma, cg.raw_ext, R, Nf, gpre_f, s), what);
+    CHECK_HIP(composite_coarse_backward_maps(raw_c, z_c, noise, noise_std, *cg.maps, R, Nc, gpre_c, s), what);
+    return DFN_OK;
+  }
+  CHECK_HIP(composite_fine_backward_train(raw, z_f, cg.g_rgb, cg.g_beta, cg.g_tsigma, cg.g_ts_dense, R, Nf, gpre_f, s), what);
+  CHECK_HIP(composite_coarse_backward(raw_c, z_c, noise, noise_std, cg.g_rgb0, R, Nc, gpre_c, s, zero_a, n_a, zero_t, n_t), what);
+  return DFN_OK;
+}
 
 extern "C" int dfn_nerfh_train_param_count(void) { return kParamCount; }
 extern "C" const char* dfn_nerfh_train_param_name(int i) { return (i >= 0 && i < kParamCount) ? names()[i].c_str() : nullptr; }
@@ -433,8 +432,8 @@ int train_backward_impl(const char* fn, dfn_nerfh_t h, const float* const* param
     if (!params[i] || !grads[i]) return set_error(DFN_ERR_ARG, "%s: params[%d] / grads[%d] is null", fn, i, i);
   if (int rc = check_train_state(h, fn)) return rc;
   if (use_fused(h))
-    return fused::train_backward(h, params, hist, hist_rows, n_rays, Nc, Ni, noise, raw_noise_std, raw, cg.g_rgb, cg.g_rgb0, cg.g_beta,
-                                 cg.g_tsigma, cg.g_ts_dense, grads, workspace, workspace_bytes, HS(stream), cg.maps, cg.raw_ext);
+    return fused::train_backward(fn, h, params, hist, hist_rows, n_rays, Nc, Ni, noise, raw_noise_std, raw, cg, grads, workspace,
+                                 workspace_bytes, HS(stream));
   const Dims m = dims_of(h->desc);
   const TrainWs w = carve_train(static_cast<float*>(workspace), m, n_rays, Nc, Ni, true);
   if (w.total > workspace_bytes) return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.total);
@@ -448,8 +447,6 @@ int train_backward_impl(const char* fn, dfn_nerfh_t h, const float* const* param
   if (int rc = composite_backward("train backward: composite", cg, raw, w.z_f, w.raw_c, w.z_c, noise, raw_noise_std, R, Nc, Nf, w.gpre_f,
                                   w.gpre_c, s))
     return rc;
-  BwdBufs gf{w.gpre_f, w.gA, w.gB, w.gfin, w.gt0, w.gt1, w.gsum, w.gray, w.wscratch};
-  BwdBufs gc{w.gpre_c, w.gA_c, w.gB_c, w.gfin_c, w.gt0_c, nullptr, w.gsum_c, w.gray_c, w.wscratch_c};
   // The two networks' backward passes share nothing (z_samples.detach(), rendering.py:302): the coarse one — a third of the points,
   // 1.5 tiles per persistent workgroup, its launches half-empty in their second round — runs on a side stream beside the fine one.
   if (!h->side_stream) {
@@ -458,12 +455,12 @@ int train_backward_impl(const char* fn, dfn_nerfh_t h, const float* const* param
   }
   CHECK_HIP(hipEventRecord(h->side_ev[0], s), "train backward: fork");
   CHECK_HIP(hipStreamWaitEvent(h->side_stream, h->side_ev[0], 0), "train backward: fork");
-  if (int rc = net_backward(net_of(params, grads, false), m, bufs_of(w, m, false, nullptr, R, Nc, Ni), gc, false, hist, hist_rows, nullptr,
-                            nullptr, R, h->side_stream))
+  if (int rc = net_backward(net_of(params, grads, false), m, bufs_of(w, m, false, nullptr, R, Nc, Ni), bwd_bufs_of(w, false), false, hist,
+                            hist_rows, nullptr, nullptr, R, h->side_stream))
     return rc;
   CHECK_HIP(hipEventRecord(h->side_ev[1], h->side_stream), "train backward: join");
-  if (int rc = net_backward(net_of(params, grads, true), m, bufs_of(w, m, true, const_cast<float*>(raw), R, Nc, Ni), gf, true, hist,
-                            hist_rows, g_emb_a, g_emb_t, R, s))
+  if (int rc = net_backward(net_of(params, grads, true), m, bufs_of(w, m, true, const_cast<float*>(raw), R, Nc, Ni), bwd_bufs_of(w, true),
+                            true, hist, hist_rows, g_emb_a, g_emb_t, R, s))
     return rc;
   CHECK_HIP(hipStreamWaitEvent(s, h->side_ev[1], 0), "train backward: join");
   return DFN_OK;
@@ -583,15 +580,13 @@ int train_backward_rays_impl(const char* fn, dfn_nerfh_t h, const float* const* 
   if (int rc = composite_backward("train backward (rays): composite", cg, raw, w.z_f, w.raw_c, w.z_c, noise, raw_noise_std, R, Nc, Nf,
                                   w.gpre_f, w.gpre_c, s))
     return rc;
-  BwdBufs gf{w.gpre_f, w.gA, w.gB, w.gfin, w.gt0, w.gt1, w.gsum, w.gray, w.wscratch};
-  BwdBufs gc{w.gpre_c, w.gA_c, w.gB_c, w.gfin_c, w.gt0_c, nullptr, w.gsum_c, w.gray_c, w.wscratch_c};
-  if (int rc = net_backward(net_of(params, nullptr, true), m, bufs_of(w, m, true, const_cast<float*>(raw), R, Nc, Ni), gf, true, hist, hist_rows,
-                            nullptr, nullptr, R, s, false, g_pe, g_dpe))
+  if (int rc = net_backward(net_of(params, nullptr, true), m, bufs_of(w, m, true, const_cast<float*>(raw), R, Nc, Ni), bwd_bufs_of(w, true), true,
+                            hist, hist_rows, nullptr, nullptr, R, s, false, g_pe, g_dpe))
     return rc;
   CHECK_HIP(posenc_backward(rays_o, rays_d, w.view, w.z_f, g_pe, g_dpe, 28, R, Nf, gpts, s), "train backward (rays): fine encodings");
   CHECK_HIP(launch_ray_grad_reduce(gpts, w.z_f, rays_d, R, Nf, 1, grad_rays_o, grad_rays_d, nullptr, s), "train backward (rays): fine reduction");
-  if (int rc = net_backward(net_of(params, nullptr, false), m, bufs_of(w, m, false, nullptr, R, Nc, Ni), gc, false, hist, hist_rows, nullptr, nullptr,
-                            R, s, false, g_pe, g_dpe))
+  if (int rc = net_backward(net_of(params, nullptr, false), m, bufs_of(w, m, false, nullptr, R, Nc, Ni), bwd_bufs_of(w, false), false, hist, hist_rows,
+                            nullptr, nullptr, R, s, false, g_pe, g_dpe))
     return rc;
   CHECK_HIP(posenc_backward(rays_o, rays_d, w.view, w.z_c, g_pe, g_dpe, 28, R, Nc, gpts, s), "train backward (rays): coarse encodings");
   CHECK_HIP(launch_ray_grad_reduce(gpts, w.z_c, rays_d, R, Nc, 1, grad_rays_o, grad_rays_d, nullptr, s, 1), "train backward (rays): coarse reduction");
@@ -635,7 +630,29 @@ extern "C" size_t dfn_nerfh_generic_workspace_bytes(dfn_nerfh_t h, size_t n_rays
 }
 
 namespace {
-// `entry`: the public name the messages carry (the two entries share this body; viewdirs == nullptr: d / |d|, written to w.view)
+// The test-time forward of the generic-width render and of its gradient: sigma [R, Nc] from the coarse network, the fine depths, then
+// every activation of the fine network left in `w` and its outputs in raw [R, Nc+Ni, 9].  viewdirs == nullptr: d / |d|, written to `view`.
+int generic_forward(dfn_nerfh_t h, const Dims& m, const TrainWs& w, const float* rays_o, const float* rays_d, const float* viewdirs,
+                    float* view, const float* hist, size_t hist_rows, size_t R, int Nc, int Ni, float near, float far, float* sigma,
+                    float* raw, hipStream_t s) {
+  const int Nf = Nc + Ni;
+  const float* const* params = h->gen_params.data();
+  if (!viewdirs) CHECK_HIP(launch_viewdirs(rays_d, R, view, s), "generic render: viewdirs");
+  CHECK_HIP(ray_inputs(viewdirs ? viewdirs : view, hist, hist_rows, params[kCoarseParams + kFineParams], params[kCoarseParams + kFineParams + 1],
+                       m.hist_bin, m.dim_a, m.dim_t, m.n_vocab, R, w.dir_f, m.ld_df, w.t_in, m.ld_t, s),
+            "generic render: ray inputs");
+  CHECK_HIP(stratified_z(nullptr, R, Nc, near, far, w.z_c, s, h->render_flags & DFN_RENDER_LINDISP), "generic render: z");
+  CHECK_HIP(posenc_points(rays_o, rays_d, w.z_c, R, Nc, w.pe_c, s), "generic render: coarse encoding");
+  NetBufs bc = bufs_of(w, m, false, nullptr, R, Nc, Ni);
+  bc.raw = sigma;   // sigma only: [R, Nc]
+  bc.raw_ld = 1;
+  if (int rc = net_forward(net_of(params, nullptr, false), m, bc, false, true, s)) return rc;
+  CHECK_HIP(launch_sample_fine(sigma, R, Nc, Ni, near, far, w.z_f, nullptr, nullptr, s, h->render_flags & DFN_RENDER_LINDISP), "generic render: sample_fine");
+  CHECK_HIP(posenc_points(rays_o, rays_d, w.z_f, R, Nf, w.pe_f, s), "generic render: fine encoding");
+  return net_forward(net_of(params, nullptr, true), m, bufs_of(w, m, true, raw, R, Nc, Ni), true, false, s);
+}
+
+// `entry`: the public name the messages carry (the entries share this body)
 int generic_render_rays_impl(const char* entry, dfn_nerfh_t h, const float* rays_o, const float* rays_d, const float* viewdirs,
                              const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far, float* rgb,
                              float* disp, float* acc, float* raw, void* workspace, size_t workspace_bytes, void* stream,
@@ -653,25 +670,7 @@ int generic_render_rays_impl(const char* entry, dfn_nerfh_t h, const float* rays
   hipStream_t s = HS(stream);
   const size_t R = n_rays;
   const int Nf = Nc + Ni;
-  const float* const* params = h->gen_params.data();
-  const Net nc = net_of(params, nullptr, false), nf = net_of(params, nullptr, true);
-  const float* v = viewdirs;
-  if (!v) {
-    CHECK_HIP(launch_viewdirs(rays_d, R, w.view, s), "generic render: viewdirs");
-    v = w.view;
-  }
-  CHECK_HIP(ray_inputs(v, hist, hist_rows, params[kCoarseParams + kFineParams], params[kCoarseParams + kFineParams + 1], m.hist_bin,
-                       m.dim_a, m.dim_t, m.n_vocab, R, w.dir_f, m.ld_df, w.t_in, m.ld_t, s),
-            "generic render: ray inputs");
-  CHECK_HIP(stratified_z(nullptr, R, Nc, near, far, w.z_c, s, h->render_flags & DFN_RENDER_LINDISP), "generic render: z");
-  CHECK_HIP(posenc_points(rays_o, rays_d, w.z_c, R, Nc, w.pe_c, s), "generic render: coarse encoding");
-  NetBufs bc = bufs_of(w, m, false, nullptr, R, Nc, Ni);
-  bc.raw = sigma;   // sigma only: [R, Nc]
-  bc.raw_ld = 1;
-  if (int rc = net_forward(nc, m, bc, false, true, s)) return rc;
-  CHECK_HIP(launch_sample_fine(sigma, R, Nc, Ni, near, far, w.z_f, nullptr, nullptr, s, h->render_flags & DFN_RENDER_LINDISP), "generic render: sample_fine");
-  CHECK_HIP(posenc_points(rays_o, rays_d, w.z_f, R, Nf, w.pe_f, s), "generic render: fine encoding");
-  if (int rc = net_forward(nf, m, bufs_of(w, m, true, raw, R, Nc, Ni), true, false, s)) return rc;
+  if (int rc = generic_forward(h, m, w, rays_o, rays_d, viewdirs, w.view, hist, hist_rows, R, Nc, Ni, near, far, sigma, raw, s)) return rc;
   CHECK_HIP(launch_composite_fine(raw, w.z_f, R, Nf, 0.1f, DFN_COMP_TEST_TIME | DFN_COMP_STATIC_ONLY, rgb, disp, acc, nullptr, nullptr,
                                   nullptr, s),
             "generic render: composite");
@@ -765,66 +764,21 @@ int generic_render_rays_backward_impl(const char* entry, dfn_nerfh_t h, const fl
   hipStream_t s = HS(stream);
   const TrainWs& w = g.t;
   const size_t R = n_rays;
-  const int Nf = Nc + Ni, W = m.W, W2 = m.W2;
-  const long long P = (long long)R * Nf;
-  const float* const* params = h->gen_params.data();
-  const Net nc = net_of(params, nullptr, false), nf = net_of(params, nullptr, true);
-  const float* v = viewdirs;
-  if (!v) {
-    CHECK_HIP(launch_viewdirs(rays_d, R, g.view, s), "generic render gradient: viewdirs");
-    v = g.view;
-  }
+  const int Nf = Nc + Ni;
+  const float* v = viewdirs ? viewdirs : g.view;
   // ---- forward (dfn_nerfh_generic_render_rays), every fine activation kept in the workspace
-  CHECK_HIP(ray_inputs(v, hist, hist_rows, params[kCoarseParams + kFineParams], params[kCoarseParams + kFineParams + 1], m.hist_bin,
-                       m.dim_a, m.dim_t, m.n_vocab, R, w.dir_f, m.ld_df, w.t_in, m.ld_t, s),
-            "generic render gradient: ray inputs");
-  CHECK_HIP(stratified_z(nullptr, R, Nc, near, far, w.z_c, s, h->render_flags & DFN_RENDER_LINDISP), "generic render gradient: z");
-  CHECK_HIP(posenc_points(rays_o, rays_d, w.z_c, R, Nc, w.pe_c, s), "generic render gradient: coarse encoding");
-  NetBufs bc = bufs_of(w, m, false, nullptr, R, Nc, Ni);
-  bc.raw = g.sigma;
-  bc.raw_ld = 1;
-  if (int rc = net_forward(nc, m, bc, false, true, s)) return rc;
-  CHECK_HIP(launch_sample_fine(g.sigma, R, Nc, Ni, near, far, w.z_f, nullptr, nullptr, s, h->render_flags & DFN_RENDER_LINDISP), "generic render gradient: sample_fine");
-  CHECK_HIP(posenc_points(rays_o, rays_d, w.z_f, R, Nf, w.pe_f, s), "generic render gradient: fine encoding");
-  const NetBufs b = bufs_of(w, m, true, g.raw, R, Nc, Ni);
-  if (int rc = net_forward(nf, m, b, true, false, s)) return rc;
+  if (int rc = generic_forward(h, m, w, rays_o, rays_d, viewdirs, g.view, hist, hist_rows, R, Nc, Ni, near, far, g.sigma, g.raw, s)) return rc;
   // ---- d rgb -> d raw -> d pre-activation (in place)
   float* gpre = w.gpre_f;
   if (grads)
     CHECK_HIP(launch_composite_fine_backward_all(g.raw, w.z_f, R, Nf, 0.1f, mg, gpre, s, grad_raw), "generic render gradient: composite (all outputs)");
   else
     CHECK_HIP(launch_composite_fine_backward(g.raw, w.z_f, grad_rgb, R, Nf, gpre, s, grad_raw), "generic render gradient: composite");
-  CHECK_HIP(head_prime(g.raw, gpre, size_t(P), s), "generic render gradient: head derivatives");
-  // ---- data gradients (the calls of net_backward, without the weight gradients)
-  const int C = 9, ldw_dir = W + b.kd, ldw_te0 = W + m.nt;
-  const Net& n = nf;
-  CHECK_HIP(gemm_bwd(gpre + 4, C, 3, n.w[TRGB], W2, 0, W2, w.gt0, W2, 0, nullptr, 0, P, s), "generic render gradient: transient_rgb");
-  CHECK_HIP(gemm_bwd(gpre + 7, C, 1, n.w[TSIG], W2, 0, W2, w.gt0, W2, 1, nullptr, 0, P, s), "generic render gradient: transient_sigma");
-  CHECK_HIP(gemm_bwd(gpre + 8, C, 1, n.w[TBETA], W2, 0, W2, w.gt0, W2, 1, b.te[3], W2, P, s), "generic render gradient: transient_beta");
-  float* cur = w.gt0;
-  float* nxt = w.gt1;
-  for (int j = 3; j >= 1; --j) {
-    CHECK_HIP(gemm_bwd(cur, W2, W2, n.w[TE0 + j], W2, 0, W2, nxt, W2, 0, b.te[j - 1], W2, P, s), "generic render gradient: transient_encoding");
-    float* t = cur; cur = nxt; nxt = t;
-  }
-  CHECK_HIP(gemm_bwd(cur, W2, W2, n.w[TE0], ldw_te0, 0, W, w.gfin, W, 0, nullptr, 0, P, s), "generic render gradient: d final (transient)");
-  CHECK_HIP(gemm_bwd(gpre, C, 3, n.w[RGB], W2, 0, W2, w.gt0, W2, 0, b.dirh, W2, P, s), "generic render gradient: static_rgb");
-  CHECK_HIP(gemm_bwd(w.gt0, W2, W2, n.w[DIR], ldw_dir, W, kChDir, g.g_dpe, 28, 0, nullptr, 0, P, s), "generic render gradient: d pe_dir");
-  CHECK_HIP(gemm_bwd(w.gt0, W2, W2, n.w[DIR], ldw_dir, 0, W, w.gfin, W, 1, nullptr, 0, P, s), "generic render gradient: d final");
-  CHECK_HIP(gemm_bwd(w.gfin, W, W, n.w[FIN], W, 0, W, w.gA, W, 0, nullptr, 0, P, s), "generic render gradient: xyz_encoding_final");
-  CHECK_HIP(gemm_bwd(gpre + 3, C, 1, n.w[SIG], W, 0, W, w.gA, W, 1, b.h[7], W, P, s), "generic render gradient: static_sigma");
-  cur = w.gA;
-  nxt = w.gB;
-  for (int l = 7; l >= 1; --l) {
-    if (l == 4) {
-      CHECK_HIP(gemm_bwd(cur, W, W, n.w[l], W + kChXyz, 0, kChXyz, g.g_pe, 64, 0, nullptr, 0, P, s), "generic render gradient: d pe (skip)");
-      CHECK_HIP(gemm_bwd(cur, W, W, n.w[l], W + kChXyz, kChXyz, W, nxt, W, 0, b.h[3], W, P, s), "generic render gradient: xyz_encoding_5");
-    } else {
-      CHECK_HIP(gemm_bwd(cur, W, W, n.w[l], W, 0, W, nxt, W, 0, b.h[l - 1], W, P, s), "generic render gradient: xyz_encoding");
-    }
-    float* t = cur; cur = nxt; nxt = t;
-  }
-  CHECK_HIP(gemm_bwd(cur, W, W, n.w[0], kChXyz, 0, kChXyz, g.g_pe, 64, 1, nullptr, 0, P, s), "generic render gradient: d pe");
+  CHECK_HIP(head_prime(g.raw, gpre, R * size_t(Nf), s), "generic render gradient: head derivatives");
+  // ---- data gradients: the fine network's chain, continued into the encodings
+  if (int rc = net_backward(net_of(h->gen_params.data(), nullptr, true), m, bufs_of(w, m, true, g.raw, R, Nc, Ni), bwd_bufs_of(w, true), true,
+                            hist, hist_rows, nullptr, nullptr, R, s, /*weights*/ false, g.g_pe, g.g_dpe))
+    return rc;
   // ---- encodings, then the per-ray reduction of dfn_render_rays_backward
   CHECK_HIP(posenc_backward(rays_o, rays_d, v, w.z_f, g.g_pe, g.g_dpe, 28, R, Nf, g.gpts, s), "generic render gradient: encodings");
   CHECK_HIP(launch_ray_grad_reduce(g.gpts, w.z_f, rays_d, R, Nf, viewdirs == nullptr, grad_rays_o, grad_rays_d,

@@ -11,7 +11,7 @@ Two equivalent surfaces:
   * NerfHTrainer.train_step(...)  — forward + fused NerfWLoss + backward, three library calls (run_nerf.py uses this);
   * rendering.render(..., **render_kwargs_train) — returns tensors attached to autograd (`_RenderTrainFn`), so the
     reference's own loop shape (loss_func(results, target); loss.backward()) runs unchanged.  With diff_maps=True
-    (`_RenderTrainMapsFn`) EVERY output is attached, as in the reference — disp_map, acc_map, raw, disp0, acc0 and the two depths
+    (the node's diff_maps mode) EVERY output is attached, as in the reference — disp_map, acc_map, raw, disp0, acc0 and the two depths
     of rendering.py:241 — through dfn_nerfh_train_backward_maps: a depth, disparity or opacity term is the caller's torch code.
 The reference's random draws (stratified jitter, coarse-density noise, importance-sampling u) are drawn with torch on
 the device and handed to the library as inputs, which is what makes the path checkable against the reference.
@@ -165,14 +165,27 @@ class NerfHTrainer:
               "dfn_nerfw_loss")
         return loss5, (g_rgb, g_rgb0, g_beta), float(coef) * float(lambda_u) / (n * Nf)
 
-    def _map_operands(self, s, g_rgb, g_rgb0, g_beta, g_tsigma_dense, g_maps, g_raw):
-        """(held tensors, dfn_train_map_grads struct, grad_raw_ext) of a backward(g_maps=..., g_raw=...) call."""
+    def _comp_operands(self, s, g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense, g_maps, g_raw):
+        """What the compositing-backward stage of backward() / backward_rays() starts from -> (True: the *_maps entry, that entry's
+        compositing arguments, the tensors they point into).  g_maps / g_raw given: dfn_train_map_grads + grad_raw_ext; neither: the
+        operands of NerfWLoss."""
+        n, Nf = s["n"], s["Nc"] + s["Ni"]
+        if g_maps is None and g_raw is None:
+            held = (_f32c(g_rgb).reshape(-1, 3), _f32c(g_rgb0).reshape(-1, 3), _f32c(g_beta).reshape(-1),
+                    None if g_tsigma_dense is None else _f32c(g_tsigma_dense).reshape(n, Nf))
+            return False, (ptr(held[0]), ptr(held[1]), ptr(held[2]), float(g_tsigma), ptr(held[3])), held
         if g_rgb is not None or g_rgb0 is not None or g_beta is not None or g_tsigma_dense is not None:
             raise ValueError("g_maps / g_raw stand in the place of g_rgb, g_rgb0, g_beta and g_tsigma_dense (a gradient given twice): name them "
                              "in g_maps (rgb, rgb0, beta) and put a dense transient_sigma gradient into channel 7 of g_raw")
-        held, st = train_map_grads(g_maps, s["n"])
-        ext = None if g_raw is None else _f32c(g_raw).reshape(s["n"], s["Nc"] + s["Ni"], 9)
-        return held, st, ext
+        held, st = train_map_grads(g_maps, n)
+        ext = None if g_raw is None else _f32c(g_raw).reshape(n, Nf, 9)
+        return True, (ctypes.byref(st), float(g_tsigma), ptr(ext)), (held, st, ext)
+
+    @staticmethod
+    def _step_args(s):
+        """The arguments every backward entry shares: (the step's inputs up to raw, the workspace)."""
+        return ((ptr(s["hist"]), s["hist"].shape[0], s["n"], s["Nc"], s["Ni"], ptr(s["noise"]), s["raw_noise_std"], ptr(s["raw"])),
+                (ctypes.c_void_p(s["ws"].data_ptr()), s["ws"].numel()))
 
     def backward(self, g_rgb=None, g_rgb0=None, g_beta=None, g_tsigma=0., g_tsigma_dense=None, grads=None, saved=None, g_maps=None, g_raw=None):
         """Gradients of every parameter from the last forward() (or from `saved`, the state an autograd node took from its own
@@ -188,23 +201,12 @@ class NerfHTrainer:
                 if p.grad is None or not p.grad.is_contiguous():
                     p.grad = torch.empty_like(p)
             grads = [p.grad for p in self.params]
-        if g_maps is not None or g_raw is not None:
-            held, st, ext = self._map_operands(s, g_rgb, g_rgb0, g_beta, g_tsigma_dense, g_maps, g_raw)
-            self.set_mode(s["exact"])
-            check(self.lib.dfn_nerfh_train_backward_maps(self.engine.handle, self._ptr_array(self.params), ptr(s["hist"]), s["hist"].shape[0],
-                                                         s["n"], s["Nc"], s["Ni"], ptr(s["noise"]), s["raw_noise_std"], ptr(s["raw"]),
-                                                         ctypes.byref(st), float(g_tsigma), ptr(ext), self._ptr_array(grads),
-                                                         ctypes.c_void_p(s["ws"].data_ptr()), s["ws"].numel(), current_stream()),
-                  "dfn_nerfh_train_backward_maps")
-            return grads
-        g_rgb, g_rgb0, g_beta = _f32c(g_rgb).reshape(-1, 3), _f32c(g_rgb0).reshape(-1, 3), _f32c(g_beta).reshape(-1)
-        gd = None if g_tsigma_dense is None else _f32c(g_tsigma_dense).reshape(s["n"], s["Nc"] + s["Ni"])
+        maps, comp, held = self._comp_operands(s, g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense, g_maps, g_raw)
+        name = "dfn_nerfh_train_backward_maps" if maps else "dfn_nerfh_train_backward"
+        step, ws = self._step_args(s)
         self.set_mode(s["exact"])   # the workspace was laid out by the forward's implementation
-        check(self.lib.dfn_nerfh_train_backward(self.engine.handle, self._ptr_array(self.params), ptr(s["hist"]), s["hist"].shape[0], s["n"],
-                                                s["Nc"], s["Ni"], ptr(s["noise"]), s["raw_noise_std"], ptr(s["raw"]), ptr(g_rgb), ptr(g_rgb0),
-                                                ptr(g_beta), float(g_tsigma), ptr(gd), self._ptr_array(grads),
-                                                ctypes.c_void_p(s["ws"].data_ptr()), s["ws"].numel(), current_stream()),
-              "dfn_nerfh_train_backward")
+        check(getattr(self.lib, name)(self.engine.handle, self._ptr_array(self.params), *step, *comp, self._ptr_array(grads), *ws,
+                                      current_stream()), name)
         return grads
 
     def backward_rays(self, g_rgb=None, g_rgb0=None, g_beta=None, g_tsigma=0., g_tsigma_dense=None, saved=None, g_maps=None, g_raw=None):
@@ -218,23 +220,11 @@ class NerfHTrainer:
         go, gdir = torch.empty(s["n"], 3, device=dev), torch.empty(s["n"], 3, device=dev)
         nb = self.lib.dfn_nerfh_train_backward_rays_scratch_bytes(s["n"], s["Nc"], s["Ni"])
         scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-        if g_maps is not None or g_raw is not None:
-            held, st, ext = self._map_operands(s, g_rgb, g_rgb0, g_beta, g_tsigma_dense, g_maps, g_raw)
-            check(self.lib.dfn_nerfh_train_backward_rays_maps(self.engine.handle, self._ptr_array(self.params), ptr(s["rays_o"]), ptr(s["rays_d"]),
-                                                              ptr(s["hist"]), s["hist"].shape[0], s["n"], s["Nc"], s["Ni"], ptr(s["noise"]),
-                                                              s["raw_noise_std"], ptr(s["raw"]), ctypes.byref(st), float(g_tsigma), ptr(ext),
-                                                              ptr(go), ptr(gdir), ctypes.c_void_p(s["ws"].data_ptr()), s["ws"].numel(),
-                                                              ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), current_stream()),
-                  "dfn_nerfh_train_backward_rays_maps")
-            return go, gdir
-        g_rgb, g_rgb0, g_beta = _f32c(g_rgb).reshape(-1, 3), _f32c(g_rgb0).reshape(-1, 3), _f32c(g_beta).reshape(-1)
-        gd = None if g_tsigma_dense is None else _f32c(g_tsigma_dense).reshape(s["n"], s["Nc"] + s["Ni"])
-        check(self.lib.dfn_nerfh_train_backward_rays(self.engine.handle, self._ptr_array(self.params), ptr(s["rays_o"]), ptr(s["rays_d"]),
-                                                     ptr(s["hist"]), s["hist"].shape[0], s["n"], s["Nc"], s["Ni"], ptr(s["noise"]),
-                                                     s["raw_noise_std"], ptr(s["raw"]), ptr(g_rgb), ptr(g_rgb0), ptr(g_beta), float(g_tsigma), ptr(gd),
-                                                     ptr(go), ptr(gdir), ctypes.c_void_p(s["ws"].data_ptr()), s["ws"].numel(),
-                                                     ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), current_stream()),
-              "dfn_nerfh_train_backward_rays")
+        maps, comp, held = self._comp_operands(s, g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense, g_maps, g_raw)
+        name = "dfn_nerfh_train_backward_rays_maps" if maps else "dfn_nerfh_train_backward_rays"
+        step, ws = self._step_args(s)
+        check(getattr(self.lib, name)(self.engine.handle, self._ptr_array(self.params), ptr(s["rays_o"]), ptr(s["rays_d"]), *step, *comp,
+                                      ptr(go), ptr(gdir), *ws, ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), current_stream()), name)
         return go, gdir
 
     def recommit(self):
@@ -346,40 +336,61 @@ class NerfHTrainer:
 class _RenderTrainFn(torch.autograd.Function):
     """render_rays in training mode as an autograd node: outputs (rgb, disp, acc, raw, rgb0, disp0, acc0, z_std, beta,
     transient_sigmas); gradients flow from rgb, rgb0, beta and transient_sigmas to every parameter (what NerfWLoss
-    uses, losses.py:43-52); the other outputs are marked non-differentiable."""
+    uses, losses.py:43-52); the other outputs are marked non-differentiable.
+    diff_maps (render(test_time=False, diff_maps=True)): EVERY output is attached, and depth, depth0 follow the ten: all but z_std (a
+    function of the detached z_samples, rendering.py:302,327) are differentiable, as the reference's are (rendering.py:161-243, :295-331).
+    An output the loss does not use arrives as None = a NULL upstream pointer.  The forward values are the same bits either way."""
+
+    NAMES = ("rgb", "disp", "acc", None, "rgb0", "disp0", "acc0", None, "beta", None, "depth", "depth0")   # outputs -> dfn_train_map_grads
 
     @staticmethod
-    def forward(ctx, trainer, rays_o, rays_d, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, *params):
+    def forward(ctx, diff_maps, trainer, rays_o, rays_d, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, *params):
         # gradients w.r.t. the rays (pose optimisation through the training render) come from the exact step, which keeps activations
-        ctx.want_rays = bool(ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        out = trainer.forward(rays_o, rays_d, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, exact=True if ctx.want_rays else None)
+        ctx.want_rays = bool(ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+        out = trainer.forward(rays_o, rays_d, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, exact=True if ctx.want_rays else None,
+                              maps=diff_maps)
+        ctx.diff_maps = diff_maps
         ctx.trainer = trainer
         ctx.saved = trainer._saved
-        ts = out["transient_sigmas"].contiguous()
-        nd = (out["disp_map"], out["acc_map"], out["raw"], out["disp0"], out["acc0"], out["z_std"])
-        ctx.mark_non_differentiable(*nd)
-        return (out["rgb_map"], out["disp_map"], out["acc_map"], out["raw"], out["rgb0"], out["disp0"], out["acc0"], out["z_std"],
-                out["beta"], ts)
+        # (diff_maps) the caller's raw is a copy: an in-place edit of it must not reach the state the backward reads
+        res = (out["rgb_map"], out["disp_map"], out["acc_map"], out["raw"].clone() if diff_maps else out["raw"], out["rgb0"], out["disp0"],
+               out["acc0"], out["z_std"], out["beta"], out["transient_sigmas"].contiguous())
+        if diff_maps:
+            ctx.set_materialize_grads(False)
+            ctx.mark_non_differentiable(out["z_std"])
+            return res + (out["depth"], out["depth0"])
+        ctx.mark_non_differentiable(*(res[i] for i in (1, 2, 3, 5, 6, 7)))
+        return res
 
     @staticmethod
-    def backward(ctx, g_rgb, _gd, _ga, _graw, g_rgb0, _gd0, _ga0, _gz, g_beta, g_ts):
-        tr = ctx.trainer
-        if tr._saved is not ctx.saved:
+    def backward(ctx, *gs):
+        tr, s = ctx.trainer, ctx.saved
+        if tr._saved is not s:
             raise RuntimeError("render(): backward through a training render after another forward reused its workspace")
-        n = ctx.saved["n"]
-        dev = ctx.saved["raw"].device
-        z3, z1 = torch.zeros(n, 3, device=dev), torch.zeros(n, device=dev)
-        grads = [torch.empty_like(p) for p in tr.params]
-        gs = (z3 if g_rgb is None else g_rgb, z3 if g_rgb0 is None else g_rgb0, z1 if g_beta is None else g_beta)
+        n, dev = s["n"], s["raw"].device
+        g_raw, g_ts = gs[3], gs[9]
+        if ctx.diff_maps:
+            g_maps = {k: g for k, g in zip(_RenderTrainFn.NAMES, gs) if k is not None and g is not None}
+            if g_ts is not None:   # transient_sigmas = raw[..., 7]
+                g_raw = torch.zeros(n, s["Nc"] + s["Ni"], 9, device=dev) if g_raw is None else g_raw.clone()
+                g_raw[..., 7] += g_ts
+            if not g_maps and g_raw is None:
+                g_maps = dict(rgb=torch.zeros(n, 3, device=dev))
+            ops = dict(g_maps=g_maps, g_raw=g_raw)
+        else:
+            z3, z1 = torch.zeros(n, 3, device=dev), torch.zeros(n, device=dev)
+            ops = dict(g_rgb=z3 if gs[0] is None else gs[0], g_rgb0=z3 if gs[4] is None else gs[4], g_beta=z1 if gs[8] is None else gs[8],
+                       g_tsigma_dense=g_ts)
         g_o = g_d = None
         if ctx.want_rays:   # before the weight gradients: they reuse the gradient buffers of the workspace
-            g_o, g_d = tr.backward_rays(*gs, 0., g_ts, saved=ctx.saved)
-        if any(ctx.needs_input_grad[12:]):
-            tr.backward(*gs, 0., g_ts, grads=grads, saved=ctx.saved)
-            _after_node_backward(tr, ctx.saved, dev)
+            g_o, g_d = tr.backward_rays(saved=s, **ops)
+        if any(ctx.needs_input_grad[13:]):
+            grads = [torch.empty_like(p) for p in tr.params]
+            tr.backward(grads=grads, saved=s, **ops)
+            _after_node_backward(tr, s, dev)
         else:
             grads = [None] * len(tr.params)
-        return (None, g_o if ctx.needs_input_grad[1] else None, g_d if ctx.needs_input_grad[2] else None) + (None,) * 9 + tuple(grads)
+        return (None, None, g_o if ctx.needs_input_grad[2] else None, g_d if ctx.needs_input_grad[3] else None) + (None,) * 9 + tuple(grads)
 
 
 def _after_node_backward(tr, saved, dev):
@@ -393,61 +404,13 @@ def _after_node_backward(tr, saved, dev):
                                 "trainer.recommit() (weights outgrew the committed scale) or set trainer.exact = True")
 
 
-class _RenderTrainMapsFn(torch.autograd.Function):
-    """render_rays in training mode with EVERY output attached (render(test_time=False, diff_maps=True)): outputs (rgb, disp, acc, raw,
-    rgb0, disp0, acc0, z_std, beta, transient_sigmas, depth, depth0); all but z_std (a function of the detached z_samples,
-    rendering.py:302,327) are differentiable, as the reference's are (rendering.py:161-243, :295-331).  An output the loss does not use
-    arrives as None = a NULL upstream pointer.  Forward values are the bits of _RenderTrainFn's."""
-
-    NAMES = ("rgb", "disp", "acc", None, "rgb0", "disp0", "acc0", None, "beta", None, "depth", "depth0")   # outputs -> dfn_train_map_grads
-
-    @staticmethod
-    def forward(ctx, trainer, rays_o, rays_d, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, *params):
-        ctx.want_rays = bool(ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        out = trainer.forward(rays_o, rays_d, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, exact=True if ctx.want_rays else None,
-                              maps=True)
-        ctx.trainer = trainer
-        ctx.saved = trainer._saved
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(out["z_std"])
-        # the caller's raw is a copy: an in-place edit of it must not reach the state the backward reads
-        return (out["rgb_map"], out["disp_map"], out["acc_map"], out["raw"].clone(), out["rgb0"], out["disp0"], out["acc0"], out["z_std"],
-                out["beta"], out["transient_sigmas"].contiguous(), out["depth"], out["depth0"])
-
-    @staticmethod
-    def backward(ctx, *gs):
-        tr = ctx.trainer
-        if tr._saved is not ctx.saved:
-            raise RuntimeError("render(): backward through a training render after another forward reused its workspace")
-        s = ctx.saved
-        n, dev = s["n"], s["raw"].device
-        g_maps = {k: g for k, g in zip(_RenderTrainMapsFn.NAMES, gs) if k is not None and g is not None}
-        g_raw, g_ts = gs[3], gs[9]
-        if g_ts is not None:   # transient_sigmas = raw[..., 7]
-            g_raw = torch.zeros(n, s["Nc"] + s["Ni"], 9, device=dev) if g_raw is None else g_raw.clone()
-            g_raw[..., 7] += g_ts
-        if not g_maps and g_raw is None:
-            g_maps = dict(rgb=torch.zeros(n, 3, device=dev))
-        g_o = g_d = None
-        if ctx.want_rays:   # before the weight gradients: they reuse the gradient buffers of the workspace
-            g_o, g_d = tr.backward_rays(g_maps=g_maps, g_raw=g_raw, saved=s)
-        if any(ctx.needs_input_grad[12:]):
-            grads = [torch.empty_like(p) for p in tr.params]
-            tr.backward(g_maps=g_maps, g_raw=g_raw, grads=grads, saved=s)
-            _after_node_backward(tr, s, dev)
-        else:
-            grads = [None] * len(tr.params)
-        return (None, g_o if ctx.needs_input_grad[1] else None, g_d if ctx.needs_input_grad[2] else None) + (None,) * 9 + tuple(grads)
-
-
 def render_train(trainer, rays_o, rays_d, hist, Nc, Ni, near, far, perturb, raw_noise_std, retraw, draws=None, diff_maps=False, maps=()):
     """The training branch of rendering.render(): [rgb, disp, acc, extras] with the reference's extras keys.  diff_maps: every output
-    attached (_RenderTrainMapsFn), and the depths named by `maps` (out of depth, depth0) among the extras."""
+    attached (_RenderTrainFn's diff_maps mode), and the depths named by `maps` (out of depth, depth0) among the extras."""
     n = rays_o.reshape(-1, 3).shape[0]
     t_rand, noise, u = draws if draws is not None else NerfHTrainer.draw(n, Nc, Ni, float(perturb), rays_o.device)
-    fn = _RenderTrainMapsFn if diff_maps else _RenderTrainFn
-    (rgb, disp, acc, raw, rgb0, disp0, acc0, z_std, beta, ts, *depths) = fn.apply(
-        trainer, rays_o, rays_d, hist, int(Nc), int(Ni), float(near), float(far), t_rand, noise, float(raw_noise_std), u, *trainer.params)
+    (rgb, disp, acc, raw, rgb0, disp0, acc0, z_std, beta, ts, *depths) = _RenderTrainFn.apply(
+        bool(diff_maps), trainer, rays_o, rays_d, hist, int(Nc), int(Ni), float(near), float(far), t_rand, noise, float(raw_noise_std), u, *trainer.params)
     extras = {'rgb0': rgb0, 'disp0': disp0, 'acc0': acc0, 'z_std': z_std, 'transient_sigmas': ts, 'beta': beta}
     if retraw:
         extras['raw'] = raw
