@@ -164,6 +164,9 @@ struct Packer {
   std::string pre;
   int width() const { return h->desc.width; }
   mutable int fwd_units = 0;   // pack_bwd: number of forward units at the head of the table
+  // kernel variant 5 (kFineFoldSeq): dir_encoding.0[:, :W] . xyz_encoding_final and transient_encoding.0[:, :W] . xyz_encoding_final,
+  // row-major [W / 2][W] (fold_final)
+  std::vector<float> fold_dir, fold_tr;
   Mat mat(const std::string& key) const {
     Mat m;
     const auto& w = h->params.at(pre + key + ".weight");
@@ -198,6 +201,12 @@ struct Packer {
         else { m = mat("transient_beta.0"); row = -1; }
         break;
       case LY_SIG: m = mat("static_sigma.0"); row = i == 0 ? 0 : -1; break;
+      case LY_DIRF: case LY_TE0F:   // no bias of their own (unit_has_bias): it is folded per ray
+        m = Mat();
+        m.w = (layer == LY_DIRF ? fold_dir : fold_tr).data();
+        m.rows = width() / 2;
+        m.cols = width();
+        break;
     }
   }
   // Source column of slot s of half h; < 0 = zero.
@@ -219,7 +228,7 @@ struct Packer {
   // PrecX3M16: row of the 32-row M-block's weights behind packed row i (-1 = zero row), see head_row_m16
   int row_m16(int layer, int mb, int i) const { return head_block(layer, mb) ? head_row_m16(i) : i; }
   // The bias folded per ray (DIR, TE0) is NOT packed into the unit.
-  static bool unit_has_bias(int layer) { return layer != LY_DIR && layer != LY_TE0; }
+  static bool unit_has_bias(int layer) { return layer != LY_DIR && layer != LY_TE0 && layer != LY_DIRF && layer != LY_TE0F; }
 
   // One layer's M-blocks [mb0, mb0+group) as [A fragments][bias fragments], appended at `base`.
   // split-f16 (P::kSplit): a fragment is a hi plane then a lo plane of w * wscale; the bias is pre-multiplied by
@@ -393,8 +402,8 @@ struct Packer {
   // layers of one group (kFineGroup / kCoarseGroup) share a unit; otherwise a unit is <= umb M-blocks of a layer.
   // l5_umb: M-blocks per unit of layer 5 (< 0: the same as the other layers)
   template <class P>
-  void pack(bool fine, int umb, bool merge, std::vector<uint8_t>& blob, std::vector<uint32_t>& tab, int l5_umb = -1) const {
-    const int* seq = fine ? kFineSeq : kCoarseSeq;
+  void pack(bool fine, int umb, bool merge, std::vector<uint8_t>& blob, std::vector<uint32_t>& tab, int l5_umb = -1, bool fold = false) const {
+    const int* seq = fine ? (fold ? kFineFoldSeq : kFineSeq) : kCoarseSeq;
     const int* grp = fine ? kFineGroup : kCoarseGroup;
     const int nl = fine ? kFineLayers : kCoarseLayers;
     if (merge) {
@@ -443,6 +452,28 @@ struct Packer {
     }
   }
 };
+
+// xyz_encoding_final is a Linear without activation whose output feeds only the first W columns of dir_encoding.0 and
+// transient_encoding.0:  A[:, :W] (F h + b_F) = (A[:, :W] F) h + A[:, :W] b_F.  Both products in double, rounded to float once.
+// a: [rows][lda] row-major (its first W columns are used), F: [W][W], b_F: [W]  ->  af [rows][W], ab [rows].
+void fold_final(const std::vector<float>& a, int rows, int lda, const std::vector<float>& F, const std::vector<float>& bF, int W,
+                std::vector<float>& af, std::vector<float>& ab) {
+  af.assign(size_t(rows) * W, 0.f);
+  ab.assign(rows, 0.f);
+  std::vector<double> acc(W);
+  for (int r = 0; r < rows; ++r) {
+    std::fill(acc.begin(), acc.end(), 0.0);
+    double b = 0.0;
+    for (int k = 0; k < W; ++k) {
+      const double ark = a[size_t(r) * lda + k];
+      const float* frow = &F[size_t(k) * W];
+      for (int c = 0; c < W; ++c) acc[c] += ark * double(frow[c]);
+      b += ark * double(bF[k]);
+    }
+    for (int c = 0; c < W; ++c) af[size_t(r) * W + c] = float(acc[c]);
+    ab[r] = float(b);
+  }
+}
 
 int upload(const void* src, size_t bytes, void** dst) {
   if (hipMalloc(dst, bytes ? bytes : 16) != hipSuccess) return set_error(DFN_ERR_HIP, "hipMalloc(%zu) failed", bytes);
@@ -523,6 +554,7 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
     for (size_t o : offs) h->gen_params.push_back(h->gen_blob + o);
   }
   const int Wd = h->desc.width;
+  std::vector<float> fold_bd, fold_bt;   // netwidth 128: W_dir[:, :W] b_final, W_tr[:, :W] b_final (fold_final)
   if (Wd != kWidth && Wd != kMaxWidth) {   // generic-width path only
     h->committed = true;
     return DFN_OK;
@@ -557,6 +589,9 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
   for (int f = 0; f < 2; ++f)
     for (int prec = 0; prec < 3; ++prec)
       for (int var = 0; var < kVariants; ++var) {
+        // variant 5 has one network of its own, the split-f16 fine one; everything else of it is variant 4's (net_of)
+        const bool fold = var == kFoldVariant;
+        if (fold && !(f == 1 && prec == DFN_PREC_F16X3)) continue;
         Packer pk{h, f ? "fine." : "coarse."};
         std::vector<uint8_t> blob;
         std::vector<uint32_t> tab;
@@ -576,7 +611,16 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
           sexp = sexp < -8 ? -8 : (sexp > 24 ? 24 : sexp);
           pk.wscale = std::ldexp(1.f, sexp);
           n.in_scale = pk.wscale * kX3ActScale;
-          if (var == 4) pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)));
+          if (fold) {
+            // the folded matrices stay out of the scan above: wscale is what every other layer's operands were scaled for.  Their
+            // entries may exceed the largest weight (sums of W products); as hi + lo f16 pairs of w x wscale that is harmless.
+            const int ldd = Wd + kChDir + h->desc.hist_bin * h->desc.dim_a, ldt = Wd + h->desc.hist_bin * h->desc.dim_t;
+            const auto& F = h->params.at("fine.xyz_encoding_final.weight");
+            const auto& bF = h->params.at("fine.xyz_encoding_final.bias");
+            fold_final(h->params.at("fine.dir_encoding.0.weight"), Wd / 2, ldd, F, bF, Wd, pk.fold_dir, fold_bd);
+            fold_final(h->params.at("fine.transient_encoding.0.weight"), Wd / 2, ldt, F, bF, Wd, pk.fold_tr, fold_bt);
+            pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)), true);
+          } else if (var == 4) pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)));
           else pk.pack<PrecX3>(f, unit_mb<PrecX3>(var), false, blob, tab, l5_unit_mb_p<PrecX3>(unit_mb<PrecX3>(var)));
         }
         int rc = upload(blob.data(), blob.size(), reinterpret_cast<void**>(&n.blob));
@@ -618,8 +662,8 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
   const auto& et = h->params.at("embedding_t.weight");
   std::vector<float> ex;
   const size_t o_wd = 0, o_bd = o_wd + size_t(kd) * NO, o_wt = o_bd + NO, o_bt = o_wt + size_t(nt) * NO,
-               o_ea = o_bt + NO, o_et = o_ea + ea.size();
-  ex.resize(o_et + et.size());
+               o_ea = o_bt + NO, o_et = o_ea + ea.size(), o_bdf = o_et + et.size(), o_btf = o_bdf + NO;
+  ex.resize(o_btf + NO);
   const int ld_d = Wd + kd, ld_t = Wd + nt;
   for (int j = 0; j < kd; ++j)
     for (int f = 0; f < NO; ++f) ex[o_wd + size_t(j) * NO + f] = wd[size_t(f) * ld_d + Wd + j];
@@ -629,6 +673,11 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
   std::memcpy(&ex[o_bt], bt.data(), NO * 4);
   std::memcpy(&ex[o_ea], ea.data(), ea.size() * 4);
   std::memcpy(&ex[o_et], et.data(), et.size() * 4);
+  // variant 5's per-ray seeds: b + W[:, :W] b_final (netwidth 256 has no variant 5: the plain biases)
+  for (int f = 0; f < NO; ++f) {
+    ex[o_bdf + f] = fold_bd.empty() ? bd[f] : bd[f] + fold_bd[f];
+    ex[o_btf + f] = fold_bt.empty() ? bt[f] : bt[f] + fold_bt[f];
+  }
   int rc = upload(ex.data(), ex.size() * 4, reinterpret_cast<void**>(&h->extra));
   if (rc) return rc;
   h->rb.w_dir = h->extra + o_wd;
@@ -642,6 +691,9 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
   h->rb.dim_t = d.dim_t;
   h->rb.n_vocab = d.n_vocab;
   h->rb.nout = NO;
+  h->rb_fold = h->rb;
+  h->rb_fold.b_dir = h->extra + o_bdf;
+  h->rb_fold.b_tr = h->extra + o_btf;
   h->committed = true;
   h->fast = true;
   return DFN_OK;
@@ -726,18 +778,24 @@ static int check_grad_prec(int prec, const char* fn) {
   return DFN_OK;
 }
 
-// Kernel variant: DFN_MLP_VARIANT=0..4 (A/B aid, see nerfh_layout.h).  Default 4: split-f16 on 16x16x32 MFMAs (f16 / exact fp32 run their
-// variant-0 kernels under it); DFN_MLP_VARIANT=0 keeps the 32x32x16 split-f16 kernels.
+// Kernel variant: DFN_MLP_VARIANT=0..5 (A/B aid, see nerfh_layout.h).  Default 5: split-f16 on 16x16x32 MFMAs (f16 / exact fp32 run their
+// variant-0 kernels under it) with the fine render kernel's tail folded (fold_fine, base_variant); DFN_MLP_VARIANT=4 is the same
+// without the fold, DFN_MLP_VARIANT=0 keeps the 32x32x16 split-f16 kernels.
 static int mlp_variant_128();
 static int mlp_variant_of(dfn_nerfh_t h) { return h->desc.width == kWidth ? mlp_variant_128() : 0; }
 static int mlp_variant_128() {
   static int v = -1;
   if (v < 0) {
     const char* e = getenv("DFN_MLP_VARIANT");
-    v = (e && e[0] >= '0' && e[0] < '0' + kVariants) ? e[0] - '0' : 4;
+    v = (e && e[0] >= '0' && e[0] < '0' + kVariants) ? e[0] - '0' : kFoldVariant;
   }
   return v;
 }
+// Variant 5 differs from variant 4 in ONE kernel: the split-f16 netwidth-128 fine render kernel (launch_mlp_fold), which reads its own
+// packed network (net[1][F16X3][5]) and a per-ray table written from rb_fold.  Every other launch under it, the gradient paths' forward
+// recompute included (their backward kernels read the plain table), is variant 4's: base_variant.
+static int base_variant(int var) { return var == kFoldVariant ? 4 : var; }
+static bool fold_fine(int var, int prec) { return var == kFoldVariant && prec == DFN_PREC_F16X3; }
 
 // The handle's range-guard flag (device int): allocated and cleared by dfn_nerfh_commit, which fails loudly when it cannot be —
 // every kernel launch that carries the guard runs on a committed handle.
@@ -765,12 +823,13 @@ extern "C" int dfn_mlp_coarse(dfn_nerfh_t h, int prec, const float* rays_o, cons
   if (int rc = check_net(h, prec, "dfn_mlp_coarse", true)) return rc;
   if (!n_rays) return DFN_OK;
   if (!rays_o || !rays_d || !sigma || Nc < 1) return set_error(DFN_ERR_ARG, "dfn_mlp_coarse: bad argument");
-  const PackedNet& n = h->net[0][prec][mlp_variant_of(h)];
+  const int var = base_variant(mlp_variant_of(h));
+  const PackedNet& n = h->net[0][prec][var];
   MlpArgs a{n.blob, n.tab, n.n_units, rays_o, rays_d, nullptr, nullptr, sigma, nullptr, (long long)n_rays, Nc, near, far, nullptr, n.in_scale,
             h->render_flags & DFN_RENDER_LINDISP};
   a.status = range_flag_of(h);
   ScopedTimer t(0, HS(stream));
-  CHECK_HIP(launch_mlp(false, prec, mlp_variant_of(h), a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_coarse");
+  CHECK_HIP(launch_mlp(false, prec, var, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_coarse");
   return DFN_OK;
 }
 
@@ -851,12 +910,15 @@ extern "C" int dfn_mlp_fine(dfn_nerfh_t h, int prec, const float* rays_o, const 
       (hist_rows != 1 && hist_rows != n_rays))
     return set_error(DFN_ERR_ARG, "dfn_mlp_fine: bad argument (hist_rows must be 1 or n_rays)");
   float* table = static_cast<float*>(bias_ws);
-  CHECK_HIP(launch_ray_bias(h->rb, viewdirs, hist, hist_rows, n_rays, table, HS(stream)), "dfn_mlp_fine(ray_bias)");
-  const PackedNet& n = h->net[1][prec][mlp_variant_of(h)];
+  const bool fold = fold_fine(mlp_variant_of(h), prec);
+  const int var = fold ? kFoldVariant : base_variant(mlp_variant_of(h));
+  CHECK_HIP(launch_ray_bias(fold ? h->rb_fold : h->rb, viewdirs, hist, hist_rows, n_rays, table, HS(stream)), "dfn_mlp_fine(ray_bias)");
+  const PackedNet& n = h->net[1][prec][var];
   MlpArgs a{n.blob, n.tab, n.n_units, rays_o, rays_d, z_fine, table, raw, nullptr, (long long)n_rays, Nf, 0.f, 0.f, g_timing_buf, n.in_scale};
   a.status = range_flag_of(h);
   ScopedTimer t(1, HS(stream));
-  CHECK_HIP(launch_mlp(true, prec, mlp_variant_of(h), a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_fine");
+  if (fold) CHECK_HIP(launch_mlp_fold(false, a, device_cu_count(), HS(stream)), "dfn_mlp_fine");
+  else CHECK_HIP(launch_mlp(true, prec, var, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_fine");
   return DFN_OK;
 }
 
@@ -922,12 +984,13 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
   // Compositing is fused into the fine kernel when a wave's points are one ray segment and raw is not wanted: 64 samples per wave in
   // the f16 variants 0/1/3, 32 in the split-f16 and fp32 kernels (one point block per wave); the 3-block f16 variant and netwidth
   // 256 keep the separate compositor.
-  const int var = mlp_variant_of(h);
+  const bool fold = fold_fine(mlp_variant_of(h), prec);
+  const int var = base_variant(mlp_variant_of(h));
   const int seg = prec == DFN_PREC_F16 ? 64 : 32;
   const bool fused = !raw_out && Nf % seg == 0 && !(prec == DFN_PREC_F16 && var == 2) && h->desc.width == kWidth;
   const int cprec = (h->render_flags & DFN_RENDER_COARSE_F16) ? DFN_PREC_F16 : prec;   // the coarse pass only places the fine samples
   const PackedNet& nc = h->net[0][cprec][var];
-  const PackedNet& nf = h->net[1][prec][var];
+  const PackedNet& nf = h->net[1][prec][fold ? kFoldVariant : var];
   const int cus = device_cu_count();
   const size_t chunk = chunk_rays(n_rays);
   for (size_t r0 = 0; r0 < n_rays; r0 += chunk) {
@@ -951,13 +1014,14 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
     }
     {
       ScopedTimer t(DFN_PROF_RAY_BIAS, s);
-      CHECK_HIP(launch_ray_bias(h->rb, cv, ch, hist_rows, n, w.bias, s), "render: ray_bias");
+      CHECK_HIP(launch_ray_bias(fold ? h->rb_fold : h->rb, cv, ch, hist_rows, n, w.bias, s), "render: ray_bias");
     }
     {
       MlpArgs a{nf.blob, nf.tab, nf.n_units, co, cd, w.z, w.bias, raw, fused ? w.partial : nullptr, (long long)n, Nf, 0.f, 0.f, g_timing_buf, nf.in_scale};
       a.status = range_flag_of(h);
       ScopedTimer t(1, s);
-      if (fused && want_maps) CHECK_HIP(launch_mlp_maps(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP (maps)");
+      if (fold) CHECK_HIP(launch_mlp_fold(fused && want_maps, a, cus, s), "render: fine MLP (folded)");
+      else if (fused && want_maps) CHECK_HIP(launch_mlp_maps(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP (maps)");
       else CHECK_HIP(launch_mlp(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP");
     }
     if (fused && want_maps) {
@@ -1205,7 +1269,7 @@ BwdWorkspace carve_bwd(char* base, size_t n_rays, int Nc, int Ni) {
 int render_backward_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const float* v, bool derive_v,
                          const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
                          const float* grad_rgb, float* go, float* gd, float* gv, const BwdWorkspace& w, hipStream_t s) {
-  const int Nf = Nc + Ni, var = mlp_variant_of(h), cus = device_cu_count();
+  const int Nf = Nc + Ni, var = base_variant(mlp_variant_of(h)), cus = device_cu_count();
   const PackedNet& nc = h->net[0][prec][var];
   const PackedNet& nf = h->net[1][prec][var];
   const PackedNet& nb = h->bwd[prec];

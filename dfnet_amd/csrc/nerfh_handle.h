@@ -24,8 +24,9 @@ struct dfn_nerfh_s {
   PackedNet net[2][3][dfn::kVariants];  // [coarse/fine][prec][kernel variant]
   PackedNet bwd[3];                // [prec] fine forward units + backward (W^T) units of the gradient kernel
                                    // (prec 2: split-f16 forward and backward units)
-  float* extra = nullptr;  // w_dir^T | b_dir | w_tr^T | b_tr | emb_a | emb_t
+  float* extra = nullptr;  // w_dir^T | b_dir | w_tr^T | b_tr | emb_a | emb_t | b_dir + W_dir[:, :W] b_final | b_tr + W_tr[:, :W] b_final
   dfn::RayBiasWeights rb{};
+  dfn::RayBiasWeights rb_fold{};   // rb with the two folded bias vectors: the table of kernel variant 5's fine kernel, and of it alone
   bool fast = false;       // the register-resident MFMA kernels are packed (netwidth == dfn::kWidth)
   // Generic-width path (nerfh_train_api.hip): every parameter as a plain row-major fp32 device tensor, in the canonical
   // order of dfn_nerfh_train_param_name(); one allocation.

@@ -34,6 +34,9 @@ constexpr int kMapsRecFloats = 16;   // segment record of the maps flavour: the 
 hipError_t launch_mlp(bool fine, int prec, int variant, const MlpArgs& a, int n_cu, hipStream_t stream, int width = 128);
 // The fine kernel's render-maps flavour (nerfh_mlp_maps.hip): fine = true, a.partial with kMapsRecFloats floats per segment.
 hipError_t launch_mlp_maps(bool fine, int prec, int variant, const MlpArgs& a, int n_cu, hipStream_t stream, int width = 128);
+// Kernel variant 5's fine kernel (nerfh_mlp_fold.hip): split-f16, netwidth 128, the blob packed along kFineFoldSeq and a.ray_bias
+// written from the folded per-ray-bias weights (dfn_nerfh_s::rb_fold).  maps: the render-maps flavour, as launch_mlp_maps.
+hipError_t launch_mlp_fold(bool maps, const MlpArgs& a, int n_cu, hipStream_t stream);
 
 // --- stages (nerfh_stages.hip)
 // (frames > 1: c2w [frames,3,4], outputs [frames,H,W,3] — one launch for the frames of a mini-batch)

@@ -38,7 +38,10 @@ enum LayerId {
   LY_TE0,    // transient_encoding.0 on the `final` columns; transient-embedding columns -> per-ray bias
   LY_TE1, LY_TE2, LY_TE3,  // transient_encoding.{2,4,6}
   LY_THEAD,  // rows 0..2 transient_rgb, row 3 transient_sigma, row 8 transient_beta (all on half 0)
-  LY_SIG,    // coarse net: static_sigma alone (row 0)
+  LY_SIG,    // static_sigma alone (row 0): the coarse net, and the fine net of kernel variant 5
+  // kernel variant 5 (xyz_encoding_final folded at commit): h8 -> 64 directly, the shapes of LY_DIR / LY_TE0
+  LY_DIRF,   // (dir_encoding.0[:, :W] . xyz_encoding_final) on h8; the per-ray bias also carries dir_encoding.0[:, :W] . b_final
+  LY_TE0F,   // (transient_encoding.0[:, :W] . xyz_encoding_final) on h8, likewise
   LY_COUNT
 };
 
@@ -55,6 +58,7 @@ DFN_HD constexpr LayerShape layer_shape(int id, int W = kWidth) {
        : id == LY_TE0 ? LayerShape{W / 2, W / 64}
        : id <= LY_TE3 ? LayerShape{W / 4, W / 64}
        : id == LY_THEAD ? LayerShape{W / 4, 1}
+       : id == LY_DIRF || id == LY_TE0F ? LayerShape{W / 2, W / 64}
        : LayerShape{W / 2, 1};  // LY_SIG
 }
 
@@ -62,6 +66,11 @@ DFN_HD constexpr LayerShape layer_shape(int id, int W = kWidth) {
 constexpr int kCoarseSeq[] = {LY_L1, LY_L2, LY_L3, LY_L4, LY_L5, LY_L6, LY_L7, LY_L8, LY_SIG};
 constexpr int kFineSeq[] = {LY_L1, LY_L2, LY_L3, LY_L4, LY_L5, LY_L6, LY_L7, LY_L8, LY_FIN,
                             LY_DIR, LY_RGB, LY_TE0, LY_TE1, LY_TE2, LY_TE3, LY_THEAD};
+// Kernel variant 5: xyz_encoding_final has no activation and feeds only dir_encoding.0 and transient_encoding.0, so the packer
+// multiplies it into them (LY_DIRF, LY_TE0F) and the kernel never forms `final`; static_sigma reads h8 as its own head block.
+constexpr int kFineFoldSeq[] = {LY_L1, LY_L2, LY_L3, LY_L4, LY_L5, LY_L6, LY_L7, LY_L8, LY_SIG,
+                                LY_DIRF, LY_RGB, LY_TE0F, LY_TE1, LY_TE2, LY_TE3, LY_THEAD};
+static_assert(sizeof(kFineFoldSeq) == sizeof(kFineSeq), "the folded sequence has the layer count of the plain one");
 // Staging-unit group of each layer when a unit may hold whole layers (unit_mb >= 8): small layers share a unit.
 constexpr int kCoarseGroup[] = {0, 1, 2, 3, 4, 5, 6, 7, 7};
 constexpr int kFineGroup[] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 10, 10, 10, 10, 10};
@@ -129,7 +138,11 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //   variant 3: variant 0's geometry without the pipelined epilogue (A/B reference)
 //   variant 2: 4 waves per workgroup x 3 point blocks, 1 workgroup per CU (1 wave per SIMD, 512 VGPRs), unit as variant 0
 //   variant 4: split-f16 as variant 0 on 16x16x32 MFMAs (PrecX3M16); f16 and exact fp32 run their variant-0 kernels
-constexpr int kVariants = 5;
+//   variant 5: variant 4 with the split-f16 FINE RENDER kernel's tail folded (kFineFoldSeq, nerfh_mlp_fold.hip: 1 968 MFMAs
+//              per 32-point tile instead of 2 160); the coarse kernel and every other arithmetic mode, width and gradient path run
+//              variant 4's kernels on variant 4's weights
+constexpr int kVariants = 6;
+constexpr int kFoldVariant = 5;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));
 }

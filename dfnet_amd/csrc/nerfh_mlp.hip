@@ -36,6 +36,14 @@ constexpr bool kMapsTU = true;
 constexpr bool kMapsTU = false;
 #define DFN_LAUNCH_MLP launch_mlp
 #endif
+// Kernel variant 5 (nerfh_layout.h: kFineFoldSeq) is a third translation unit, nerfh_mlp_fold.hip, for the same reason: it includes
+// this file with DFN_MLP_FOLD_TU defined and gets launch_mlp_fold and the fine kernel under the name nerfh_fine_fold_kernel (plain and
+// MAPS) with the folded tail below; what the other two units compile does not change by a token.
+#ifdef DFN_MLP_FOLD_TU
+#define DFN_FINE_KERNEL nerfh_fine_fold_kernel
+#else
+#define DFN_FINE_KERNEL nerfh_fine_kernel
+#endif
 
 // Head activations per arithmetic mode: f16 = hardware transcendentals (1e-6), split-f16 = the fp32-grade hardware forms
 // (exp_hw / rcp_nr, 1.5e-7: nerfh_device.h), exact fp32 = libm.
@@ -128,7 +136,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 // MAPS: the render-maps flavour of the fused compositing epilogue (dfn_render_*_maps): the segment record grows from 12 to
 // kMapsRecFloats floats by the static-only and the transient colour sums.  Its own instantiation: the kernels without it are unchanged.
 template <class P, bool FAST, int WAVES, int UMB, int NB, bool PIPE, int W = kWidth, bool MASKS = false, bool MAPS = false>
-__global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) void nerfh_fine_kernel(MlpArgs a) {
+__global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) void DFN_FINE_KERNEL(MlpArgs a) {
   static_assert(!MASKS || (P::kSplit && !P::kM16 && NB == 1 && WAVES == 8 && W == kWidth), "the sign masks follow the gradient kernel's tile geometry");
   static_assert(!MAPS || (!MASKS && W == kWidth && NB <= 2), "the maps flavour exists where the fused compositing does");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -243,10 +251,24 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     };
     if constexpr (MASKS) trunk<P, UMB, PIPE, FAST, NB, W>(st, smem, x, hid, carry, sign128);
     else trunk<P, UMB, PIPE, FAST, NB, W>(st, smem, x, hid, carry);
+    f32x16 head[NB];
+#ifdef DFN_MLP_FOLD_TU
+    // static_sigma alone on h8, as the coarse kernel's last layer: it completes h8 (the carry-in of layer 8's last M-block) on the way.
+    // `final` is never formed: dir_encoding.0 and transient_encoding.0 below read h8 through the folded weights (LY_DIRF, LY_TE0F)
+    // and the per-ray seeds that carry W[:, :128] . b_final.  The carry-in and the head M-block sit where they sit in the coarse
+    // kernel, and dir_encoding.0 follows a head M-block as it follows xyz_encoding_final's: the read-hazard rules of layer() hold
+    // for this sequence by the same counts.
+    static_assert(P::kM16 && !MASKS && W == kWidth, "the folded tail exists for the split-f16 16x16x32 render kernel");
+    F (&fin)[NB][HC] = hid;
+    {
+      F dummy[NB][chunks_of<P>(16)];
+      layer<P, UMB, PIPE, NB, HC, 0, false, true, false, true, (CY ? 6 : -1), true, false>(st, smem, hid, dummy, head, norb, carry);
+    }
+#else
     // xyz_encoding_final (no activation) + static_sigma
     F fin[NB][HC];
-    f32x16 head[NB];
     layer<P, UMB, PIPE, NB, HC, MBW, false, true, false, true, (CY ? 6 : -1), true, false>(st, smem, hid, fin, head, norb, carry);
+#endif
     sign128(7, hid[0]);   // layer 8's output, completed inside the layer above
     float o[NB][9];
 #pragma unroll
@@ -426,6 +448,36 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 }
 
 // ------------------------------------------------------------------------------------------
+#ifdef DFN_MLP_FOLD_TU
+// variant 5's fine kernel: variant 4's geometry (launch_one<PrecX3M16, false, 8, 2, 1, 1, true> below), plain or render-maps flavour
+hipError_t launch_mlp_fold(bool maps, const MlpArgs& a, int n_cu, hipStream_t stream) {
+  using P = PrecX3M16;
+  constexpr int WAVES = 8, UMB = unit_mb<P>(0), NB = 1, PPT = WAVES * NB * 32;
+  const long long n_pts = (long long)a.n_rays * a.n_samples;
+  if (n_pts <= 0) return hipSuccess;
+  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
+  if (a.masks || (maps && !a.partial)) return hipErrorInvalidValue;
+  const long long n_tiles = (n_pts + PPT - 1) / PPT;
+  const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
+  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB>();
+  void (*kern)(MlpArgs) = maps ? nerfh_fine_fold_kernel<P, false, WAVES, UMB, NB, true, kWidth, false, true>
+                               : nerfh_fine_fold_kernel<P, false, WAVES, UMB, NB, true>;
+  static bool attr_done[2] = {false, false};
+  if (!attr_done[maps]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    if (e != hipSuccess) return e;
+    attr_done[maps] = true;
+  }
+  MlpArgs b = a;
+  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid, as launch_mlp
+    static int env = -1;
+    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
+    b.dma_waves = env > 0 ? env : 4;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
+  return hipGetLastError();
+}
+#else
 template <class P, bool FAST, int WAVES, int UMB, int NB, int WG_PER_CU, bool PIPE, int W = kWidth>
 static hipError_t launch_one(bool fine, const MlpArgs& a, int n_cu, hipStream_t stream) {
   constexpr int PPT = WAVES * NB * 32;
@@ -502,5 +554,6 @@ hipError_t DFN_LAUNCH_MLP(bool fine, int prec, int variant, const MlpArgs& a, in
   if (variant == 1) return launch_one<PrecF32, false, 4, 1, 1, 1, false>(fine, a, n_cu, stream);
   return launch_one<PrecF32, false, 8, 1, 1, 1, false>(fine, a, n_cu, stream);
 }
+#endif  // DFN_MLP_FOLD_TU
 
 }  // namespace dfn
