@@ -112,10 +112,10 @@ static void free_packed(dfn_nerfh_s* h) {
         if (n.tab) (void)hipFree(n.tab);
         n = PackedNet();
       }
-  for (auto& n : h->bwd) {
-    if (n.blob) (void)hipFree(n.blob);
-    if (n.tab) (void)hipFree(n.tab);
-    n = PackedNet();
+  for (PackedNet* n : {&h->bwd[0], &h->bwd[1], &h->bwd[2], &h->half_maps}) {
+    if (n->blob) (void)hipFree(n->blob);
+    if (n->tab) (void)hipFree(n->tab);
+    *n = PackedNet();
   }
   if (h->extra) (void)hipFree(h->extra);
   h->extra = nullptr;
@@ -167,6 +167,10 @@ struct Packer {
   // kernel variant 5 (kFineFoldSeq): dir_encoding.0[:, :W] . xyz_encoding_final and transient_encoding.0[:, :W] . xyz_encoding_final,
   // row-major [W / 2][W] (fold_final)
   std::vector<float> fold_dir, fold_tr;
+  // kernel variant 6 (PrecX3M16): head M-blocks packed half-height, the fragments of their 16-row half ms = 0 only (head_row_m16 puts
+  // head values c = 0..3 there): static_sigma and static_rgb; the transient head too where transient_beta (c = 4) is not wanted
+  bool half_heads = false, half_thead = false;
+  bool half_block(int layer) const { return half_heads && (layer == LY_SIG || layer == LY_RGB || (layer == LY_THEAD && half_thead)); }
   Mat mat(const std::string& key) const {
     Mat m;
     const auto& w = h->params.at(pre + key + ".weight");
@@ -240,7 +244,9 @@ struct Packer {
     const LayerShape sh = layer_shape(layer, width());
     const int KC = sh.slots / P::kSlotsPerChunk;
     Elem* frag = reinterpret_cast<Elem*>(base);
-    float* bias = reinterpret_cast<float*>(base + size_t(group) * KC * 64 * P::kLaneBytes);
+    const bool half = P::kM16 && half_block(layer);   // KC / 2 fragments per M-block: kc = 0, 2, .. (ms = 0)
+    const int KCP = half ? KC / 2 : KC;
+    float* bias = reinterpret_cast<float*>(base + size_t(group) * KCP * 64 * P::kLaneBytes);
     for (int g = 0; g < group; ++g) {
       const int mb = mb0 + g;
       if constexpr (P::kM16) {
@@ -253,13 +259,14 @@ struct Packer {
         };
         for (int lane = 0; lane < 64; ++lane)
           for (int kc = 0; kc < KC; ++kc) {
+            if (half && (kc & 1)) continue;
             Mat m;
             int row;
             source(16 * (kc & 1) + (lane & 15), m, row);
             for (int j = 0; j < 8; ++j) {
               const int col = col_source_m16(layer, lane >> 4, 8 * (kc >> 1) + j);
               const float v = (row >= 0 && col >= 0 && col < m.cols) ? m.w[size_t(row) * m.cols + col] : 0.f;
-              Elem* fr = frag + (size_t(g) * KC + kc) * 64 * 16;
+              Elem* fr = frag + (size_t(g) * KCP + (half ? kc >> 1 : kc)) * 64 * 16;
               const Elem hi = Elem(v * wscale);
               fr[lane * 8 + j] = hi;
               fr[512 + lane * 8 + j] = Elem(v * wscale - float(hi));
@@ -395,7 +402,8 @@ struct Packer {
   template <class P>
   uint32_t blocks_bytes(int layer, int group) const {
     const LayerShape sh = layer_shape(layer, width());
-    return uint32_t(group) * (sh.slots / P::kSlotsPerChunk) * 64 * P::kLaneBytes + uint32_t(group) * 128;
+    const bool half = P::kM16 && half_block(layer);
+    return uint32_t(group) * (sh.slots / P::kSlotsPerChunk / (half ? 2 : 1)) * 64 * P::kLaneBytes + uint32_t(group) * 128;
   }
 
   // The packed blob: staging units in execution order.  umb >= 8: a unit holds whole layers and the small
@@ -442,7 +450,7 @@ struct Packer {
       const int lu = (seq[li] == LY_L5 && l5_umb > 0) ? l5_umb : umb;
       for (int mb0 = 0; mb0 < sh.mb; mb0 += lu) {
         const int group = sh.mb - mb0 < lu ? sh.mb - mb0 : lu;
-        const uint32_t bytes = unit_bytes<P>(sh.slots, group);
+        const uint32_t bytes = unit_bytes<P>(sh.slots, group, P::kM16 && half_block(seq[li]));
         const uint32_t off = uint32_t(blob.size());
         blob.resize(off + bytes, 0);
         tab.push_back(off);
@@ -589,10 +597,16 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
   for (int f = 0; f < 2; ++f)
     for (int prec = 0; prec < 3; ++prec)
       for (int var = 0; var < kVariants; ++var) {
-        // variant 5 has one network of its own, the split-f16 fine one; everything else of it is variant 4's (net_of)
-        const bool fold = var == kFoldVariant;
-        if (fold && !(f == 1 && prec == DFN_PREC_F16X3)) continue;
+        // variant 5 has one network of its own, the split-f16 fine one; everything else of it is variant 4's (net_of).  Variant 6 has
+        // three, all split-f16 with half-height head blocks: the coarse one, the folded fine one without transient_beta's half (fused
+        // compositing, no maps) and, in h->half_maps, the folded fine one with it (the maps flavour); the rest is variant 5's
+        const bool half = var == kHalfVariant;
+        const bool fold = var == kFoldVariant || (half && f == 1);
+        if (var == kFoldVariant && !(f == 1 && prec == DFN_PREC_F16X3)) continue;
+        if (half && prec != DFN_PREC_F16X3) continue;
         Packer pk{h, f ? "fine." : "coarse."};
+        pk.half_heads = half;
+        pk.half_thead = half;
         std::vector<uint8_t> blob;
         std::vector<uint32_t> tab;
         PackedNet& n = h->net[f][prec][var];
@@ -620,7 +634,20 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
             fold_final(h->params.at("fine.dir_encoding.0.weight"), Wd / 2, ldd, F, bF, Wd, pk.fold_dir, fold_bd);
             fold_final(h->params.at("fine.transient_encoding.0.weight"), Wd / 2, ldt, F, bF, Wd, pk.fold_tr, fold_bt);
             pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)), true);
-          } else if (var == 4) pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)));
+            if (half) {   // the maps flavour's network: the transient head at full height
+              std::vector<uint8_t> mblob;
+              std::vector<uint32_t> mtab;
+              pk.half_thead = false;
+              pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, mblob, mtab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)), true);
+              PackedNet& m = h->half_maps;
+              m.in_scale = n.in_scale;
+              int rc = upload(mblob.data(), mblob.size(), reinterpret_cast<void**>(&m.blob));
+              if (rc) return rc;
+              rc = upload(mtab.data(), mtab.size() * 4, reinterpret_cast<void**>(&m.tab));
+              if (rc) return rc;
+              m.n_units = int(mtab.size() / 2);
+            }
+          } else if (var == 4 || half) pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)));
           else pk.pack<PrecX3>(f, unit_mb<PrecX3>(var), false, blob, tab, l5_unit_mb_p<PrecX3>(unit_mb<PrecX3>(var)));
         }
         int rc = upload(blob.data(), blob.size(), reinterpret_cast<void**>(&n.blob));
@@ -778,24 +805,30 @@ static int check_grad_prec(int prec, const char* fn) {
   return DFN_OK;
 }
 
-// Kernel variant: DFN_MLP_VARIANT=0..5 (A/B aid, see nerfh_layout.h).  Default 5: split-f16 on 16x16x32 MFMAs (f16 / exact fp32 run their
-// variant-0 kernels under it) with the fine render kernel's tail folded (fold_fine, base_variant); DFN_MLP_VARIANT=4 is the same
-// without the fold, DFN_MLP_VARIANT=0 keeps the 32x32x16 split-f16 kernels.
+// Kernel variant: DFN_MLP_VARIANT=0..6 (A/B aid, see nerfh_layout.h).  Default 6: split-f16 on 16x16x32 MFMAs (f16 / exact fp32 run their
+// variant-0 kernels under it) with the fine render kernel's tail folded (fold_fine, base_variant) and half-height head blocks in the
+// render kernels (half_heads); DFN_MLP_VARIANT=5 is the same with full-height head blocks, DFN_MLP_VARIANT=4 also without the fold,
+// DFN_MLP_VARIANT=0 keeps the 32x32x16 split-f16 kernels.
+constexpr int kDefaultVariant = kHalfVariant;
 static int mlp_variant_128();
 static int mlp_variant_of(dfn_nerfh_t h) { return h->desc.width == kWidth ? mlp_variant_128() : 0; }
 static int mlp_variant_128() {
   static int v = -1;
   if (v < 0) {
     const char* e = getenv("DFN_MLP_VARIANT");
-    v = (e && e[0] >= '0' && e[0] < '0' + kVariants) ? e[0] - '0' : kFoldVariant;
+    v = (e && e[0] >= '0' && e[0] < '0' + kVariants) ? e[0] - '0' : kDefaultVariant;
   }
   return v;
 }
 // Variant 5 differs from variant 4 in ONE kernel: the split-f16 netwidth-128 fine render kernel (launch_mlp_fold), which reads its own
 // packed network (net[1][F16X3][5]) and a per-ray table written from rb_fold.  Every other launch under it, the gradient paths' forward
 // recompute included (their backward kernels read the plain table), is variant 4's: base_variant.
-static int base_variant(int var) { return var == kFoldVariant ? 4 : var; }
-static bool fold_fine(int var, int prec) { return var == kFoldVariant && prec == DFN_PREC_F16X3; }
+// Variant 6 is variant 5 except in the split-f16 netwidth-128 render kernels that launch_mlp_half has: the coarse kernel, and the fine
+// kernel where the compositing is fused (plain: net[1][F16X3][6], maps: half_maps; coarse: net[0][F16X3][6]).  Its raw route runs
+// variant 5's fine kernel on variant 5's network, and everything else resolves as under variant 5.
+static int base_variant(int var) { return var == kFoldVariant || var == kHalfVariant ? 4 : var; }
+static bool fold_fine(int var, int prec) { return (var == kFoldVariant || var == kHalfVariant) && prec == DFN_PREC_F16X3; }
+static bool half_heads(int var, int prec) { return var == kHalfVariant && prec == DFN_PREC_F16X3; }
 
 // The handle's range-guard flag (device int): allocated and cleared by dfn_nerfh_commit, which fails loudly when it cannot be —
 // every kernel launch that carries the guard runs on a committed handle.
@@ -823,13 +856,15 @@ extern "C" int dfn_mlp_coarse(dfn_nerfh_t h, int prec, const float* rays_o, cons
   if (int rc = check_net(h, prec, "dfn_mlp_coarse", true)) return rc;
   if (!n_rays) return DFN_OK;
   if (!rays_o || !rays_d || !sigma || Nc < 1) return set_error(DFN_ERR_ARG, "dfn_mlp_coarse: bad argument");
+  const bool half = half_heads(mlp_variant_of(h), prec);
   const int var = base_variant(mlp_variant_of(h));
-  const PackedNet& n = h->net[0][prec][var];
+  const PackedNet& n = h->net[0][prec][half ? kHalfVariant : var];
   MlpArgs a{n.blob, n.tab, n.n_units, rays_o, rays_d, nullptr, nullptr, sigma, nullptr, (long long)n_rays, Nc, near, far, nullptr, n.in_scale,
             h->render_flags & DFN_RENDER_LINDISP};
   a.status = range_flag_of(h);
   ScopedTimer t(0, HS(stream));
-  CHECK_HIP(launch_mlp(false, prec, var, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_coarse");
+  if (half) CHECK_HIP(launch_mlp_half(false, false, a, device_cu_count(), HS(stream)), "dfn_mlp_coarse");
+  else CHECK_HIP(launch_mlp(false, prec, var, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_coarse");
   return DFN_OK;
 }
 
@@ -989,8 +1024,10 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
   const int seg = prec == DFN_PREC_F16 ? 64 : 32;
   const bool fused = !raw_out && Nf % seg == 0 && !(prec == DFN_PREC_F16 && var == 2) && h->desc.width == kWidth;
   const int cprec = (h->render_flags & DFN_RENDER_COARSE_F16) ? DFN_PREC_F16 : prec;   // the coarse pass only places the fine samples
-  const PackedNet& nc = h->net[0][cprec][var];
-  const PackedNet& nf = h->net[1][prec][fold ? kFoldVariant : var];
+  // kernel variant 6: its coarse kernel, and its fine kernel where the compositing is fused (the raw route keeps variant 5's)
+  const bool half_c = half_heads(mlp_variant_of(h), cprec), half_f = half_heads(mlp_variant_of(h), prec) && fused;
+  const PackedNet& nc = h->net[0][cprec][half_c ? kHalfVariant : var];
+  const PackedNet& nf = half_f ? (want_maps ? h->half_maps : h->net[1][prec][kHalfVariant]) : h->net[1][prec][fold ? kFoldVariant : var];
   const int cus = device_cu_count();
   const size_t chunk = chunk_rays(n_rays);
   for (size_t r0 = 0; r0 < n_rays; r0 += chunk) {
@@ -1005,7 +1042,8 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
                  h->render_flags & DFN_RENDER_LINDISP};
       a.status = range_flag_of(h);
       ScopedTimer t(0, s);
-      CHECK_HIP(launch_mlp(false, cprec, var, a, cus, s, h->desc.width), "render: coarse MLP");
+      if (half_c) CHECK_HIP(launch_mlp_half(false, false, a, cus, s), "render: coarse MLP (half-height heads)");
+      else CHECK_HIP(launch_mlp(false, cprec, var, a, cus, s, h->desc.width), "render: coarse MLP");
     }
     {
       ScopedTimer t(DFN_PROF_SAMPLE_FINE, s);
@@ -1020,7 +1058,8 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
       MlpArgs a{nf.blob, nf.tab, nf.n_units, co, cd, w.z, w.bias, raw, fused ? w.partial : nullptr, (long long)n, Nf, 0.f, 0.f, g_timing_buf, nf.in_scale};
       a.status = range_flag_of(h);
       ScopedTimer t(1, s);
-      if (fold) CHECK_HIP(launch_mlp_fold(fused && want_maps, a, cus, s), "render: fine MLP (folded)");
+      if (half_f) CHECK_HIP(launch_mlp_half(true, want_maps, a, cus, s), "render: fine MLP (half-height heads)");
+      else if (fold) CHECK_HIP(launch_mlp_fold(fused && want_maps, a, cus, s), "render: fine MLP (folded)");
       else if (fused && want_maps) CHECK_HIP(launch_mlp_maps(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP (maps)");
       else CHECK_HIP(launch_mlp(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP");
     }

@@ -22,6 +22,7 @@ struct dfn_nerfh_s {
   std::map<std::string, std::vector<float>> params;
   bool committed = false;
   PackedNet net[2][3][dfn::kVariants];  // [coarse/fine][prec][kernel variant]
+  PackedNet half_maps;             // kernel variant 6: the split-f16 fine network of the maps flavour (transient head at full height)
   PackedNet bwd[3];                // [prec] fine forward units + backward (W^T) units of the gradient kernel
                                    // (prec 2: split-f16 forward and backward units)
   float* extra = nullptr;  // w_dir^T | b_dir | w_tr^T | b_tr | emb_a | emb_t | b_dir + W_dir[:, :W] b_final | b_tr + W_tr[:, :W] b_final

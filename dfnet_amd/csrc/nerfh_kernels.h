@@ -37,6 +37,10 @@ hipError_t launch_mlp_maps(bool fine, int prec, int variant, const MlpArgs& a, i
 // Kernel variant 5's fine kernel (nerfh_mlp_fold.hip): split-f16, netwidth 128, the blob packed along kFineFoldSeq and a.ray_bias
 // written from the folded per-ray-bias weights (dfn_nerfh_s::rb_fold).  maps: the render-maps flavour, as launch_mlp_maps.
 hipError_t launch_mlp_fold(bool maps, const MlpArgs& a, int n_cu, hipStream_t stream);
+// Kernel variant 6 (nerfh_mlp_half.hip): variant 5's kernels with half-height head M-blocks, on the networks packed for them
+// (Packer::half_heads).  Coarse (fine = false), or the fine kernel with the compositing fused (a.partial set; maps as above): the
+// plain flavour leaves 0 in the segment record's beta slot.  The raw route stays with launch_mlp_fold.
+hipError_t launch_mlp_half(bool fine, bool maps, const MlpArgs& a, int n_cu, hipStream_t stream);
 
 // --- stages (nerfh_stages.hip)
 // (frames > 1: c2w [frames,3,4], outputs [frames,H,W,3] — one launch for the frames of a mini-batch)

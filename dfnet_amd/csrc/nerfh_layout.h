@@ -141,8 +141,14 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //   variant 5: variant 4 with the split-f16 FINE RENDER kernel's tail folded (kFineFoldSeq, nerfh_mlp_fold.hip: 1 968 MFMAs
 //              per 32-point tile instead of 2 160); the coarse kernel and every other arithmetic mode, width and gradient path run
 //              variant 4's kernels on variant 4's weights
-constexpr int kVariants = 6;
+//   variant 6: variant 5 with HALF-HEIGHT head M-blocks in the split-f16 render kernels (nerfh_mlp_half.hip): a PrecX3M16 head
+//              block keeps its values c = 0..3 on the 16-row half ms = 0 (head_row_m16), so static_sigma, static_rgb and -- where
+//              transient_beta reaches no output: compositing fused, no maps -- the transient head are packed and multiplied as their
+//              ms = 0 fragments only (1 920 / 1 932 MFMAs per fine tile plain / maps, 1 560 per coarse tile instead of 1 584); the
+//              raw route and everything else resolve as under variant 5
+constexpr int kVariants = 7;
 constexpr int kFoldVariant = 5;
+constexpr int kHalfVariant = 6;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));
 }
@@ -154,10 +160,11 @@ constexpr uint32_t kPiece = 1024;  // staging granule: one wave-wide 16-byte LDS
 
 DFN_HD constexpr uint32_t align_piece(uint32_t b) { return (b + kPiece - 1) / kPiece * kPiece; }
 
-// Bytes of one staging unit holding `nmb` M-blocks of a layer with `slots` slots per half.
+// Bytes of one staging unit holding `nmb` M-blocks of a layer with `slots` slots per half.  half: a half-height PrecX3M16 head
+// block (kernel variant 6): the fragments of its 16-row half ms = 0 only; the 128-byte bias block keeps its size.
 template <class P>
-DFN_HD constexpr uint32_t unit_bytes(int slots, int nmb) {
-  return align_piece(uint32_t(nmb) * (slots / P::kSlotsPerChunk) * 64 * P::kLaneBytes + uint32_t(nmb) * 2 * 16 * 4);
+DFN_HD constexpr uint32_t unit_bytes(int slots, int nmb, bool half = false) {
+  return align_piece(uint32_t(nmb) * (slots / P::kSlotsPerChunk / (half ? 2 : 1)) * 64 * P::kLaneBytes + uint32_t(nmb) * 2 * 16 * 4);
 }
 // Largest unit of either network when at most `umb` M-blocks go into one unit (sizes the two LDS
 // staging buffers): the widest layers are L5 (96 slots, 4 M-blocks) and FIN (64 slots, 5 M-blocks).

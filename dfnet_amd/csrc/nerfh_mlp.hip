@@ -39,10 +39,22 @@ constexpr bool kMapsTU = false;
 // Kernel variant 5 (nerfh_layout.h: kFineFoldSeq) is a third translation unit, nerfh_mlp_fold.hip, for the same reason: it includes
 // this file with DFN_MLP_FOLD_TU defined and gets launch_mlp_fold and the fine kernel under the name nerfh_fine_fold_kernel (plain and
 // MAPS) with the folded tail below; what the other two units compile does not change by a token.
+// Kernel variant 6 (half-height head M-blocks: layer<..., HALF>) is a fourth one, nerfh_mlp_half.hip: DFN_MLP_HALF_TU on top of
+// DFN_MLP_FOLD_TU.  It gets launch_mlp_half, the folded fine kernel as nerfh_fine_half_kernel (fused compositing only, plain and MAPS)
+// and the coarse kernel as nerfh_coarse_half_kernel; in the other three units kHalfHeads is false and every layer<> below names the
+// instantiation it named before.
+#ifdef DFN_MLP_HALF_TU
+#define DFN_FINE_KERNEL nerfh_fine_half_kernel
+#define DFN_COARSE_KERNEL nerfh_coarse_half_kernel
+constexpr bool kHalfHeads = true;
+#else
 #ifdef DFN_MLP_FOLD_TU
 #define DFN_FINE_KERNEL nerfh_fine_fold_kernel
 #else
 #define DFN_FINE_KERNEL nerfh_fine_kernel
+#endif
+#define DFN_COARSE_KERNEL nerfh_coarse_kernel
+constexpr bool kHalfHeads = false;
 #endif
 
 // Head activations per arithmetic mode: f16 = hardware transcendentals (1e-6), split-f16 = the fp32-grade hardware forms
@@ -68,7 +80,7 @@ template <class P, int WAVES, int NB, int W> constexpr int mlp_min_blocks() {
 
 // ------------------------------------------------------------------------------------------
 template <class P, bool FAST, int WAVES, int UMB, int NB, bool PIPE, int W = kWidth>
-__global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) void nerfh_coarse_kernel(MlpArgs a) {
+__global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) void DFN_COARSE_KERNEL(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int PPT = WAVES * NB * 32;
   using F = typename FragOf<P>::type;
@@ -122,7 +134,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     f32x16 head[NB];
     F dummy[NB][chunks_of<P>(16)];
     const float* const norb[LP] = {};
-    layer<P, UMB, PIPE, NB, chunks_of<P>(W / 2), 0, false, true, false, !MERGE, (CY ? 6 : -1), true, false>(st, smem, hid, dummy, head, norb, carry);
+    layer<P, UMB, PIPE, NB, chunks_of<P>(W / 2), 0, false, true, false, !MERGE, (CY ? 6 : -1), true, false, false, false, true, kHalfHeads>(st, smem, hid, dummy, head, norb, carry);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
       if (h == 0 && pt[nb] < npts) a.out[pt[nb]] = head_softplus<P, FAST>(head[nb][0]);
@@ -146,6 +158,9 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   constexpr uint32_t USTRIDE = max_unit_bytes<P>(UMB, W);
   constexpr int PF_ROUNDS = (NB * 32 + 63) / 64;  // 64-point rounds of the next-tile input prefetch
   constexpr int LP = lane_pts<P>(NB);             // points whose inputs a lane carries (PrecX3M16: 16 n + (lane & 15), n = 0, 1)
+  // kernel variant 6, compositing fused and no maps: transient_beta (head value 4, on half 1 of the transient head block) reaches no
+  // output -- composite_combine_kernel does not read the record's beta slot -- so the block is half-height too and the slot holds 0
+  constexpr bool NOBETA = kHalfHeads && !MAPS;
   using F = typename FragOf<P>::type;
   Stager st;
   st.blob = a.blob; st.tab = a.tab; st.n_units = a.n_units; st.u = 0;
@@ -262,7 +277,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     F (&fin)[NB][HC] = hid;
     {
       F dummy[NB][chunks_of<P>(16)];
-      layer<P, UMB, PIPE, NB, HC, 0, false, true, false, true, (CY ? 6 : -1), true, false>(st, smem, hid, dummy, head, norb, carry);
+      layer<P, UMB, PIPE, NB, HC, 0, false, true, false, true, (CY ? 6 : -1), true, false, false, false, true, kHalfHeads>(st, smem, hid, dummy, head, norb, carry);
     }
 #else
     // xyz_encoding_final (no activation) + static_sigma
@@ -279,7 +294,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       const float* rb_dir[LP];
       ray_table(rb_dir, 0);
       layer<P, UMB, PIPE, NB, HC, MBQ, true, false, true, true, -1, true, CY>(st, smem, fin, de, head, rb_dir, carry);
-      layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE, (CY ? 2 : -1), true, false>(st, smem, de, dummy, head, norb, carry);
+      layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE, (CY ? 2 : -1), true, false, false, false, true, kHalfHeads>(st, smem, de, dummy, head, norb, carry);
       sign64(16, de[0]);
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
@@ -318,14 +333,15 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       sign64(18, t1[0]);
       layer<P, UMB, PIPE, NB, QC, MBQ, true, false, false, !MERGE, (CY ? 2 : -1), true, CY>(st, smem, t0, t1, head, norb, carry);
       sign64(19, t0[0]);
-      layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE, (CY ? 2 : -1), true, false>(st, smem, t1, dummy, head, norb, carry);
+      layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE, (CY ? 2 : -1), true, false, false, false, true, NOBETA>(st, smem, t1, dummy, head, norb, carry);
       sign64(20, t1[0]);
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[nb][4 + c] = head_sigmoid<P, FAST>(head[nb][c]);
         o[nb][7] = head_softplus<P, FAST>(head[nb][3]);
-        o[nb][8] = head_softplus<P, FAST>(head[nb][4]);  // C register 4 of half 0 = row 8 = transient_beta
+        if constexpr (NOBETA) o[nb][8] = 0.f;
+        else o[nb][8] = head_softplus<P, FAST>(head[nb][4]);  // C register 4 of half 0 = row 8 = transient_beta
       }
     }
     // the lane's own sample (sample p on lane p of half 0, as the heads): PrecX3M16 lane 16 g + (l & 15) carries it as point n = g & 1
@@ -371,7 +387,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
         s_acc += wj;
         s_dso += as * Ts * z_own[nb];
         s_dj += wj * z_own[nb];
-        s_beta += live ? wt * o[nb][8] : 0.f;
+        if constexpr (!NOBETA) s_beta += live ? wt * o[nb][8] : 0.f;
         if constexpr (MAPS) {
           // rendering.py:218-227 (the static field under its own transmittance), :201-203 (the transient layer under the joint one).
           // The transient weight goes through an opaque copy: its products must not be shared with s_rgb's, whose rounding
@@ -391,7 +407,8 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #pragma unroll
       for (int c = 0; c < 3; ++c) s_rgb[c] = read_lane31(scan32_sum(s_rgb[c]));   // lanes 32..63 contribute zeros
       s_acc = read_lane31(scan32_sum(s_acc)); s_dso = read_lane31(scan32_sum(s_dso));
-      s_dj = read_lane31(scan32_sum(s_dj)); s_beta = read_lane31(scan32_sum(s_beta));
+      s_dj = read_lane31(scan32_sum(s_dj));
+      if constexpr (!NOBETA) s_beta = read_lane31(scan32_sum(s_beta));
       if constexpr (MAPS) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) { s_rs[c] = read_lane31(scan32_sum(s_rs[c])); s_rt[c] = read_lane31(scan32_sum(s_rt[c])); }
@@ -448,7 +465,39 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 }
 
 // ------------------------------------------------------------------------------------------
-#ifdef DFN_MLP_FOLD_TU
+#if defined(DFN_MLP_HALF_TU)
+// variant 6's kernels: variant 4's geometry (launch_one<PrecX3M16, false, 8, 2, 1, 1, true> below).  coarse; fine with the compositing
+// fused, plain or render-maps flavour -- the raw route (a.partial == nullptr) stays with launch_mlp_fold.
+hipError_t launch_mlp_half(bool fine, bool maps, const MlpArgs& a, int n_cu, hipStream_t stream) {
+  using P = PrecX3M16;
+  constexpr int WAVES = 8, UMB = unit_mb<P>(0), NB = 1, PPT = WAVES * NB * 32;
+  const long long n_pts = (long long)a.n_rays * a.n_samples;
+  if (n_pts <= 0) return hipSuccess;
+  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
+  if (a.masks || (fine && !a.partial) || (maps && !fine)) return hipErrorInvalidValue;
+  const long long n_tiles = (n_pts + PPT - 1) / PPT;
+  const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
+  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB>();
+  const int slot = fine ? (maps ? 2 : 1) : 0;
+  void (*kern)(MlpArgs) = !fine ? nerfh_coarse_half_kernel<P, false, WAVES, UMB, NB, true>
+                          : maps ? nerfh_fine_half_kernel<P, false, WAVES, UMB, NB, true, kWidth, false, true>
+                                 : nerfh_fine_half_kernel<P, false, WAVES, UMB, NB, true>;
+  static bool attr_done[3] = {false, false, false};
+  if (!attr_done[slot]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    if (e != hipSuccess) return e;
+    attr_done[slot] = true;
+  }
+  MlpArgs b = a;
+  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid, as launch_mlp
+    static int env = -1;
+    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
+    b.dma_waves = env > 0 ? env : 4;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
+  return hipGetLastError();
+}
+#elif defined(DFN_MLP_FOLD_TU)
 // variant 5's fine kernel: variant 4's geometry (launch_one<PrecX3M16, false, 8, 2, 1, 1, true> below), plain or render-maps flavour
 hipError_t launch_mlp_fold(bool maps, const MlpArgs& a, int n_cu, hipStream_t stream) {
   using P = PrecX3M16;

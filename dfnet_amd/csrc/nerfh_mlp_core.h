@@ -434,8 +434,12 @@ struct X3Piece {
 // kernels' unit weight scale — the gradient kernels keep the 2^10 scale and per-point renormalisation factors (Stager::lane_mul).
 // TRACK = false: the range guard does not watch this layer's conversions (the caller checks the finished operand itself: the gradient
 // kernel's renormalisation already takes the maximum |hi| of it, renorm_factor).
+// HALF (PrecX3M16, a layer that is ONE head M-block: kernel variant 6): the block's head values c = 0..3 sit on its 16-row half
+// ms = 0 (head_row_m16) and nothing of half 1 is read, so the unit holds and the loop runs the KC / 2 fragments with ms = 0 only (live
+// chunk kl = the 32-K chunk k32 = kl); head[] values c >= 4 come back as zeros.  The carried-in M-block is then converted inside
+// KC / 2 - 1 live chunks: see the hazard counts at the chunk body.
 template <class P, int UMB, bool PIPE, int NB, int KC, int MB, bool RELU, bool EXTRA, bool RAYBIAS, bool NEWUNIT,
-          int CIN, bool CIN_RELU, bool COUT, bool NOBIAS = false, bool SCALE_FIRST = false, bool TRACK = true>
+          int CIN, bool CIN_RELU, bool COUT, bool NOBIAS = false, bool SCALE_FIRST = false, bool TRACK = true, bool HALF = false>
 DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][KC],
                    typename FragOf<P>::type (&Bout)[NB][(MB ? MB : 1) * chunks_of<P>(16)],
                    f32x16 (&head)[NB], const float* const (&raybias)[lane_pts<P>(NB)], f32x16 (&carry)[NB]) {
@@ -449,6 +453,11 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
   static_assert(CIN < 0 || (PIPE && P::kSlotsPerChunk == 8 && CIN > 0 && CIN + 1 < KC + 1), "carry-in needs the pipelined f16 path");
   static_assert(!COUT || (PIPE && MB >= 1 && !EXTRA), "carry-out needs a regular last M-block");
   static_assert(NEWUNIT || UMB >= TOT, "a layer that continues a unit must fit in it");
+  static_assert(!HALF || (P::kM16 && EXTRA && MB == 0 && !RAYBIAS && KC % 2 == 0 && CIN >= 2 && CIN % 2 == 0 && CIN + 2 == KC),
+                "a half-height block is a PrecX3M16 head layer whose last 32-K chunk is the carried-in M-block");
+  constexpr int KCL = HALF ? KC / 2 : KC;      // fragments (chunks of the loop) per M-block
+  constexpr int CINL = HALF ? CIN / 2 : CIN;   // chunks that precede the first reader of the carried-in M-block
+  constexpr bool TAILBLK = HALF && CINL == 1;  // K = 64 half-height heads: one live chunk precedes the reader (see the chunk body)
   const int h = st.lane >> 5, g16 = st.lane >> 4;   // g16: lane group of the 16x16 fragments (PrecX3M16)
   uint32_t rmax_sink = 0;
   uint32_t& rmax_ = TRACK ? st.rmax : rmax_sink;
@@ -471,14 +480,14 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
 #pragma unroll
   for (int u0 = 0; u0 < TOT; u0 += UMB) {
     const int nmb = (TOT - u0) < UMB ? (TOT - u0) : UMB;  // M-blocks in this unit (compile-time after unrolling)
-    const int nt = nmb * KC;
+    const int nt = nmb * KCL;
     uint32_t ub;
     if (NEWUNIT) { ub = open_unit(st); st.ubase = ub; st.uoff = 0; }
     else ub = st.ubase + st.uoff;
-    st.uoff += nmb * KC * FB + nmb * 128;
+    st.uoff += nmb * KCL * FB + nmb * 128;
     // split-f16 fragment = a hi plane (64 lanes x 16 B) followed by a lo plane: both reads stay lane-linear 16-byte
     const char* wl = smem + ub + st.lane * (P::kSplit ? 16 : P::kLaneBytes);
-    const char* bl = smem + ub + nmb * KC * FB + (P::kM16 ? g16 * 32 : h * 64);
+    const char* bl = smem + ub + nmb * KCL * FB + (P::kM16 ? g16 * 32 : h * 64);
     F a[PF];
 #define DFN_AFRAG(t) load_afrag<P>(wl + (t) * FB)
 #pragma unroll
@@ -495,6 +504,10 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
       if (lm < nmb) {
         const int mb = u0 + lm;
         f32x16 acc[NB];
+        if constexpr (HALF) {   // registers 8..15 (half 1) are never written
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb) acc[nb] = f32x16{};
+        }
         f32x16 bias_next = bias;
         if (RAYBIAS) {
 #pragma unroll
@@ -505,19 +518,20 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
           }
         }
 #pragma unroll
-        for (int kc = 0; kc < KC; ++kc) {
-          const int t = lm * KC + kc;
-          if (NEWUNIT && lm == 0 && kc == (KC > 1 ? KC / 2 : 0)) mid_sync(st, smem);
+        for (int kc = 0; kc < KCL; ++kc) {
+          const int t = lm * KCL + kc;
+          if (NEWUNIT && lm == 0 && kc == (KCL > 1 ? KCL / 2 : 0)) mid_sync(st, smem);
           const F cur = a[t % PF];
           if (t + PF < nt) a[t % PF] = DFN_AFRAG(t + PF);
-          if (kc == (PIPE ? KC / 2 : 0) && !RAYBIAS && !NOBIAS && lm + 1 < nmb) bias_next = load_bias(bl + (lm + 1) * 128);
+          if (kc == (PIPE ? KCL / 2 : 0) && !RAYBIAS && !NOBIAS && lm + 1 < nmb) bias_next = load_bias(bl + (lm + 1) * 128);
           __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ABOVE this chunk's MFMAs (hipcc otherwise sinks it to its use)
           if constexpr (P::kSplit && PIPE && NB == 1 && !SCALE_FIRST) {
             // split-f16: the conversion pieces of this chunk go BETWEEN its three dependent MFMAs, a third each (the block form
             // behind them measured 46.5 against 42.7 cycles per MFMA in tools/ubench/x3loop.hip)
-            constexpr int PPKI_ = (CIN > 0) ? (8 * NB + CIN - 1) / CIN : 1, PPK_ = (8 * NB + KC - 1) / KC;
+            constexpr int PPKI_ = TAILBLK ? 4 : ((CIN > 0) ? (8 * NB + CINL - 1) / CINL : 1), PPK_ = (8 * NB + KCL - 1) / KCL;
             constexpr int NPMAX = PPKI_ > PPK_ ? PPKI_ : PPK_;
-            const bool from_carry = CIN > 0 && mb == 0 && kc < CIN, from_pend = mb >= 1;
+            static_assert(!HALF || NPMAX <= 4, "half 1's pieces must not start in the first chunk");
+            const bool from_carry = CIN > 0 && mb == 0 && kc < CINL, from_pend = mb >= 1;
             const int np = from_carry ? PPKI_ : (from_pend ? PPK_ : 0), base = kc * np;
             X3Piece pc[NPMAX];
             // kc == 0: the accumulators the pieces read (pend / carry) were written by the MFMA issued just before this chunk; an
@@ -542,9 +556,25 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
               // half ms = i >> 2, last written in chunk KC - 2 + ms of the previous M-block (layer), and half 1's pieces start at chunk
               // 8 / (2 np) >= 1 (np <= 4 pieces per chunk): >= 8 MFMA issues lie between producer and reader in every chunk, the first
               // one included (the 32x32 path's `late` rule holds by construction).
-              const int ms = kc & 1, bc = 2 * (kc >> 1);
+              // HALF: live chunk kl = (k32 = kl, ms = 0); the producer of the carried-in M-block is unchanged (half ms last written in
+              // chunk KC - 2 + ms of the layer before), only the readers move.
+              //   K = 128 (static_sigma: 4 live chunks, the carried-in chunk is read by the 4th): 8 pieces over live chunks 0..2 = 3 per
+              //   chunk (np = 3 <= 4).  Pieces 0..2 (half 0) in live chunk 0: part A sits behind 6 (producer layer's last chunk) + 2
+              //   = 8 MFMA issues after half 0's last write.  Half 1's first pieces 4, 5 are in live chunk 1 = 4 / 3: part A behind
+              //   6 (live chunk 0) + 2 = 8 MFMA issues after the producer layer's last MFMA.  The count of the full-height form holds.
+              //   K = 64 (static_rgb, transient head: 2 live chunks, the 2nd reads the carried-in chunk; TAILBLK): pieces 0..3 (half 0) go
+              //   into live chunk 0's gaps exactly as in the full-height form (8 issues).  No gap with 8 MFMA issues behind half 1's
+              //   producer exists before the reader, so pieces 4..7 are converted in the BLOCK form behind live chunk 0's last MFMA,
+              //   with explicit wait states: 6 MFMA issues + s_nop 7 (8 states) = 14 >= the 12 wait states an 8-pass XDL result needs
+              //   before a VALU read, counting each MFMA issue as ONE state (an issue behind an 8-pass MFMA takes >= 8 passes, and the
+              //   36 VALU instructions of pieces 0..3 lie in between as well).  The same parts in the same arithmetic: same bits.
+              //   These are counts in SOURCE order.  hipcc keeps the asm pieces in order among themselves but may place a chunk's
+              //   first two MFMAs behind its part A (it does for bias-seeded chunks, in the full-height kernels too), which takes 2 off
+              //   a count; in the generated code of the three half-height kernels the shortest distance from an accumulator's last
+              //   write to the piece that reads it is 6 MFMA issues, the full-height folded kernel's own minimum (LABBOOK R12.1).
+              const int ms = HALF ? 0 : (kc & 1), bc = HALF ? 2 * kc : 2 * (kc >> 1);
               f32x4 c0, c1;
-              if (kc < 2 && !RAYBIAS) { c0 = sub4(bias, 4 * ms); c1 = c0; }
+              if (kc < (HALF ? 1 : 2) && !RAYBIAS) { c0 = sub4(bias, 4 * ms); c1 = c0; }
               else { c0 = sub4(acc[0], 8 * ms); c1 = sub4(acc[0], 8 * ms + 4); }
 #define DFN_X3_PARTS(...) \
               _Pragma("unroll") for (int q = 0; q < NPMAX; ++q) \
@@ -571,7 +601,22 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
 #undef DFN_X3_PARTS
               put4(acc[0], 8 * ms, c0);
               put4(acc[0], 8 * ms + 4, c1);
-              if (from_carry && kc == CIN - 1) asm volatile("s_nop 3");
+              if constexpr (TAILBLK) {
+                if (from_carry) {   // pieces 4..7 (half 1 of the carried-in M-block) in the block form: the counts above
+                  __builtin_amdgcn_sched_barrier(0);
+                  asm volatile("s_nop 7");
+                  X3Piece tp[4];
+#pragma unroll
+                  for (int q = 0; q < 4; ++q) tp[q].template A<CIN_RELU>(carry[0], 4 + q);
+#pragma unroll
+                  for (int q = 0; q < 4; ++q) tp[q].B1(pscale2);
+#pragma unroll
+                  for (int q = 0; q < 4; ++q) tp[q].B2(pscale);
+#pragma unroll
+                  for (int q = 0; q < 4; ++q) tp[q].template C<CIN_RELU, P>(Bin[0], CIN / 2, 4 + q, rmax_);
+                }
+              }
+              if (from_carry && kc == CINL - 1) asm volatile("s_nop 3");
               __builtin_amdgcn_sched_barrier(0);
               continue;
             }
@@ -642,7 +687,10 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
               const f32x16 v = head[nb];
               const bool g1 = (g16 & 1) != 0;
 #pragma unroll
-              for (int c = 0; c < 8; ++c) head[nb][c] = g1 ? v[8 * (c >> 2) + 4 + (c & 3)] : v[8 * (c >> 2) + (c & 3)];
+              for (int c = 0; c < 8; ++c) {
+                if (HALF && c >= 4) head[nb][c] = 0.f;   // half 1 was not computed (fragments q = nb only)
+                else head[nb][c] = g1 ? v[8 * (c >> 2) + 4 + (c & 3)] : v[8 * (c >> 2) + (c & 3)];
+              }
             }
           }
         }

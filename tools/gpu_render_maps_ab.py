@@ -11,8 +11,9 @@ the two flavours of the fine kernel.
                    the line carries the figure without it ("median_without_z_recompute_ms")
     and the per-launch averages of the fine kernel and the segment combine in both flavours (dfn_profile_read).
   python tools/gpu_render_maps_ab.py --registers   no GPU: VGPR / SGPR / scratch / code bytes of every nerfh_fine_kernel instantiation in
-                                                dfnet_amd/csrc/build/nerfh_mlp.o, nerfh_mlp_maps.o and nerfh_mlp_fold.o (kernel variant 5's
-                                                nerfh_fine_fold_kernel); the last template argument is the maps flavour.
+                                                dfnet_amd/csrc/build/nerfh_mlp.o, nerfh_mlp_maps.o, nerfh_mlp_fold.o (kernel variant 5's
+                                                nerfh_fine_fold_kernel) and nerfh_mlp_half.o (kernel variant 6's nerfh_fine_half_kernel and
+                                                nerfh_coarse_half_kernel); the fine kernels' last template argument is the maps flavour.
   python tools/gpu_render_maps_ab.py --text-sha [nerfh_mlp.o ...]   no GPU: sha256 and size of the .text of each object's gfx950 code
                                                 object (default: this build's nerfh_mlp.o): equal digests of two builds = the same
                                                 instructions at the same offsets for every kernel that runs without maps.
@@ -31,7 +32,7 @@ sys.path.insert(0, ROOT)
 
 
 def registers():
-    for name in ("nerfh_mlp.o", "nerfh_mlp_maps.o", "nerfh_mlp_fold.o"):
+    for name in ("nerfh_mlp.o", "nerfh_mlp_maps.o", "nerfh_mlp_fold.o", "nerfh_mlp_half.o"):
         registers_of(os.path.join(ROOT, "dfnet_amd", "csrc", "build", name))
 
 
@@ -66,7 +67,7 @@ def registers_of(obj):
     for blk in notes.split("- .agpr_count:")[1:]:
         g = lambda k: re.search(r"\." + k + r":\s+(\S+)", blk).group(1)
         name = g("name")
-        if "nerfh_fine_kernel" not in name and "nerfh_fine_fold_kernel" not in name:
+        if not any(k in name for k in ("nerfh_fine_kernel", "nerfh_fine_fold_kernel", "nerfh_fine_half_kernel", "nerfh_coarse_half_kernel")):
             continue
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().replace("dfn::", "")
         print(json.dumps(dict(kernel=dem, vgpr=int(g("vgpr_count")), sgpr=int(g("sgpr_count")), scratch_bytes=int(g("private_segment_fixed_size")),
