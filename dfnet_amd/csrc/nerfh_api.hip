@@ -1210,6 +1210,66 @@ extern "C" int dfn_mlp_fine_backward(dfn_nerfh_t h, int prec, const float* rays_
   return DFN_OK;
 }
 
+// Point queries (nerfw.py:15-95 run_network_NeRFW as network_query_fn calls it, :425-434).  The default kernel variant's kernels whatever
+// DFN_MLP_VARIANT says: split-f16 at netwidth 128 = variant 6's coarse kernel and variant 5's fine kernel (the raw route of dfn_mlp_fine).
+static int check_points(size_t n_rows, int N, const char* fn) {
+  if (N < 1) return set_error(DFN_ERR_ARG, "%s: bad argument (N >= 1)", fn);
+  if (n_rows > ((size_t(1) << 31) - 1) / size_t(N)) return set_error(DFN_ERR_ARG, "%s: n_rows * N must stay below 2^31 (chunk by rows)", fn);
+  return DFN_OK;
+}
+
+extern "C" int dfn_mlp_coarse_points(dfn_nerfh_t h, int prec, const float* pts, size_t n_rows, int N, float* sigma, void* stream) {
+  if (int rc = check_net(h, prec, "dfn_mlp_coarse_points", true)) return rc;
+  if (!n_rows) return DFN_OK;
+  if (!pts || !sigma) return set_error(DFN_ERR_ARG, "dfn_mlp_coarse_points: bad argument");
+  if (int rc = check_points(n_rows, N, "dfn_mlp_coarse_points")) return rc;
+  const bool w128 = h->desc.width == kWidth;
+  const bool half = w128 && half_heads(kDefaultVariant, prec);
+  const PackedNet& n = h->net[0][prec][half ? kHalfVariant : (w128 ? base_variant(kDefaultVariant) : 0)];
+  MlpArgs a{n.blob, n.tab, n.n_units, pts, nullptr, nullptr, nullptr, sigma, nullptr, (long long)n_rows, N, 0.f, 0.f, nullptr, n.in_scale};
+  a.status = range_flag_of(h);
+  if (half) CHECK_HIP(launch_mlp_pts_half(a, device_cu_count(), HS(stream)), "dfn_mlp_coarse_points");
+  else CHECK_HIP(launch_mlp_pts(false, prec, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_coarse_points");
+  return DFN_OK;
+}
+
+extern "C" int dfn_mlp_fine_points(dfn_nerfh_t h, int prec, const float* pts, const float* viewdirs, const float* hist, size_t hist_rows,
+                                   size_t n_rows, int N, float* raw, void* bias_ws, void* stream) {
+  if (int rc = check_net(h, prec, "dfn_mlp_fine_points", true)) return rc;
+  if (!n_rows) return DFN_OK;
+  if (!pts || !viewdirs || !hist || !raw || !bias_ws || (hist_rows != 1 && hist_rows != n_rows))
+    return set_error(DFN_ERR_ARG, "dfn_mlp_fine_points: bad argument (hist_rows must be 1 or n_rows)");
+  if (int rc = check_points(n_rows, N, "dfn_mlp_fine_points")) return rc;
+  float* table = static_cast<float*>(bias_ws);
+  const bool w128 = h->desc.width == kWidth;
+  const bool fold = w128 && fold_fine(kDefaultVariant, prec);
+  CHECK_HIP(launch_ray_bias(fold ? h->rb_fold : h->rb, viewdirs, hist, hist_rows, n_rows, table, HS(stream)), "dfn_mlp_fine_points(ray_bias)");
+  const PackedNet& n = h->net[1][prec][fold ? kFoldVariant : (w128 ? base_variant(kDefaultVariant) : 0)];
+  MlpArgs a{n.blob, n.tab, n.n_units, pts, nullptr, nullptr, table, raw, nullptr, (long long)n_rows, N, 0.f, 0.f, nullptr, n.in_scale};
+  a.status = range_flag_of(h);
+  if (fold) CHECK_HIP(launch_mlp_pts_fold(a, device_cu_count(), HS(stream)), "dfn_mlp_fine_points");
+  else CHECK_HIP(launch_mlp_pts(true, prec, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_fine_points");
+  return DFN_OK;
+}
+
+extern "C" int dfn_mlp_fine_points_backward(dfn_nerfh_t h, int prec, const float* pts, const float* viewdirs, const float* hist,
+                                            size_t hist_rows, size_t n_rows, int N, const float* grad_raw, float* grad_pts, void* bias_ws,
+                                            void* stream) {
+  if (int rc = check_net(h, prec, "dfn_mlp_fine_points_backward", true)) return rc;
+  if (int rc = check_grad_prec(prec, "dfn_mlp_fine_points_backward")) return rc;
+  if (int rc = check_grad_width(h, "dfn_mlp_fine_points_backward")) return rc;
+  if (!n_rows) return DFN_OK;
+  if (!pts || !viewdirs || !hist || !grad_raw || !grad_pts || !bias_ws || (hist_rows != 1 && hist_rows != n_rows))
+    return set_error(DFN_ERR_ARG, "dfn_mlp_fine_points_backward: bad argument (hist_rows must be 1 or n_rows)");
+  if (int rc = check_points(n_rows, N, "dfn_mlp_fine_points_backward")) return rc;
+  float* table = static_cast<float*>(bias_ws);
+  CHECK_HIP(launch_ray_bias(h->rb, viewdirs, hist, hist_rows, n_rows, table, HS(stream)), "dfn_mlp_fine_points_backward(ray_bias)");
+  const PackedNet& n = h->bwd[prec];
+  BwdArgs a{n.blob, n.tab, n.n_units, pts, nullptr, viewdirs, nullptr, table, grad_raw, grad_pts, (long long)n_rows, N, n.in_scale};
+  CHECK_HIP(launch_mlp_fine_backward_pts(prec, a, device_cu_count(), HS(stream)), "dfn_mlp_fine_points_backward");
+  return DFN_OK;
+}
+
 extern "C" size_t dfn_mlp_fine_mask_bytes(size_t n_points) {
   return (n_points + kBwdTilePoints - 1) / kBwdTilePoints * (kBwdTilePoints / 32) * kBwdMaskWords * 64 * sizeof(uint32_t);
 }

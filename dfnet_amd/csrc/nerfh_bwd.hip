@@ -22,6 +22,18 @@
 
 namespace dfn {
 
+// The points flavour (dfn_mlp_fine_points_backward) is compiled in a translation unit of its own: nerfh_bwd_pts.hip includes this file
+// with DFN_BWD_PTS_TU defined and gets the one-pass kernel under the name nerfh_fine_backward_pts_kernel, its inputs loaded from
+// pts [n_rows, n_samples, 3] (BwdArgs::rays_o) instead of being formed as o + d z, and the launcher launch_mlp_fine_backward_pts.
+// What this unit compiles does not change by a token.
+#ifdef DFN_BWD_PTS_TU
+#define DFN_BWD_KERNEL nerfh_fine_backward_pts_kernel
+#define DFN_LAUNCH_BWD launch_mlp_fine_backward_pts
+#else
+#define DFN_BWD_KERNEL nerfh_fine_backward_kernel
+#define DFN_LAUNCH_BWD launch_mlp_fine_backward
+#endif
+
 // Head activations of the forward recompute: split-f16 = the fp32-grade hardware forms of the inference kernel (exp_hw / rcp_nr,
 // 1.5e-7: nerfh_device.h), exact fp32 = libm.
 template <class PF, bool FAST> DFN_DEV float bwd_sigmoid(float v) { return PF::kSplit ? sigmoid_hw(v) : act_sigmoid<FAST>(v); }
@@ -57,7 +69,7 @@ template <class PF, class P> constexpr uint32_t bwd_lds_bytes() { return 3 * bwd
 // tracked forward of an autograd step).  MODE 2: the backward only, from those masks and raw — the head derivatives follow
 // from the head OUTPUTS (sigmoid' = y (1 - y), softplus' = 1 - exp(-y)), so no activation has to be kept or recomputed.
 template <class PF, class P, bool FAST, int WAVES, int UMBF, int UMB, int NB, int MODE = 0>
-__global__ __launch_bounds__(WAVES * 64, 1) void nerfh_fine_backward_kernel(BwdArgs a) {
+__global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int PPT = WAVES * NB * 32;
   constexpr int HC = chunks_of<P>(64), QC = chunks_of<P>(32), PC = chunks_of<P>(32), SC = chunks_of<P>(16);
@@ -95,9 +107,14 @@ __global__ __launch_bounds__(WAVES * 64, 1) void nerfh_fine_backward_kernel(BwdA
       pt[nb] = tile * PPT + st.wave * (NB * 32) + nb * 32 + p;
       const uint32_t q = uint32_t(pt[nb] < n_pts ? pt[nb] : n_pts - 1);
       ray_of[nb] = q / uint32_t(a.n_samples);
+#ifdef DFN_BWD_PTS_TU
+#pragma unroll
+      for (int c = 0; c < 3; ++c) x[nb][c] = a.rays_o[size_t(q) * 3 + c];   // pts [n_rows, n_samples, 3]
+#else
       const float z = a.z[q];
 #pragma unroll
       for (int c = 0; c < 3; ++c) x[nb][c] = add_rn(a.rays_o[ray_of[nb] * 3 + c], mul_rn(a.rays_d[ray_of[nb] * 3 + c], z));
+#endif
 #pragma unroll
       for (int c = 0; c < 9; ++c) g[nb][c] = (MODE != 1 && h == 0 && pt[nb] < n_pts) ? a.graw[size_t(q) * 9 + c] : 0.f;
       rb_dir[nb] = a.ray_bias + size_t(ray_of[nb]) * kRayBiasFloats;
@@ -491,7 +508,7 @@ static hipError_t launch_bwd_one(const BwdArgs& a, int n_cu, hipStream_t stream)
   const long long n_tiles = (n_pts + PPT - 1) / PPT;
   const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
   const uint32_t lds = bwd_lds_bytes<PF, P>();
-  auto kern = nerfh_fine_backward_kernel<PF, P, FAST, WAVES, UMBF, UMB, NB, MODE>;
+  auto kern = DFN_BWD_KERNEL<PF, P, FAST, WAVES, UMBF, UMB, NB, MODE>;
   static bool attr_done = false;
   if (!attr_done) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
@@ -502,13 +519,17 @@ static hipError_t launch_bwd_one(const BwdArgs& a, int n_cu, hipStream_t stream)
   return hipGetLastError();
 }
 
-hipError_t launch_mlp_fine_backward(int prec, const BwdArgs& a, int n_cu, hipStream_t stream, int mode) {
+hipError_t DFN_LAUNCH_BWD(int prec, const BwdArgs& a, int n_cu, hipStream_t stream, int mode) {
+#ifdef DFN_BWD_PTS_TU
+  if (mode || !a.rays_o) return hipErrorInvalidValue;   // the one-pass form only
+#else
   if (mode) {   // two-pass form: split-f16 only (exact gates are its point)
     if (prec != 2) return hipErrorInvalidValue;
     static_assert(kBwdTilePoints == 8 * 32, "tile geometry of the split-f16 gradient kernel");
     return mode == 1 ? launch_bwd_one<PrecX3, PrecX3, false, 8, bwd_fwd_unit_mb<PrecX3>(), bwd_unit_mb<PrecX3>(), 1, 1>(a, n_cu, stream)
                      : launch_bwd_one<PrecX3, PrecX3, false, 8, bwd_fwd_unit_mb<PrecX3>(), bwd_unit_mb<PrecX3>(), 1, 2>(a, n_cu, stream);
   }
+#endif
   // plain f16 gradient arithmetic is not offered: ReLU gates flipped by f16 rounding put it at 3e-2 of autograd (30x the
   // contract); split-f16 runs at the f16 MFMA rate with fp32-grade gates (nerfh_api.hip rejects DFN_PREC_F16 here)
   if (prec == 0) return hipErrorInvalidValue;

@@ -42,6 +42,14 @@ hipError_t launch_mlp_fold(bool maps, const MlpArgs& a, int n_cu, hipStream_t st
 // plain flavour leaves 0 in the segment record's beta slot.  The raw route stays with launch_mlp_fold.
 hipError_t launch_mlp_half(bool fine, bool maps, const MlpArgs& a, int n_cu, hipStream_t stream);
 
+// The points flavour (nerfh_mlp_pts*.hip): a.rays_o is pts [n_rays, n_samples, 3] (n_rays = query rows), a.rays_d, a.z and a.partial
+// are unused (a.partial must be null: the raw route only), a.ray_bias has one row per query row.  launch_mlp_pts: f16 / exact fp32 at
+// netwidth 128 (variant 0's kernels) and netwidth 256; split-f16 at netwidth 128: launch_mlp_pts_half = variant 6's coarse kernel
+// (net[0][F16X3][6]), launch_mlp_pts_fold = variant 5's fine kernel (net[1][F16X3][5], a.ray_bias from rb_fold).
+hipError_t launch_mlp_pts(bool fine, int prec, const MlpArgs& a, int n_cu, hipStream_t stream, int width = 128);
+hipError_t launch_mlp_pts_fold(const MlpArgs& a, int n_cu, hipStream_t stream);
+hipError_t launch_mlp_pts_half(const MlpArgs& a, int n_cu, hipStream_t stream);
+
 // --- stages (nerfh_stages.hip)
 // (frames > 1: c2w [frames,3,4], outputs [frames,H,W,3] — one launch for the frames of a mini-batch)
 hipError_t launch_raygen(int H, int W, float focal, const float* c2w, float* rays_o, float* rays_d,
@@ -118,6 +126,8 @@ struct BwdArgs {
 constexpr int kBwdMaskWords = 21;    // 8 trunk layers x 128 bits, dir_encoding 64, transient_encoding 4 x 64 — per point
 constexpr int kBwdTilePoints = 256;  // points per workgroup tile of the split-f16 gradient kernel (8 waves x 32)
 hipError_t launch_mlp_fine_backward(int prec, const BwdArgs& a, int n_cu, hipStream_t stream, int mode = 0);
+// Its points flavour (nerfh_bwd_pts.hip): a.rays_o is pts [n_rays, n_samples, 3], a.rays_d and a.z are unused; the one-pass form only.
+hipError_t launch_mlp_fine_backward_pts(int prec, const BwdArgs& a, int n_cu, hipStream_t stream, int mode = 0);
 // d L / d raw from d L / d rgb through the fine compositing (test-time, rgb only).  grad_raw_ext [n_rays, Nf, 9] (optional): a
 // gradient that reaches raw directly, added in the same kernel (graw = d raw(compositor) + grad_raw_ext); with grad_rgb == nullptr
 // graw = grad_raw_ext and the scan is skipped.  Without it: the rgb-only kernel, unchanged.

@@ -43,7 +43,26 @@ constexpr bool kMapsTU = false;
 // DFN_MLP_FOLD_TU.  It gets launch_mlp_half, the folded fine kernel as nerfh_fine_half_kernel (fused compositing only, plain and MAPS)
 // and the coarse kernel as nerfh_coarse_half_kernel; in the other three units kHalfHeads is false and every layer<> below names the
 // instantiation it named before.
-#ifdef DFN_MLP_HALF_TU
+// The points flavour (dfn_mlp_coarse_points, dfn_mlp_fine_points: DFN_MLP_PTS_TU, on top of none, DFN_MLP_FOLD_TU or DFN_MLP_HALF_TU) is
+// compiled in three more units, nerfh_mlp_pts.hip, nerfh_mlp_pts_fold.hip and nerfh_mlp_pts_half.hip: the three inputs of a point are
+// loaded from pts [n_rows, n_samples, 3] (MlpArgs::rays_o) instead of being formed as o + d z, and everything behind x[..][3] is the
+// code of the ray flavour.  The kernels carry names of their own (nerfh_*_pts_kernel) and only the raw route exists (no depths, so no
+// compositing); what the other four units compile does not change by a token.
+#if defined(DFN_MLP_PTS_TU)
+#if defined(DFN_MLP_HALF_TU)
+#define DFN_FINE_KERNEL nerfh_fine_half_pts_kernel
+#define DFN_COARSE_KERNEL nerfh_coarse_half_pts_kernel
+constexpr bool kHalfHeads = true;
+#elif defined(DFN_MLP_FOLD_TU)
+#define DFN_FINE_KERNEL nerfh_fine_fold_pts_kernel
+#define DFN_COARSE_KERNEL nerfh_coarse_fold_pts_kernel
+constexpr bool kHalfHeads = false;
+#else
+#define DFN_FINE_KERNEL nerfh_fine_pts_kernel
+#define DFN_COARSE_KERNEL nerfh_coarse_pts_kernel
+constexpr bool kHalfHeads = false;
+#endif
+#elif defined(DFN_MLP_HALF_TU)
 #define DFN_FINE_KERNEL nerfh_fine_half_kernel
 #define DFN_COARSE_KERNEL nerfh_coarse_half_kernel
 constexpr bool kHalfHeads = true;
@@ -120,12 +139,17 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     for (int n = 0; n < LP; ++n) {   // the lane's MLP inputs (PrecX3M16: point 16 n + (lane & 15) of the wave)
       const uint32_t pn = P::kM16 ? uint32_t(tile) * uint32_t(PPT) + st.wave * 32 + 16 * n + (st.lane & 15) : pt[n];
       const uint32_t q = pn < npts ? pn : npts - 1;
+#ifdef DFN_MLP_PTS_TU
+#pragma unroll
+      for (int c = 0; c < 3; ++c) x[n][c] = a.rays_o[size_t(q) * 3 + c];   // pts [n_rows, n_samples, 3]
+#else
       const uint32_t ray = q / uint32_t(a.n_samples);
       const int i = int(q - ray * uint32_t(a.n_samples));
       const float z = coarse_z_at(i, a.n_samples, a.near, a.far, a.lindisp != 0);
 #pragma unroll
       for (int c = 0; c < 3; ++c)
         x[n][c] = add_rn(a.rays_o[ray * 3 + c], mul_rn(a.rays_d[ray * 3 + c], z));
+#endif
     }
     constexpr bool CY = PIPE && P::kSlotsPerChunk == 8, MERGE = UMB >= 8;
     F hid[NB][chunks_of<P>(W / 2)];
@@ -189,7 +213,11 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   // Tile inputs.  The first tile's are loaded normally; every later tile's are PREFETCHED during the
   // previous tile's small layers with direct-to-LDS loads and only
   // waited for at the end of that tile, so the HBM latency of z / o / d is off the critical path.
+#ifdef DFN_MLP_PTS_TU
+  float xin[LP][3];   // the points themselves: pts [n_rows, n_samples, 3] in a.rays_o
+#else
   float zin[LP], znext[LP], oin[LP][3], din[LP][3];
+#endif
   // launch_one() guarantees n_pts < 2^31: point / ray indices are 32-bit (as 64-bit values and as per-ray table POINTERS held
   // across the trunk they cost 16 registers at NB = 2 and the f16 kernel spilled them: any scratch use costs this kernel clock)
   uint32_t pt[LP], ray_of[LP];
@@ -208,10 +236,15 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #pragma unroll
   for (int nb = 0; nb < LP; ++nb) {
     const uint32_t q = pt[nb] < npts ? pt[nb] : npts - 1;
+#ifdef DFN_MLP_PTS_TU
+#pragma unroll
+    for (int c = 0; c < 3; ++c) xin[nb][c] = a.rays_o[size_t(q) * 3 + c];
+#else
     zin[nb] = a.z[q];
     znext[nb] = a.z[q + 1 < npts ? q + 1 : q];
 #pragma unroll
     for (int c = 0; c < 3; ++c) { oin[nb][c] = a.rays_o[ray_of[nb] * 3 + c]; din[nb][c] = a.rays_d[ray_of[nb] * 3 + c]; }
+#endif
   }
   for (; tile < n_tiles; tile += gridDim.x) {
     st.more = tile + gridDim.x < n_tiles;
@@ -222,7 +255,11 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       pt_cur[nb] = pt[nb];
       ray_cur[nb] = ray_of[nb];
 #pragma unroll
+#ifdef DFN_MLP_PTS_TU
+      for (int c = 0; c < 3; ++c) x[nb][c] = xin[nb][c];
+#else
       for (int c = 0; c < 3; ++c) x[nb][c] = add_rn(oin[nb][c], mul_rn(din[nb][c], zin[nb]));
+#endif
     }
     // per-ray table rows: the pointers are formed where they are used (opaque ray index: not hoisted above the trunk)
     auto ray_table = [&](const float* (&rb)[LP], int half_table) {
@@ -317,6 +354,11 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
         for (int r = 0; r < PF_ROUNDS; ++r) {
           const uint32_t ptn = base + r * 64 + st.lane;
           const uint32_t q = ptn < npts ? ptn : npts - 1;
+#ifdef DFN_MLP_PTS_TU
+          // points flavour: the three coordinates of the wave's point 64 r + l (dwords 0..2 of the round's eight)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) lds_dma_b32(a.rays_o + size_t(q) * 3 + c, slot + (r * 8 + c) * 256);
+#else
           const uint32_t ray = q / uint32_t(a.n_samples);
           lds_dma_b32(a.z + q, slot + (r * 8) * 256);
           lds_dma_b32(a.z + (q + 1 < npts ? q + 1 : q), slot + (r * 8 + 7) * 256);
@@ -325,6 +367,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
             lds_dma_b32(a.rays_o + ray * 3 + c, slot + (r * 8 + 1 + c) * 256);
             lds_dma_b32(a.rays_d + ray * 3 + c, slot + (r * 8 + 4 + c) * 256);
           }
+#endif
         }
       }
       layer<P, UMB, PIPE, NB, QC, MBQ, true, false, false, !MERGE, (CY ? 2 : -1), true, CY>(st, smem, t0, t1, head, norb, carry);
@@ -345,6 +388,16 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       }
     }
     // the lane's own sample (sample p on lane p of half 0, as the heads): PrecX3M16 lane 16 g + (l & 15) carries it as point n = g & 1
+#ifdef DFN_MLP_PTS_TU
+    // points have no depths: the raw store below is the only epilogue (launch_mlp_pts refuses a.partial)
+    uint32_t pt_own[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      if constexpr (P::kM16) pt_own[nb] = (st.lane & 16) != 0 ? pt_cur[1] : pt_cur[0];
+      else pt_own[nb] = pt_cur[nb];
+    }
+    {
+#else
     uint32_t pt_own[NB], ray_own[NB];
     float z_own[NB], zn_own[NB];
 #pragma unroll
@@ -426,6 +479,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
         }
       }
     } else {
+#endif
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
         if (h == 0 && pt_own[nb] < npts) {
@@ -445,10 +499,15 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
         asm volatile("" : "+v"(loc));   // formed here: as a loop invariant it was hoisted to the prologue and spilled
         const int r = loc >> 6, l = loc & 63;
         const float* f = reinterpret_cast<const float*>(slot + r * 8 * 256) + l;
+#ifdef DFN_MLP_PTS_TU
+#pragma unroll
+        for (int c = 0; c < 3; ++c) xin[nb][c] = f[c * 64];
+#else
         zin[nb] = f[0];
         znext[nb] = f[7 * 64];
 #pragma unroll
         for (int c = 0; c < 3; ++c) { oin[nb][c] = f[(1 + c) * 64]; din[nb][c] = f[(4 + c) * 64]; }
+#endif
       }
     }
   }
@@ -465,7 +524,73 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 }
 
 // ------------------------------------------------------------------------------------------
+#if defined(DFN_MLP_PTS_TU)
+// The points flavour's launchers.  One geometry per (unit, arithmetic), the one the raw route of the ray entries runs at the default
+// kernel variant, so that a point equal to o + d z gives the bits the ray entry gives.
+template <class P, bool FAST, int WAVES, int UMB, int NB, bool PIPE, int W, bool FINE>
+static hipError_t launch_pts_one(const MlpArgs& a, int n_cu, hipStream_t stream) {
+  constexpr int PPT = WAVES * NB * 32;
+  const long long n_pts = (long long)a.n_rays * a.n_samples;
+  if (n_pts <= 0) return hipSuccess;
+  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
+  if (a.masks || a.partial || !a.rays_o || !a.out) return hipErrorInvalidValue;   // raw route only: points have no depths to composite along
+  const long long n_tiles = (n_pts + PPT - 1) / PPT;
+  const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
+  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB, W>();
+  void (*kern)(MlpArgs) = nullptr;
+  if constexpr (FINE) kern = DFN_FINE_KERNEL<P, FAST, WAVES, UMB, NB, PIPE, W>;
+  else kern = DFN_COARSE_KERNEL<P, FAST, WAVES, UMB, NB, PIPE, W>;
+  static bool attr_done = false;
+  if (!attr_done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    if (e != hipSuccess) return e;
+    attr_done = true;
+  }
+  MlpArgs b = a;
+  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid, as launch_mlp
+    static int env = -1;
+    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
+    b.dma_waves = env > 0 ? env : (WAVES == 8 ? 4 : WAVES);
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
+  return hipGetLastError();
+}
 #if defined(DFN_MLP_HALF_TU)
+// split-f16, netwidth 128, coarse: variant 6's half-height kernel (launch_mlp_half's geometry) on net[0][F16X3][6]
+hipError_t launch_mlp_pts_half(const MlpArgs& a, int n_cu, hipStream_t stream) {
+  return launch_pts_one<PrecX3M16, false, 8, unit_mb<PrecX3M16>(0), 1, true, kWidth, false>(a, n_cu, stream);
+}
+#elif defined(DFN_MLP_FOLD_TU)
+// split-f16, netwidth 128, fine: variant 5's folded kernel (launch_mlp_fold's geometry) on net[1][F16X3][5], a.ray_bias from rb_fold
+hipError_t launch_mlp_pts_fold(const MlpArgs& a, int n_cu, hipStream_t stream) {
+  return launch_pts_one<PrecX3M16, false, 8, unit_mb<PrecX3M16>(0), 1, true, kWidth, true>(a, n_cu, stream);
+}
+#else
+// f16 and exact fp32 at netwidth 128 (their variant-0 kernels) and the three plain kernels of netwidth 256, as launch_mlp picks them
+hipError_t launch_mlp_pts(bool fine, int prec, const MlpArgs& a, int n_cu, hipStream_t stream, int width) {
+  if (width == 256) {
+    if (prec == 0) {
+      return fine ? launch_pts_one<PrecF16, true, 8, unit_mb_w256<PrecF16>(), 1, false, 256, true>(a, n_cu, stream)
+                  : launch_pts_one<PrecF16, true, 8, unit_mb_w256<PrecF16>(), 1, false, 256, false>(a, n_cu, stream);
+    }
+    if (prec == 2) {
+      return fine ? launch_pts_one<PrecX3, false, 4, unit_mb_w256<PrecX3>(), 1, false, 256, true>(a, n_cu, stream)
+                  : launch_pts_one<PrecX3, false, 4, unit_mb_w256<PrecX3>(), 1, false, 256, false>(a, n_cu, stream);
+    }
+    return fine ? launch_pts_one<PrecF32, false, 4, unit_mb_w256<PrecF32>(), 1, false, 256, true>(a, n_cu, stream)
+                : launch_pts_one<PrecF32, false, 4, unit_mb_w256<PrecF32>(), 1, false, 256, false>(a, n_cu, stream);
+  }
+  if (width != kWidth) return hipErrorInvalidValue;
+  if (prec == 0) {
+    return fine ? launch_pts_one<PrecF16, true, 8, 8, 2, true, kWidth, true>(a, n_cu, stream)
+                : launch_pts_one<PrecF16, true, 8, 8, 2, true, kWidth, false>(a, n_cu, stream);
+  }
+  if (prec == 2) return hipErrorInvalidValue;   // split-f16 at netwidth 128: launch_mlp_pts_half (coarse), launch_mlp_pts_fold (fine)
+  return fine ? launch_pts_one<PrecF32, false, 8, 1, 1, false, kWidth, true>(a, n_cu, stream)
+              : launch_pts_one<PrecF32, false, 8, 1, 1, false, kWidth, false>(a, n_cu, stream);
+}
+#endif
+#elif defined(DFN_MLP_HALF_TU)
 // variant 6's kernels: variant 4's geometry (launch_one<PrecX3M16, false, 8, 2, 1, 1, true> below).  coarse; fine with the compositing
 // fused, plain or render-maps flavour -- the raw route (a.partial == nullptr) stays with launch_mlp_fold.
 hipError_t launch_mlp_half(bool fine, bool maps, const MlpArgs& a, int n_cu, hipStream_t stream) {

@@ -232,6 +232,78 @@ class NerfHEngine:
                                                    ptr(gpts), current_stream()), "dfn_mlp_fine_backward_saved")
         return gpts
 
+    # ------------------------------------------------------------------ point queries
+    POINTS_CHUNK = 1 << 28       # points per library call (the kernels index points with 32 bits)
+    POINT_ROWS_CHUNK = 1 << 18   # rows per library call of the fine queries (one 1 KB bias-table row each)
+
+    def _point_rows(self, pts, viewdirs=None, hist=None):
+        """Contiguous fp32 pts [n, N, 3] (read in place by the kernels), view directions [n, 3] and histograms [1 | n, hist_bin]."""
+        pts = _f32c(pts)
+        if pts.dim() != 3 or pts.shape[-1] != 3 or pts.shape[1] < 1:
+            raise ValueError(f"pts must be [rows, N, 3] with N >= 1, got {tuple(pts.shape)}")
+        n = pts.shape[0]
+        if viewdirs is not None:
+            viewdirs = _f32c(viewdirs).reshape(-1, 3)
+            if viewdirs.shape[0] != n:   # the kernels read one row per row of points
+                raise ValueError(f"viewdirs must have {n} rows, got {tuple(viewdirs.shape)}")
+        if hist is not None:
+            hist = _f32c(hist).reshape(-1, self.hist_bin)
+            if hist.shape[0] not in (1, n):
+                raise ValueError(f"hist must have 1 or {n} rows, got {tuple(hist.shape)}")
+        return pts, viewdirs, hist
+
+    def _point_chunks(self, n, N, fine):
+        """Row ranges [r0, r1) of one library call each.  A single trailing row is not left a call of its own (it takes a row from the
+        call before it): the bias-table kernel sums a lone row's histogram in its shared-histogram order, whose rounding differs from
+        the per-row order the same row gets inside a larger call, and a split query must return the bits of the unsplit one."""
+        step = max(1, self.POINTS_CHUNK // N)
+        if fine:
+            step = min(step, self.POINT_ROWS_CHUNK)
+        chunks = [(r0, min(n, r0 + step)) for r0 in range(0, n, step)]
+        if fine and len(chunks) > 1 and step >= 3 and chunks[-1][1] - chunks[-1][0] == 1:
+            (a, b), (_, c) = chunks[-2], chunks[-1]
+            chunks[-2:] = [(a, b - 1), (b - 1, c)]
+        return chunks
+
+    def mlp_coarse_points(self, pts, precision=None):
+        """The coarse network's density at the caller's own points: pts [n, N, 3] -> sigma [n, N] (nerfw.py:37-46)."""
+        pts, _, _ = self._point_rows(pts)
+        n, N = pts.shape[:2]
+        sigma = torch.empty(n, N, device=pts.device)
+        for r0, r1 in self._point_chunks(n, N, False) or [(0, 0)]:
+            check(self.lib.dfn_mlp_coarse_points(self.handle, self._prec(precision), ptr(pts[r0:r1]), r1 - r0, N, ptr(sigma[r0:r1]),
+                                                 current_stream()), "dfn_mlp_coarse_points")
+        return sigma
+
+    def mlp_fine_points(self, pts, viewdirs, hist, precision=None):
+        """The fine network at the caller's own points: pts [n, N, 3], one view direction [n, 3] and one histogram (hist [1 | n,
+        hist_bin]) per row -> raw [n, N, 9] (nerfw.py:62-95)."""
+        pts, viewdirs, hist = self._point_rows(pts, viewdirs, hist)
+        n, N = pts.shape[:2]
+        raw = torch.empty(n, N, 9, device=pts.device)
+        for r0, r1 in self._point_chunks(n, N, True) or [(0, 0)]:
+            hs = hist if hist.shape[0] == 1 else hist[r0:r1]
+            bias = torch.empty(self.lib.dfn_fine_bias_bytes(r1 - r0), dtype=torch.uint8, device=pts.device)
+            check(self.lib.dfn_mlp_fine_points(self.handle, self._prec(precision), ptr(pts[r0:r1]), ptr(viewdirs[r0:r1]), ptr(hs),
+                                               hs.shape[0], r1 - r0, N, ptr(raw[r0:r1]), ctypes.c_void_p(bias.data_ptr()),
+                                               current_stream()), "dfn_mlp_fine_points")
+        return raw
+
+    def mlp_fine_points_backward(self, pts, viewdirs, hist, grad_raw, precision=None):
+        """d L/d raw [n,N,9] of mlp_fine_points -> [n,N,6]: d L/d point (3) and d L/d viewdir through that point (3)."""
+        pts, viewdirs, hist = self._point_rows(pts, viewdirs, hist)
+        n, N = pts.shape[:2]
+        grad_raw = _f32c(grad_raw).reshape(n, N, 9)
+        gpts = torch.empty(n, N, 6, device=pts.device)
+        for r0, r1 in self._point_chunks(n, N, True) or [(0, 0)]:
+            hs = hist if hist.shape[0] == 1 else hist[r0:r1]
+            bias = torch.empty(self.lib.dfn_fine_bias_bytes(r1 - r0), dtype=torch.uint8, device=pts.device)
+            check(self.lib.dfn_mlp_fine_points_backward(self.handle, self._prec(precision), ptr(pts[r0:r1]), ptr(viewdirs[r0:r1]), ptr(hs),
+                                                        hs.shape[0], r1 - r0, N, ptr(grad_raw[r0:r1]), ptr(gpts[r0:r1]),
+                                                        ctypes.c_void_p(bias.data_ptr()), current_stream()),
+                  "dfn_mlp_fine_points_backward")
+        return gpts
+
     # ------------------------------------------------------------------ whole path
     GENERIC_GRAD_CHUNK = 8192   # rays per pass of the generic-width gradient (every fine activation is kept: ~1.3 MB per ray at 64+128, netwidth 256)
     GENERIC_CHUNK = 4096   # rays per pass of the generic path (its activations live in HBM: ~1.2 MB per ray at 64+128, W=128)

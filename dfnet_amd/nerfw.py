@@ -66,9 +66,43 @@ class NeRFW(nn.Module):
                            "(the fused HIP kernels take rays, not pre-embedded vectors)")
 
 
+class _FinePointsFn(torch.autograd.Function):
+    """raw [R,N,9] = the fine network at pts [R,N,3] with one view direction per row; backward: d L/d pts and d L/d viewdirs from
+    d L/d raw (NerfHEngine.mlp_fine_points / mlp_fine_points_backward: the forward is recomputed inside the gradient kernel)."""
+
+    @staticmethod
+    def forward(ctx, pts, viewdirs, eng, hist, prec):
+        pts, viewdirs = pts.detach().contiguous().float(), viewdirs.detach().contiguous().float()
+        ctx.eng, ctx.prec = eng, prec
+        ctx.save_for_backward(pts, viewdirs, hist)
+        return eng.mlp_fine_points(pts, viewdirs, hist, precision=prec)
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        pts, viewdirs, hist = ctx.saved_tensors
+        g = ctx.eng.mlp_fine_points_backward(pts, viewdirs, hist, g_raw, precision=ctx.prec)
+        g_pts = g[..., :3].contiguous() if ctx.needs_input_grad[0] else None
+        g_v = g[..., 3:].sum(dim=1) if ctx.needs_input_grad[1] else None   # one view direction per row of points
+        return g_pts, g_v, None, None, None
+
+
 class HipQuery:
-    """Stands in for the reference's `network_query_fn` lambda (nerfw.py:425-434): carries the engine
-    that evaluates both networks.  Calling it with pre-sampled points evaluates the MLP stage."""
+    """Stands in for the reference's `network_query_fn` lambda (nerfw.py:425-434): carries the engine that evaluates both networks,
+    and is callable as the reference's is.
+
+    `query(inputs, viewdirs, ts, network_fn, typ, embedding_a, embedding_t, output_transient, test_time)` evaluates a network on
+    pre-sampled points (run_network_NeRFW, nerfw.py:15-95) with the register-resident HIP kernels: inputs [..., N, 3] (any points,
+    not only samples of a ray), one view direction per row of N points (viewdirs [R, 3]) and one histogram per row or one for all
+    (ts [R | 1, hist_bin]).  The result keeps the leading shape of `inputs`:
+      typ='coarse', test_time=True          sigma [..., N, 1]            (nerfw.py:37-46)
+      typ='fine',   output_transient=True   raw   [..., N, 9]            (nerfw.py:62-95)
+      typ='fine',   output_transient=False  raw[..., :4] = (static_rgb, static_sigma), the four values the reference concatenates
+    The networks are the ones packed into the engine: a `network_fn` / `embedding_a` / `embedding_t` that is not the module behind
+    it raises ValueError (None is accepted).  With grad enabled and `inputs` or `viewdirs` requiring it, typ='fine' is differentiable
+    with respect to both (the weights receive no gradient here: that is the training step's job), in fp32-grade arithmetic as
+    `render` under autograd: an engine whose precision is plain f16 differentiates in split-f16.
+    Refused with NotImplementedError: typ='coarse' with test_time=False (the 4-channel training query, nerfw.py:47-60), typ='coarse'
+    under autograd, and a netwidth other than 128 or 256 (no register-resident kernels)."""
 
     def __init__(self, engine, netchunk=65536, trainer=None, modules=None):
         self.engine = engine
@@ -95,8 +129,50 @@ class HipQuery:
             self.stale = False
             self._packed_versions = cur
 
-    def __call__(self, *a, **k):
-        raise RuntimeError("network_query_fn is fused into the HIP render path; call rendering.render()")
+    def _check_module(self, given, index, name):
+        if given is None:
+            return
+        if self.modules is None or given is not self.modules[index]:
+            raise ValueError(f"network_query_fn: {name} is not the module packed into this engine; the HIP kernels evaluate the "
+                             "engine's own weights (pass None, or the module create_nerf returned)")
+
+    def __call__(self, inputs, viewdirs, ts, network_fn=None, typ='fine', embedding_a=None, embedding_t=None, output_transient=True,
+                 test_time=True):
+        self.refresh()
+        if typ not in ('coarse', 'fine'):
+            raise ValueError(f"network_query_fn: typ must be 'coarse' or 'fine', got {typ!r}")
+        self._check_module(network_fn, 0 if typ == 'coarse' else 1, "network_fn")
+        self._check_module(embedding_a, 2, "embedding_a")
+        self._check_module(embedding_t, 3, "embedding_t")
+        eng = self.engine
+        if not eng.fast:
+            raise NotImplementedError(f"network_query_fn: point queries exist for netwidth 128 and 256 (the register-resident "
+                                      f"kernels); this engine has netwidth {eng.width}")
+        if inputs.shape[-1] != 3 or inputs.dim() < 2:
+            raise ValueError(f"network_query_fn: inputs must be [..., N, 3], got {tuple(inputs.shape)}")
+        lead = tuple(inputs.shape[:-1])
+        pts = inputs.reshape(-1, inputs.shape[-2], 3) if inputs.dim() > 2 else inputs.reshape(-1, 1, 3)
+        tracked = torch.is_grad_enabled() and (inputs.requires_grad or (viewdirs is not None and viewdirs.requires_grad))
+        if typ == 'coarse':
+            if not test_time:
+                raise NotImplementedError("network_query_fn: typ='coarse' with test_time=False (the 4-channel training query, "
+                                          "nerfw.py:47-60) is not implemented; the training render evaluates it (rendering.render)")
+            if tracked:
+                raise NotImplementedError("network_query_fn: typ='coarse' under autograd is not implemented (the input-gradient "
+                                          "kernel is the fine network's)")
+            return eng.mlp_coarse_points(pts.detach()).reshape(lead + (1,))
+        if viewdirs is None or ts is None:
+            raise ValueError("network_query_fn: typ='fine' needs viewdirs [R, 3] and ts [R | 1, hist_bin]")
+        v = viewdirs.reshape(-1, 3)
+        if v.shape[0] != pts.shape[0]:
+            raise ValueError(f"network_query_fn: viewdirs must have one row per row of points ({pts.shape[0]}), got {tuple(viewdirs.shape)}")
+        hist = ts.detach().float().reshape(-1, eng.hist_bin).contiguous()
+        if tracked:
+            raw = _FinePointsFn.apply(pts, v, eng, hist, "f16x3" if eng.precision in ("f16", "fp16") else eng.precision)
+        else:
+            raw = eng.mlp_fine_points(pts.detach(), v.detach(), hist)
+        raw = raw.reshape(lead + (9,))
+        return raw if output_transient else raw[..., :4]
 
 
 def create_nerf(args):

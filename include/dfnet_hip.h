@@ -270,6 +270,26 @@ int dfn_mlp_fine_saving(dfn_nerfh_t h, int prec, const float* rays_o, const floa
 int dfn_mlp_fine_backward_saved(dfn_nerfh_t h, int prec, const float* rays_o, const float* rays_d,
                                 const float* viewdirs, size_t n_rays, const float* z_fine, int Nf, const float* raw,
                                 const void* masks, const float* grad_raw, float* grad_pts, void* stream);
+/* Point queries: the networks evaluated on the caller's own points, pts [n_rows, N, 3] (fp32, contiguous), read in place -- not on
+ * samples of a ray.  They replace models/nerfw.py:15-95 (run_network_NeRFW) as the reference's network_query_fn calls it
+ * (nerfw.py:425-434): each of the n_rows rows of N points has ONE view direction and ONE appearance / transient histogram, as
+ * run_network_NeRFW repeats viewdirs[:, None] and ts over the samples of a row.  The kernels are those of dfn_mlp_coarse /
+ * dfn_mlp_fine / dfn_mlp_fine_backward behind the three inputs of a point: a point equal to fl(o + fl(d z)) gives the bits the ray
+ * entry gives at the default kernel variant.  Under another DFN_MLP_VARIANT these entries still run the default variant's kernels (the
+ * variants are an A/B aid of the render path).  Netwidth 128 and 256 (a generic width: DFN_ERR_UNSUPPORTED); n_rows == 0 is DFN_OK;
+ * n_rows * N must stay below 2^31 (the host chunks by rows).
+ * dfn_mlp_coarse_points: nerfw.py:37-46 (test-time coarse query) -> sigma [n_rows, N].
+ * dfn_mlp_fine_points: nerfw.py:62-95 -> raw [n_rows, N, 9]; viewdirs [n_rows, 3], hist [hist_rows, hist_bin] with hist_rows 1 or
+ * n_rows, bias_ws of dfn_fine_bias_bytes(n_rows) bytes, all as dfn_mlp_fine.
+ * dfn_mlp_fine_points_backward: autograd through that query: from grad_raw [n_rows, N, 9] to grad_pts [n_rows, N, 6] = [d L / d point
+ * (3), d L / d viewdir through this point (3)], as dfn_mlp_fine_backward (netwidth 128, DFN_PREC_F16X3 or DFN_PREC_F32). */
+int dfn_mlp_coarse_points(dfn_nerfh_t h, int prec, const float* pts, size_t n_rows, int N, float* sigma, void* stream);
+int dfn_mlp_fine_points(dfn_nerfh_t h, int prec, const float* pts, const float* viewdirs, const float* hist, size_t hist_rows,
+                        size_t n_rows, int N, float* raw, void* bias_ws, void* stream);
+int dfn_mlp_fine_points_backward(dfn_nerfh_t h, int prec, const float* pts, const float* viewdirs, const float* hist,
+                                 size_t hist_rows, size_t n_rows, int N, const float* grad_raw, float* grad_pts, void* bias_ws,
+                                 void* stream);
+
 /* Per-ray reduction of grad_pts [n_rays, Nf, 6] (pts = o + d z, rendering.py:292,305): grad_rays_o = sum g,
  * grad_rays_d = sum z g; with derive_viewdirs != 0 the view-direction part is folded into grad_rays_d through
  * viewdirs = d/|d| (rendering.py:366-371), otherwise grad_viewdirs (optional) receives sum gv. */
