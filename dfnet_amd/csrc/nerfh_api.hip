@@ -110,6 +110,7 @@ static void free_packed(dfn_nerfh_s* h) {
       for (auto& n : b) {
         if (n.blob) (void)hipFree(n.blob);
         if (n.tab) (void)hipFree(n.tab);
+        if (n.res_blob) (void)hipFree(n.res_blob);
         n = PackedNet();
       }
   for (PackedNet* n : {&h->bwd[0], &h->bwd[1], &h->bwd[2], &h->half_maps}) {
@@ -409,8 +410,12 @@ struct Packer {
   // The packed blob: staging units in execution order.  umb >= 8: a unit holds whole layers and the small
   // layers of one group (kFineGroup / kCoarseGroup) share a unit; otherwise a unit is <= umb M-blocks of a layer.
   // l5_umb: M-blocks per unit of layer 5 (< 0: the same as the other layers)
+  // res (kernel variant 7, plain units only): the layers of kFineResident / kCoarseResident go there instead, unit after unit in
+  // execution order in the same fragment and bias-block format but without the rounding to pieces (nerfh_layout.h: resident_offset);
+  // blob and tab then hold the streamed units alone.  The set is zero-padded once to whole pieces.
   template <class P>
-  void pack(bool fine, int umb, bool merge, std::vector<uint8_t>& blob, std::vector<uint32_t>& tab, int l5_umb = -1, bool fold = false) const {
+  void pack(bool fine, int umb, bool merge, std::vector<uint8_t>& blob, std::vector<uint32_t>& tab, int l5_umb = -1, bool fold = false,
+            std::vector<uint8_t>* res = nullptr) const {
     const int* seq = fine ? (fold ? kFineFoldSeq : kFineSeq) : kCoarseSeq;
     const int* grp = fine ? kFineGroup : kCoarseGroup;
     const int nl = fine ? kFineLayers : kCoarseLayers;
@@ -450,6 +455,12 @@ struct Packer {
       const int lu = (seq[li] == LY_L5 && l5_umb > 0) ? l5_umb : umb;
       for (int mb0 = 0; mb0 < sh.mb; mb0 += lu) {
         const int group = sh.mb - mb0 < lu ? sh.mb - mb0 : lu;
+        if (res && layer_resident(fine, seq[li])) {
+          const size_t at = res->size();
+          res->resize(at + blocks_bytes<P>(seq[li], group), 0);
+          pack_blocks<P>(seq[li], mb0, group, res->data() + at);
+          continue;
+        }
         const uint32_t bytes = unit_bytes<P>(sh.slots, group, P::kM16 && half_block(seq[li]));
         const uint32_t off = uint32_t(blob.size());
         blob.resize(off + bytes, 0);
@@ -458,6 +469,7 @@ struct Packer {
         pack_blocks<P>(seq[li], mb0, group, blob.data() + off);
       }
     }
+    if (res) res->resize(align_piece(uint32_t(res->size())), 0);
   }
 };
 
@@ -600,14 +612,18 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
         // variant 5 has one network of its own, the split-f16 fine one; everything else of it is variant 4's (net_of).  Variant 6 has
         // three, all split-f16 with half-height head blocks: the coarse one, the folded fine one without transient_beta's half (fused
         // compositing, no maps) and, in h->half_maps, the folded fine one with it (the maps flavour); the rest is variant 5's
-        const bool half = var == kHalfVariant;
+        // Variant 7 has two, variant 6's coarse and plain fine one with the resident layers taken out of the unit table into a blob of
+        // their own (res_blob); its maps flavour reads variant 6's half_maps
+        const bool resident = var == kResidentVariant;
+        const bool half = var == kHalfVariant || resident;
         const bool fold = var == kFoldVariant || (half && f == 1);
         if (var == kFoldVariant && !(f == 1 && prec == DFN_PREC_F16X3)) continue;
         if (half && prec != DFN_PREC_F16X3) continue;
         Packer pk{h, f ? "fine." : "coarse."};
         pk.half_heads = half;
         pk.half_thead = half;
-        std::vector<uint8_t> blob;
+        std::vector<uint8_t> blob, rblob;
+        std::vector<uint8_t>* res = resident ? &rblob : nullptr;
         std::vector<uint32_t> tab;
         PackedNet& n = h->net[f][prec][var];
         if (prec == DFN_PREC_F16) pk.pack<PrecF16>(f, unit_mb<PrecF16>(var), unit_mb<PrecF16>(var) >= 8, blob, tab);
@@ -633,8 +649,8 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
             const auto& bF = h->params.at("fine.xyz_encoding_final.bias");
             fold_final(h->params.at("fine.dir_encoding.0.weight"), Wd / 2, ldd, F, bF, Wd, pk.fold_dir, fold_bd);
             fold_final(h->params.at("fine.transient_encoding.0.weight"), Wd / 2, ldt, F, bF, Wd, pk.fold_tr, fold_bt);
-            pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)), true);
-            if (half) {   // the maps flavour's network: the transient head at full height
+            pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)), true, res);
+            if (half && !resident) {   // the maps flavour's network: the transient head at full height
               std::vector<uint8_t> mblob;
               std::vector<uint32_t> mtab;
               pk.half_thead = false;
@@ -647,7 +663,7 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
               if (rc) return rc;
               m.n_units = int(mtab.size() / 2);
             }
-          } else if (var == 4 || half) pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)));
+          } else if (var == 4 || half) pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)), false, res);
           else pk.pack<PrecX3>(f, unit_mb<PrecX3>(var), false, blob, tab, l5_unit_mb_p<PrecX3>(unit_mb<PrecX3>(var)));
         }
         int rc = upload(blob.data(), blob.size(), reinterpret_cast<void**>(&n.blob));
@@ -655,6 +671,14 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
         rc = upload(tab.data(), tab.size() * 4, reinterpret_cast<void**>(&n.tab));
         if (rc) return rc;
         n.n_units = int(tab.size() / 2);
+        if (resident) {
+          if (rblob.size() != resident_bytes<PrecX3M16>(f != 0))
+            return set_error(DFN_ERR_STATE, "dfn_nerfh_commit: the resident layers pack to %zu bytes, the kernels expect %u", rblob.size(),
+                             resident_bytes<PrecX3M16>(f != 0));
+          rc = upload(rblob.data(), rblob.size(), reinterpret_cast<void**>(&n.res_blob));
+          if (rc) return rc;
+          n.res_bytes = uint32_t(rblob.size());
+        }
       }
   for (int prec = 0; prec < 3; ++prec) {
     Packer pk{h, "fine."};
@@ -805,11 +829,12 @@ static int check_grad_prec(int prec, const char* fn) {
   return DFN_OK;
 }
 
-// Kernel variant: DFN_MLP_VARIANT=0..6 (A/B aid, see nerfh_layout.h).  Default 6: split-f16 on 16x16x32 MFMAs (f16 / exact fp32 run their
-// variant-0 kernels under it) with the fine render kernel's tail folded (fold_fine, base_variant) and half-height head blocks in the
-// render kernels (half_heads); DFN_MLP_VARIANT=5 is the same with full-height head blocks, DFN_MLP_VARIANT=4 also without the fold,
-// DFN_MLP_VARIANT=0 keeps the 32x32x16 split-f16 kernels.
-constexpr int kDefaultVariant = kHalfVariant;
+// Kernel variant: DFN_MLP_VARIANT=0..7 (A/B aid, see nerfh_layout.h).  Default 7: split-f16 on 16x16x32 MFMAs (f16 / exact fp32 run their
+// variant-0 kernels under it) with the fine render kernel's tail folded (fold_fine, base_variant), half-height head blocks in the
+// render kernels (half_heads) and the small tail layers resident in LDS in the coarse and the plain fused fine kernel (resident_layers);
+// DFN_MLP_VARIANT=6 is the same with every layer streamed, DFN_MLP_VARIANT=5 also with full-height head blocks, DFN_MLP_VARIANT=4 also
+// without the fold, DFN_MLP_VARIANT=0 keeps the 32x32x16 split-f16 kernels.
+constexpr int kDefaultVariant = kResidentVariant;
 static int mlp_variant_128();
 static int mlp_variant_of(dfn_nerfh_t h) { return h->desc.width == kWidth ? mlp_variant_128() : 0; }
 static int mlp_variant_128() {
@@ -826,9 +851,19 @@ static int mlp_variant_128() {
 // Variant 6 is variant 5 except in the split-f16 netwidth-128 render kernels that launch_mlp_half has: the coarse kernel, and the fine
 // kernel where the compositing is fused (plain: net[1][F16X3][6], maps: half_maps; coarse: net[0][F16X3][6]).  Its raw route runs
 // variant 5's fine kernel on variant 5's network, and everything else resolves as under variant 5.
-static int base_variant(int var) { return var == kFoldVariant || var == kHalfVariant ? 4 : var; }
-static bool fold_fine(int var, int prec) { return (var == kFoldVariant || var == kHalfVariant) && prec == DFN_PREC_F16X3; }
-static bool half_heads(int var, int prec) { return var == kHalfVariant && prec == DFN_PREC_F16X3; }
+// Variant 7 is variant 6 except in the two kernels launch_mlp_res has: the coarse kernel (net[0][F16X3][7]) and the plain fused fine
+// kernel (net[1][F16X3][7]); the maps flavour runs variant 6's kernel on half_maps and everything else resolves as under variant 6.
+static int base_variant(int var) { return var == kFoldVariant || var == kHalfVariant || var == kResidentVariant ? 4 : var; }
+static bool fold_fine(int var, int prec) { return (var == kFoldVariant || var == kHalfVariant || var == kResidentVariant) && prec == DFN_PREC_F16X3; }
+static bool half_heads(int var, int prec) { return (var == kHalfVariant || var == kResidentVariant) && prec == DFN_PREC_F16X3; }
+static bool resident_layers(int var, int prec) { return var == kResidentVariant && prec == DFN_PREC_F16X3; }
+static MlpResArgs res_args(const MlpArgs& a, const PackedNet& n) {
+  MlpResArgs r{};
+  static_cast<MlpArgs&>(r) = a;
+  r.res_blob = n.res_blob;
+  r.res_bytes = n.res_bytes;
+  return r;
+}
 
 // The handle's range-guard flag (device int): allocated and cleared by dfn_nerfh_commit, which fails loudly when it cannot be —
 // every kernel launch that carries the guard runs on a committed handle.
@@ -856,14 +891,15 @@ extern "C" int dfn_mlp_coarse(dfn_nerfh_t h, int prec, const float* rays_o, cons
   if (int rc = check_net(h, prec, "dfn_mlp_coarse", true)) return rc;
   if (!n_rays) return DFN_OK;
   if (!rays_o || !rays_d || !sigma || Nc < 1) return set_error(DFN_ERR_ARG, "dfn_mlp_coarse: bad argument");
-  const bool half = half_heads(mlp_variant_of(h), prec);
+  const bool half = half_heads(mlp_variant_of(h), prec), res = resident_layers(mlp_variant_of(h), prec);
   const int var = base_variant(mlp_variant_of(h));
-  const PackedNet& n = h->net[0][prec][half ? kHalfVariant : var];
+  const PackedNet& n = h->net[0][prec][res ? kResidentVariant : (half ? kHalfVariant : var)];
   MlpArgs a{n.blob, n.tab, n.n_units, rays_o, rays_d, nullptr, nullptr, sigma, nullptr, (long long)n_rays, Nc, near, far, nullptr, n.in_scale,
             h->render_flags & DFN_RENDER_LINDISP};
   a.status = range_flag_of(h);
   ScopedTimer t(0, HS(stream));
-  if (half) CHECK_HIP(launch_mlp_half(false, false, a, device_cu_count(), HS(stream)), "dfn_mlp_coarse");
+  if (res) CHECK_HIP(launch_mlp_res(false, res_args(a, n), device_cu_count(), HS(stream)), "dfn_mlp_coarse");
+  else if (half) CHECK_HIP(launch_mlp_half(false, false, a, device_cu_count(), HS(stream)), "dfn_mlp_coarse");
   else CHECK_HIP(launch_mlp(false, prec, var, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_coarse");
   return DFN_OK;
 }
@@ -1026,8 +1062,11 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
   const int cprec = (h->render_flags & DFN_RENDER_COARSE_F16) ? DFN_PREC_F16 : prec;   // the coarse pass only places the fine samples
   // kernel variant 6: its coarse kernel, and its fine kernel where the compositing is fused (the raw route keeps variant 5's)
   const bool half_c = half_heads(mlp_variant_of(h), cprec), half_f = half_heads(mlp_variant_of(h), prec) && fused;
-  const PackedNet& nc = h->net[0][cprec][half_c ? kHalfVariant : var];
-  const PackedNet& nf = half_f ? (want_maps ? h->half_maps : h->net[1][prec][kHalfVariant]) : h->net[1][prec][fold ? kFoldVariant : var];
+  // kernel variant 7: its coarse kernel, and its fine kernel where variant 6's plain fused one would run (the maps flavour keeps variant 6's)
+  const bool res_c = resident_layers(mlp_variant_of(h), cprec), res_f = resident_layers(mlp_variant_of(h), prec) && fused && !want_maps;
+  const PackedNet& nc = h->net[0][cprec][res_c ? kResidentVariant : (half_c ? kHalfVariant : var)];
+  const PackedNet& nf = res_f ? h->net[1][prec][kResidentVariant]
+                      : half_f ? (want_maps ? h->half_maps : h->net[1][prec][kHalfVariant]) : h->net[1][prec][fold ? kFoldVariant : var];
   const int cus = device_cu_count();
   const size_t chunk = chunk_rays(n_rays);
   for (size_t r0 = 0; r0 < n_rays; r0 += chunk) {
@@ -1042,7 +1081,8 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
                  h->render_flags & DFN_RENDER_LINDISP};
       a.status = range_flag_of(h);
       ScopedTimer t(0, s);
-      if (half_c) CHECK_HIP(launch_mlp_half(false, false, a, cus, s), "render: coarse MLP (half-height heads)");
+      if (res_c) CHECK_HIP(launch_mlp_res(false, res_args(a, nc), cus, s), "render: coarse MLP (resident layers)");
+      else if (half_c) CHECK_HIP(launch_mlp_half(false, false, a, cus, s), "render: coarse MLP (half-height heads)");
       else CHECK_HIP(launch_mlp(false, cprec, var, a, cus, s, h->desc.width), "render: coarse MLP");
     }
     {
@@ -1058,7 +1098,8 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
       MlpArgs a{nf.blob, nf.tab, nf.n_units, co, cd, w.z, w.bias, raw, fused ? w.partial : nullptr, (long long)n, Nf, 0.f, 0.f, g_timing_buf, nf.in_scale};
       a.status = range_flag_of(h);
       ScopedTimer t(1, s);
-      if (half_f) CHECK_HIP(launch_mlp_half(true, want_maps, a, cus, s), "render: fine MLP (half-height heads)");
+      if (res_f) CHECK_HIP(launch_mlp_res(true, res_args(a, nf), cus, s), "render: fine MLP (resident layers)");
+      else if (half_f) CHECK_HIP(launch_mlp_half(true, want_maps, a, cus, s), "render: fine MLP (half-height heads)");
       else if (fold) CHECK_HIP(launch_mlp_fold(fused && want_maps, a, cus, s), "render: fine MLP (folded)");
       else if (fused && want_maps) CHECK_HIP(launch_mlp_maps(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP (maps)");
       else CHECK_HIP(launch_mlp(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP");

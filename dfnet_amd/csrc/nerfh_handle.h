@@ -15,6 +15,8 @@ struct PackedNet {
   int n_units = 0;
   int n_fwd_units = 0;   // gradient nets: the forward units come first in the table
   float in_scale = 1.f;  // split-f16: weight scale x activation scale carried by the accumulators
+  char* res_blob = nullptr;   // kernel variant 7: the LDS-resident layers (blob / tab then hold the streamed units only)
+  uint32_t res_bytes = 0;
 };
 
 struct dfn_nerfh_s {

@@ -41,6 +41,15 @@ hipError_t launch_mlp_fold(bool maps, const MlpArgs& a, int n_cu, hipStream_t st
 // (Packer::half_heads).  Coarse (fine = false), or the fine kernel with the compositing fused (a.partial set; maps as above): the
 // plain flavour leaves 0 in the segment record's beta slot.  The raw route stays with launch_mlp_fold.
 hipError_t launch_mlp_half(bool fine, bool maps, const MlpArgs& a, int n_cu, hipStream_t stream);
+// Kernel variant 7 (nerfh_mlp_res.hip): variant 6's coarse kernel and plain fused fine kernel with the layers of kCoarseResident /
+// kFineResident held in LDS.  blob / tab / n_units describe the STREAMED units only; res_blob is the resident set in execution order,
+// res_bytes = resident_bytes<PrecX3M16>(fine) (zero-padded to whole pieces).  The two fields ride behind MlpArgs in a struct of the
+// new kernels' own: a longer MlpArgs would move the hidden kernel arguments (gridDim) of every other kernel and with them their code.
+struct MlpResArgs : MlpArgs {
+  const char* res_blob;
+  uint32_t res_bytes;
+};
+hipError_t launch_mlp_res(bool fine, const MlpResArgs& a, int n_cu, hipStream_t stream);
 
 // The points flavour (nerfh_mlp_pts*.hip): a.rays_o is pts [n_rays, n_samples, 3] (n_rays = query rows), a.rays_d, a.z and a.partial
 // are unused (a.partial must be null: the raw route only), a.ray_bias has one row per query row.  launch_mlp_pts: f16 / exact fp32 at

@@ -146,9 +146,16 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //              transient_beta reaches no output: compositing fused, no maps -- the transient head are packed and multiplied as their
 //              ms = 0 fragments only (1 920 / 1 932 MFMAs per fine tile plain / maps, 1 560 per coarse tile instead of 1 584); the
 //              raw route and everything else resolve as under variant 5
-constexpr int kVariants = 7;
+//   variant 7: variant 6 with a fixed set of small layers RESIDENT in LDS in the two kernels the frame spends its time in, the coarse
+//              kernel and the plain fused fine kernel (nerfh_mlp_res.hip; kCoarseResident / kFineResident below): copied in once per
+//              workgroup behind the input slots and read there by every tile, they leave the streamed unit table (coarse 17 -> 14
+//              units, fine 26 -> 22 per 256-point tile) with their barriers and DMA round trips; the same fragments, MFMAs and
+//              conversion pieces in the same order: variant 6's outputs bit for bit.  The maps flavour, the raw route and everything
+//              else resolve as under variant 6
+constexpr int kVariants = 8;
 constexpr int kFoldVariant = 5;
 constexpr int kHalfVariant = 6;
+constexpr int kResidentVariant = 7;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));
 }
@@ -181,6 +188,40 @@ DFN_HD constexpr uint32_t max_unit_bytes(int umb, int W = kWidth) {
   const uint32_t g = umb >= 8 ? align_piece(44u * 64 * P::kLaneBytes + 9u * 128) : 0;
   return a > b ? (a > g ? a : g) : (b > g ? b : g);
 }
+
+// ---- kernel variant 7: LDS-resident layers ------------------------------------------------------------------
+// The layers a PrecX3M16 W = 128 render kernel keeps in LDS for its whole life instead of streaming them per tile, in EXECUTION order
+// (the order of the resident blob).  Head blocks are in their variant-6 half-height form.  A second candidate is one line here.
+//   fine (plain, compositing fused): static_sigma 8 320 + static_rgb 4 224 + transient_encoding.6 16 640 + transient head 4 224 = 33 408 B
+//   coarse: layer 1 (its two units, 2 x 16 640) + static_sigma 8 320 = 41 600 B
+constexpr int kCoarseResident[] = {LY_L1, LY_SIG};
+constexpr int kFineResident[] = {LY_SIG, LY_RGB, LY_TE3, LY_THEAD};
+DFN_HD constexpr int resident_count(bool fine) { return int(fine ? sizeof(kFineResident) : sizeof(kCoarseResident)) / int(sizeof(int)); }
+DFN_HD constexpr int resident_at(bool fine, int i) { return fine ? kFineResident[i] : kCoarseResident[i]; }
+DFN_HD constexpr bool layer_resident(bool fine, int id) {
+  for (int i = 0; i < resident_count(fine); ++i)
+    if (resident_at(fine, i) == id) return true;
+  return false;
+}
+// half-height head blocks of the kernels that keep layers resident (Packer::half_block with half_thead set)
+DFN_HD constexpr bool resident_half(int id) { return id == LY_SIG || id == LY_RGB || id == LY_THEAD; }
+// Bytes of a resident layer: its M-blocks in staging-unit format ([fragments][128-byte bias blocks] per unit of <= unit_mb M-blocks,
+// Packer::pack_blocks), units back to back WITHOUT the rounding to pieces: mb x (fragment bytes + 128) whatever the unit size.
+template <class P>
+DFN_HD constexpr uint32_t resident_layer_bytes(int id) {
+  const LayerShape sh = layer_shape(id);
+  return uint32_t(sh.mb) * (uint32_t(sh.slots / P::kSlotsPerChunk / (resident_half(id) ? 2 : 1)) * 64 * P::kLaneBytes + 128u);
+}
+// Offset of resident layer `id` inside the resident region; id = LY_COUNT: the bytes of the whole set.
+template <class P>
+DFN_HD constexpr uint32_t resident_offset(bool fine, int id) {
+  uint32_t off = 0;
+  for (int i = 0; i < resident_count(fine) && resident_at(fine, i) != id; ++i) off += resident_layer_bytes<P>(resident_at(fine, i));
+  return off;
+}
+// The region is filled by whole wave-wide DMA pieces: the set's bytes rounded up ONCE (the blob is zero-padded to match).
+template <class P> DFN_HD constexpr uint32_t resident_bytes(bool fine) { return align_piece(resident_offset<P>(fine, LY_COUNT)); }
+constexpr uint32_t kLdsBytes = 163840;   // LDS of a CU (gfx950)
 
 // ---- input-gradient kernel (nerfh_bwd.hip) ---------------------------------------------------------------
 // The backward pass of a Linear is the same transposed product with W^T as the A operand: the rows of an

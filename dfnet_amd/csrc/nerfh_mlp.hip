@@ -43,6 +43,10 @@ constexpr bool kMapsTU = false;
 // DFN_MLP_FOLD_TU.  It gets launch_mlp_half, the folded fine kernel as nerfh_fine_half_kernel (fused compositing only, plain and MAPS)
 // and the coarse kernel as nerfh_coarse_half_kernel; in the other three units kHalfHeads is false and every layer<> below names the
 // instantiation it named before.
+// Kernel variant 7 (LDS-resident small layers: layer<..., RES>, nerfh_layout.h: kFineResident / kCoarseResident) is nerfh_mlp_res.hip:
+// DFN_MLP_RES_TU on top of DFN_MLP_HALF_TU.  It gets launch_mlp_res, the coarse kernel as nerfh_coarse_res_kernel and the plain fused
+// fine kernel as nerfh_fine_res_kernel, both taking MlpResArgs; in every other unit kResident is false, every res_base() is -1 and
+// every layer<> and trunk<> below names the instantiation it named before.
 // The points flavour (dfn_mlp_coarse_points, dfn_mlp_fine_points: DFN_MLP_PTS_TU, on top of none, DFN_MLP_FOLD_TU or DFN_MLP_HALF_TU) is
 // compiled in three more units, nerfh_mlp_pts.hip, nerfh_mlp_pts_fold.hip and nerfh_mlp_pts_half.hip: the three inputs of a point are
 // loaded from pts [n_rows, n_samples, 3] (MlpArgs::rays_o) instead of being formed as o + d z, and everything behind x[..][3] is the
@@ -62,6 +66,10 @@ constexpr bool kHalfHeads = false;
 #define DFN_COARSE_KERNEL nerfh_coarse_pts_kernel
 constexpr bool kHalfHeads = false;
 #endif
+#elif defined(DFN_MLP_RES_TU)
+#define DFN_FINE_KERNEL nerfh_fine_res_kernel
+#define DFN_COARSE_KERNEL nerfh_coarse_res_kernel
+constexpr bool kHalfHeads = true;
 #elif defined(DFN_MLP_HALF_TU)
 #define DFN_FINE_KERNEL nerfh_fine_half_kernel
 #define DFN_COARSE_KERNEL nerfh_coarse_half_kernel
@@ -74,6 +82,17 @@ constexpr bool kHalfHeads = true;
 #endif
 #define DFN_COARSE_KERNEL nerfh_coarse_kernel
 constexpr bool kHalfHeads = false;
+#endif
+
+#if defined(DFN_MLP_RES_TU)
+#if !defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_PTS_TU)
+#error "the resident layers exist in the half-height render kernels"
+#endif
+constexpr bool kResident = true;
+#define DFN_MLP_KARGS MlpResArgs
+#else
+constexpr bool kResident = false;
+#define DFN_MLP_KARGS MlpArgs
 #endif
 
 // Head activations per arithmetic mode: f16 = hardware transcendentals (1e-6), split-f16 = the fp32-grade hardware forms
@@ -90,6 +109,26 @@ template <class P, int UMB, int WAVES, int NB, int W = kWidth> constexpr uint32_
   return ring_slots<P, W>() * max_unit_bytes<P>(UMB, W) + WAVES * ((NB * 32 + 63) / 64) * 8 * 256;
 }
 
+// Kernel variant 7: the resident region lies behind the input slots.  LDS byte offset of resident layer `id` there; -1 = the layer is
+// streamed (every layer, in the units that keep no layers resident).
+template <class P, int UMB, int WAVES, int NB, int W, bool FINE> constexpr int res_base(int id) {
+  return kResident && layer_resident(FINE, id) ? int(lds_bytes<P, UMB, WAVES, NB, W>() + resident_offset<P>(FINE, id)) : -1;
+}
+// the layers the kernels below can run out of the resident region (a table entry outside this list would silently be dropped)
+constexpr bool resident_set_supported(bool fine) {
+  for (int i = 0; i < resident_count(fine); ++i) {
+    const int id = resident_at(fine, i);
+    const bool ok = id == LY_L1 || id == LY_SIG || (fine && (id == LY_RGB || (id >= LY_TE1 && id <= LY_THEAD)));
+    if (!ok) return false;
+  }
+  return true;
+}
+static_assert(resident_set_supported(false) && resident_set_supported(true), "a resident layer the kernels stream");
+// ring 3 x 33 792 + input slots 8 x 2 048 = 117 760 B; + 33 792 (fine) / 41 984 (coarse) resident = 151 552 / 159 744 of the CU's 163 840
+static_assert(lds_bytes<PrecX3M16, unit_mb<PrecX3M16>(0), 8, 1>() + resident_bytes<PrecX3M16>(true) <= kLdsBytes &&
+              lds_bytes<PrecX3M16, unit_mb<PrecX3M16>(0), 8, 1>() + resident_bytes<PrecX3M16>(false) <= kLdsBytes,
+              "ring + input slots + resident layers must fit the LDS of a CU");
+
 // Workgroups per CU the register allocation is sized for.  netwidth 256 in split-f16 / exact fp32 holds 2 x 128 registers of
 // activations per point block: four waves per workgroup, ONE workgroup per CU (512 registers per lane).
 template <class P, int WAVES, int NB, int W> constexpr int mlp_min_blocks() {
@@ -99,7 +138,7 @@ template <class P, int WAVES, int NB, int W> constexpr int mlp_min_blocks() {
 
 // ------------------------------------------------------------------------------------------
 template <class P, bool FAST, int WAVES, int UMB, int NB, bool PIPE, int W = kWidth>
-__global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) void DFN_COARSE_KERNEL(MlpArgs a) {
+__global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) void DFN_COARSE_KERNEL(DFN_MLP_KARGS a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int PPT = WAVES * NB * 32;
   using F = typename FragOf<P>::type;
@@ -126,6 +165,9 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   const long long n_tiles = (n_pts + PPT - 1) / PPT;
   long long tile = blockIdx.x;
   if (tile >= n_tiles) return;
+#ifdef DFN_MLP_RES_TU
+  stage_resident(st, smem, a.res_blob, resident_bytes<P>(false), lds_bytes<P, UMB, WAVES, NB, W>());
+#endif
   stage_prime(st, smem, max_unit_bytes<P>(UMB, W), ring_slots<P, W>());
   for (; tile < n_tiles; tile += gridDim.x) {
     st.more = tile + gridDim.x < n_tiles;
@@ -154,11 +196,12 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     constexpr bool CY = PIPE && P::kSlotsPerChunk == 8, MERGE = UMB >= 8;
     F hid[NB][chunks_of<P>(W / 2)];
     f32x16 carry[NB];
-    trunk<P, UMB, PIPE, FAST, NB, W>(st, smem, x, hid, carry);
+    constexpr int R_L1 = res_base<P, UMB, WAVES, NB, W, false>(LY_L1), R_SIG = res_base<P, UMB, WAVES, NB, W, false>(LY_SIG);
+    trunk<P, UMB, PIPE, FAST, NB, W, NoTrunkHook, R_L1>(st, smem, x, hid, carry);
     f32x16 head[NB];
     F dummy[NB][chunks_of<P>(16)];
     const float* const norb[LP] = {};
-    layer<P, UMB, PIPE, NB, chunks_of<P>(W / 2), 0, false, true, false, !MERGE, (CY ? 6 : -1), true, false, false, false, true, kHalfHeads>(st, smem, hid, dummy, head, norb, carry);
+    layer<P, UMB, PIPE, NB, chunks_of<P>(W / 2), 0, false, true, false, !MERGE && R_SIG < 0, (CY ? 6 : -1), true, false, false, false, true, kHalfHeads, R_SIG>(st, smem, hid, dummy, head, norb, carry);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
       if (h == 0 && pt[nb] < npts) a.out[pt[nb]] = head_softplus<P, FAST>(head[nb][0]);
@@ -172,7 +215,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 // MAPS: the render-maps flavour of the fused compositing epilogue (dfn_render_*_maps): the segment record grows from 12 to
 // kMapsRecFloats floats by the static-only and the transient colour sums.  Its own instantiation: the kernels without it are unchanged.
 template <class P, bool FAST, int WAVES, int UMB, int NB, bool PIPE, int W = kWidth, bool MASKS = false, bool MAPS = false>
-__global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) void DFN_FINE_KERNEL(MlpArgs a) {
+__global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) void DFN_FINE_KERNEL(DFN_MLP_KARGS a) {
   static_assert(!MASKS || (P::kSplit && !P::kM16 && NB == 1 && WAVES == 8 && W == kWidth), "the sign masks follow the gradient kernel's tile geometry");
   static_assert(!MAPS || (!MASKS && W == kWidth && NB <= 2), "the maps flavour exists where the fused compositing does");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -185,6 +228,11 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   // kernel variant 6, compositing fused and no maps: transient_beta (head value 4, on half 1 of the transient head block) reaches no
   // output -- composite_combine_kernel does not read the record's beta slot -- so the block is half-height too and the slot holds 0
   constexpr bool NOBETA = kHalfHeads && !MAPS;
+  // kernel variant 7: LDS offsets of the resident layers (-1 = streamed; all of them outside nerfh_mlp_res.hip)
+  constexpr int R_L1 = res_base<P, UMB, WAVES, NB, W, true>(LY_L1);
+  constexpr int R_SIG = res_base<P, UMB, WAVES, NB, W, true>(LY_SIG), R_RGB = res_base<P, UMB, WAVES, NB, W, true>(LY_RGB),
+                R_TE1 = res_base<P, UMB, WAVES, NB, W, true>(LY_TE1), R_TE2 = res_base<P, UMB, WAVES, NB, W, true>(LY_TE2),
+                R_TE3 = res_base<P, UMB, WAVES, NB, W, true>(LY_TE3), R_THEAD = res_base<P, UMB, WAVES, NB, W, true>(LY_THEAD);
   using F = typename FragOf<P>::type;
   Stager st;
   st.blob = a.blob; st.tab = a.tab; st.n_units = a.n_units; st.u = 0;
@@ -209,6 +257,10 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   const long long n_tiles = (n_pts + PPT - 1) / PPT;
   long long tile = blockIdx.x;
   if (tile >= n_tiles) return;
+#ifdef DFN_MLP_RES_TU
+  static_assert(!MAPS && !MASKS, "the resident set is the plain fused fine kernel's");
+  stage_resident(st, smem, a.res_blob, resident_bytes<P>(true), lds_bytes<P, UMB, WAVES, NB, W>());
+#endif
   stage_prime(st, smem, USTRIDE, ring_slots<P, W>());
   // Tile inputs.  The first tile's are loaded normally; every later tile's are PREFETCHED during the
   // previous tile's small layers with direct-to-LDS loads and only
@@ -302,7 +354,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       }
     };
     if constexpr (MASKS) trunk<P, UMB, PIPE, FAST, NB, W>(st, smem, x, hid, carry, sign128);
-    else trunk<P, UMB, PIPE, FAST, NB, W>(st, smem, x, hid, carry);
+    else trunk<P, UMB, PIPE, FAST, NB, W, NoTrunkHook, R_L1>(st, smem, x, hid, carry);
     f32x16 head[NB];
 #ifdef DFN_MLP_FOLD_TU
     // static_sigma alone on h8, as the coarse kernel's last layer: it completes h8 (the carry-in of layer 8's last M-block) on the way.
@@ -314,7 +366,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     F (&fin)[NB][HC] = hid;
     {
       F dummy[NB][chunks_of<P>(16)];
-      layer<P, UMB, PIPE, NB, HC, 0, false, true, false, true, (CY ? 6 : -1), true, false, false, false, true, kHalfHeads>(st, smem, hid, dummy, head, norb, carry);
+      layer<P, UMB, PIPE, NB, HC, 0, false, true, false, R_SIG < 0, (CY ? 6 : -1), true, false, false, false, true, kHalfHeads, R_SIG>(st, smem, hid, dummy, head, norb, carry);
     }
 #else
     // xyz_encoding_final (no activation) + static_sigma
@@ -331,7 +383,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       const float* rb_dir[LP];
       ray_table(rb_dir, 0);
       layer<P, UMB, PIPE, NB, HC, MBQ, true, false, true, true, -1, true, CY>(st, smem, fin, de, head, rb_dir, carry);
-      layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE, (CY ? 2 : -1), true, false, false, false, true, kHalfHeads>(st, smem, de, dummy, head, norb, carry);
+      layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE && R_RGB < 0, (CY ? 2 : -1), true, false, false, false, true, kHalfHeads, R_RGB>(st, smem, de, dummy, head, norb, carry);
       sign64(16, de[0]);
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
@@ -370,13 +422,13 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #endif
         }
       }
-      layer<P, UMB, PIPE, NB, QC, MBQ, true, false, false, !MERGE, (CY ? 2 : -1), true, CY>(st, smem, t0, t1, head, norb, carry);
+      layer<P, UMB, PIPE, NB, QC, MBQ, true, false, false, !MERGE && R_TE1 < 0, (CY ? 2 : -1), true, CY, false, false, true, false, R_TE1>(st, smem, t0, t1, head, norb, carry);
       sign64(17, t0[0]);
-      layer<P, UMB, PIPE, NB, QC, MBQ, true, false, false, !MERGE, (CY ? 2 : -1), true, CY>(st, smem, t1, t0, head, norb, carry);
+      layer<P, UMB, PIPE, NB, QC, MBQ, true, false, false, !MERGE && R_TE2 < 0, (CY ? 2 : -1), true, CY, false, false, true, false, R_TE2>(st, smem, t1, t0, head, norb, carry);
       sign64(18, t1[0]);
-      layer<P, UMB, PIPE, NB, QC, MBQ, true, false, false, !MERGE, (CY ? 2 : -1), true, CY>(st, smem, t0, t1, head, norb, carry);
+      layer<P, UMB, PIPE, NB, QC, MBQ, true, false, false, !MERGE && R_TE3 < 0, (CY ? 2 : -1), true, CY, false, false, true, false, R_TE3>(st, smem, t0, t1, head, norb, carry);
       sign64(19, t0[0]);
-      layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE, (CY ? 2 : -1), true, false, false, false, true, NOBETA>(st, smem, t1, dummy, head, norb, carry);
+      layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE && R_THEAD < 0, (CY ? 2 : -1), true, false, false, false, true, NOBETA, R_THEAD>(st, smem, t1, dummy, head, norb, carry);
       sign64(20, t1[0]);
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
@@ -590,6 +642,36 @@ hipError_t launch_mlp_pts(bool fine, int prec, const MlpArgs& a, int n_cu, hipSt
               : launch_pts_one<PrecF32, false, 8, 1, 1, false, kWidth, false>(a, n_cu, stream);
 }
 #endif
+#elif defined(DFN_MLP_RES_TU)
+// variant 7's kernels: variant 6's geometry with the resident region behind the input slots.  coarse; fine with the compositing fused,
+// plain flavour -- the maps flavour stays with launch_mlp_half, the raw route with launch_mlp_fold.
+hipError_t launch_mlp_res(bool fine, const MlpResArgs& a, int n_cu, hipStream_t stream) {
+  using P = PrecX3M16;
+  constexpr int WAVES = 8, UMB = unit_mb<P>(0), NB = 1, PPT = WAVES * NB * 32;
+  const long long n_pts = (long long)a.n_rays * a.n_samples;
+  if (n_pts <= 0) return hipSuccess;
+  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
+  if (a.masks || (fine && !a.partial)) return hipErrorInvalidValue;
+  if (!a.res_blob || a.res_bytes != resident_bytes<P>(fine)) return hipErrorInvalidValue;   // the kernels copy exactly this many bytes
+  const long long n_tiles = (n_pts + PPT - 1) / PPT;
+  const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
+  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB>() + resident_bytes<P>(fine);
+  void (*kern)(MlpResArgs) = fine ? nerfh_fine_res_kernel<P, false, WAVES, UMB, NB, true> : nerfh_coarse_res_kernel<P, false, WAVES, UMB, NB, true>;
+  static bool attr_done[2] = {false, false};
+  if (!attr_done[fine]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    if (e != hipSuccess) return e;
+    attr_done[fine] = true;
+  }
+  MlpResArgs b = a;
+  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid, as launch_mlp
+    static int env = -1;
+    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
+    b.dma_waves = env > 0 ? env : 4;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
+  return hipGetLastError();
+}
 #elif defined(DFN_MLP_HALF_TU)
 // variant 6's kernels: variant 4's geometry (launch_one<PrecX3M16, false, 8, 2, 1, 1, true> below).  coarse; fine with the compositing
 // fused, plain or render-maps flavour -- the raw route (a.partial == nullptr) stays with launch_mlp_fold.

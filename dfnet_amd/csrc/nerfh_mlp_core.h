@@ -137,6 +137,19 @@ DFN_DEV void stage_prime(Stager& st, char* smem, uint32_t unit_stride, uint32_t 
   __syncthreads();
 }
 
+// Kernel variant 7: the resident layers (nerfh_layout.h: kFineResident / kCoarseResident) are copied into LDS ONCE per workgroup, by the
+// same DMA spread over the DMA waves, and read there by every tile.  Called right before stage_prime(), whose vmcnt(0) + barrier makes
+// the copy visible together with the first two units.  `bytes` is a whole number of pieces (the blob is zero-padded).
+// The ring needs no new argument: mid_sync() of streamed unit u still issues streamed unit u + 2 into the slot that held the previous
+// STREAMED unit, which every wave has left once it is past u's barrier -- a resident layer between two streamed units is computed
+// out of this region and touches no ring slot, and `st.u == 0` still names the tile's last streamed unit whether or not resident
+// layers follow it, so the wrap to the next tile (units 0 and 1 issued from the last two streamed units' mid_sync) is unchanged.
+DFN_DEV void stage_resident(const Stager& st, char* smem, const char* res_blob, uint32_t bytes, uint32_t lds_off) {
+  const char* src = res_blob + st.lane * 16;
+  if (st.wave >= st.dma_waves) return;
+  for (uint32_t p = st.wave * kPiece; p < bytes; p += st.dma_waves * kPiece) lds_dma_b128(src + p, smem + lds_off + p);
+}
+
 // Returns the LDS byte offset of unit st.u (already visible) and advances the rotation.
 DFN_DEV uint32_t open_unit(Stager& st) {
   const uint32_t cur = st.slot * st.ustride;
@@ -438,8 +451,11 @@ struct X3Piece {
 // ms = 0 (head_row_m16) and nothing of half 1 is read, so the unit holds and the loop runs the KC / 2 fragments with ms = 0 only (live
 // chunk kl = the 32-K chunk k32 = kl); head[] values c >= 4 come back as zeros.  The carried-in M-block is then converted inside
 // KC / 2 - 1 live chunks: see the hazard counts at the chunk body.
+// RES >= 0 (kernel variant 7): the layer's units sit back to back at LDS byte offset RES for the whole kernel (stage_resident), in the
+// unit format but without the rounding to pieces.  It is the NEWUNIT = false form with a compile-time base: no open_unit(), no
+// mid_sync(), the Stager is not touched; the fragment prefetch, bias reads, carry-in and conversion pieces are the streamed form's.
 template <class P, int UMB, bool PIPE, int NB, int KC, int MB, bool RELU, bool EXTRA, bool RAYBIAS, bool NEWUNIT,
-          int CIN, bool CIN_RELU, bool COUT, bool NOBIAS = false, bool SCALE_FIRST = false, bool TRACK = true, bool HALF = false>
+          int CIN, bool CIN_RELU, bool COUT, bool NOBIAS = false, bool SCALE_FIRST = false, bool TRACK = true, bool HALF = false, int RES = -1>
 DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][KC],
                    typename FragOf<P>::type (&Bout)[NB][(MB ? MB : 1) * chunks_of<P>(16)],
                    f32x16 (&head)[NB], const float* const (&raybias)[lane_pts<P>(NB)], f32x16 (&carry)[NB]) {
@@ -452,7 +468,8 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
   constexpr int PPKI = CIN > 0 ? (8 * NB + CIN - 1) / CIN : 0;  // same for the carried-in M-block
   static_assert(CIN < 0 || (PIPE && P::kSlotsPerChunk == 8 && CIN > 0 && CIN + 1 < KC + 1), "carry-in needs the pipelined f16 path");
   static_assert(!COUT || (PIPE && MB >= 1 && !EXTRA), "carry-out needs a regular last M-block");
-  static_assert(NEWUNIT || UMB >= TOT, "a layer that continues a unit must fit in it");
+  static_assert(NEWUNIT || UMB >= TOT || RES >= 0, "a layer that continues a unit must fit in it");
+  static_assert(RES < 0 || (!NEWUNIT && P::kM16), "a resident layer opens no staging unit");
   static_assert(!HALF || (P::kM16 && EXTRA && MB == 0 && !RAYBIAS && KC % 2 == 0 && CIN >= 2 && CIN % 2 == 0 && CIN + 2 == KC),
                 "a half-height block is a PrecX3M16 head layer whose last 32-K chunk is the carried-in M-block");
   constexpr int KCL = HALF ? KC / 2 : KC;      // fragments (chunks of the loop) per M-block
@@ -483,8 +500,9 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
     const int nt = nmb * KCL;
     uint32_t ub;
     if (NEWUNIT) { ub = open_unit(st); st.ubase = ub; st.uoff = 0; }
+    else if constexpr (RES >= 0) ub = uint32_t(RES) + u0 * (KCL * FB + 128);   // full units of UMB M-blocks precede unit u0 / UMB
     else ub = st.ubase + st.uoff;
-    st.uoff += nmb * KCL * FB + nmb * 128;
+    if constexpr (RES < 0) st.uoff += nmb * KCL * FB + nmb * 128;
     // split-f16 fragment = a hi plane (64 lanes x 16 B) followed by a lo plane: both reads stay lane-linear 16-byte
     const char* wl = smem + ub + st.lane * (P::kSplit ? 16 : P::kLaneBytes);
     const char* bl = smem + ub + nmb * KCL * FB + (P::kM16 ? g16 * 32 : h * 64);
@@ -805,7 +823,8 @@ DFN_DEV void posenc_xyz_m16(const float (&x)[2][3], int g, typename FragOf<P>::t
 struct NoTrunkHook {
   template <class A> DFN_DEV void operator()(int, A&) const {}
 };
-template <class P, int UMB, bool PIPE, bool FAST, int NB, int W = kWidth, class Hook = NoTrunkHook>
+// RES_L1 >= 0: layer 1 is LDS-resident at that offset (kernel variant 7's coarse kernel: layer<..., RES>).
+template <class P, int UMB, bool PIPE, bool FAST, int NB, int W = kWidth, class Hook = NoTrunkHook, int RES_L1 = -1>
 DFN_DEV void trunk(Stager& st, char* smem, const float (&x)[lane_pts<P>(NB)][3],
                    typename FragOf<P>::type (&out)[NB][chunks_of<P>(W / 2)], f32x16 (&carry)[NB], Hook hook = Hook()) {
   using F = typename FragOf<P>::type;
@@ -823,7 +842,7 @@ DFN_DEV void trunk(Stager& st, char* smem, const float (&x)[lane_pts<P>(NB)][3],
   };
   encode(x);
   F a[NB][HC], b[NB][HC];
-  layer<P, UMB, PIPE, NB, PC, MBW, true, false, false, true, -1, true, CY>(st, smem, pe, a, nohead, norb, carry);
+  layer<P, UMB, PIPE, NB, PC, MBW, true, false, false, RES_L1 < 0, -1, true, CY, false, false, true, false, RES_L1>(st, smem, pe, a, nohead, norb, carry);
   layer<P, UMB, PIPE, NB, HC, MBW, true, false, false, true, CI, true, CY>(st, smem, a, b, nohead, norb, carry);
   hook(0, a[0]);
   layer<P, UMB, PIPE, NB, HC, MBW, true, false, false, true, CI, true, CY>(st, smem, b, a, nohead, norb, carry);

@@ -13,7 +13,8 @@ the two flavours of the fine kernel.
   python tools/gpu_render_maps_ab.py --registers   no GPU: VGPR / SGPR / scratch / code bytes of every nerfh_fine_kernel instantiation in
                                                 dfnet_amd/csrc/build/nerfh_mlp.o, nerfh_mlp_maps.o, nerfh_mlp_fold.o (kernel variant 5's
                                                 nerfh_fine_fold_kernel) and nerfh_mlp_half.o (kernel variant 6's nerfh_fine_half_kernel and
-                                                nerfh_coarse_half_kernel); the fine kernels' last template argument is the maps flavour.
+                                                nerfh_coarse_half_kernel) and nerfh_mlp_res.o (kernel variant 7's nerfh_fine_res_kernel and
+                                                nerfh_coarse_res_kernel); the fine kernels' last template argument is the maps flavour.
                                                 Also every kernel of the points flavour (nerfh_*_pts_kernel: nerfh_mlp_pts.o,
                                                 nerfh_mlp_pts_fold.o, nerfh_mlp_pts_half.o, nerfh_bwd_pts.o).
   python tools/gpu_render_maps_ab.py --text-sha [nerfh_mlp.o ...]   no GPU: sha256 and size of the .text of each object's gfx950 code
@@ -34,7 +35,7 @@ sys.path.insert(0, ROOT)
 
 
 def registers():
-    for name in ("nerfh_mlp.o", "nerfh_mlp_maps.o", "nerfh_mlp_fold.o", "nerfh_mlp_half.o", "nerfh_mlp_pts.o", "nerfh_mlp_pts_fold.o",
+    for name in ("nerfh_mlp.o", "nerfh_mlp_maps.o", "nerfh_mlp_fold.o", "nerfh_mlp_half.o", "nerfh_mlp_res.o", "nerfh_mlp_pts.o", "nerfh_mlp_pts_fold.o",
                  "nerfh_mlp_pts_half.o", "nerfh_bwd_pts.o"):
         registers_of(os.path.join(ROOT, "dfnet_amd", "csrc", "build", name))
 
@@ -70,7 +71,8 @@ def registers_of(obj):
     for blk in notes.split("- .agpr_count:")[1:]:
         g = lambda k: re.search(r"\." + k + r":\s+(\S+)", blk).group(1)
         name = g("name")
-        if not any(k in name for k in ("nerfh_fine_kernel", "nerfh_fine_fold_kernel", "nerfh_fine_half_kernel", "nerfh_coarse_half_kernel", "_pts_kernel")):
+        if not any(k in name for k in ("nerfh_fine_kernel", "nerfh_fine_fold_kernel", "nerfh_fine_half_kernel", "nerfh_coarse_half_kernel", "nerfh_fine_res_kernel",
+                                       "nerfh_coarse_res_kernel", "_pts_kernel")):
             continue
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().replace("dfn::", "")
         print(json.dumps(dict(kernel=dem, vgpr=int(g("vgpr_count")), sgpr=int(g("sgpr_count")), scratch_bytes=int(g("private_segment_fixed_size")),
