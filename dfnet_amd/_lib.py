@@ -51,6 +51,12 @@ class TrainMapGrads(Structure):
                 ("disp0", c_void_p), ("acc0", c_void_p), ("depth0", c_void_p)]
 
 
+class FrameMapsOut(Structure):
+    """dfn_frame_maps_out (include/dfnet_hip.h): quantised planes of dfn_frame_post_maps, NULL = not wanted"""
+    _fields_ = [("depth16", c_void_p), ("depth_static16", c_void_p), ("beta8", c_void_p), ("rgb_static8", c_void_p),
+                ("rgb_transient8", c_void_p)]
+
+
 MAP_NAMES = tuple(n for n, _ in RenderMaps._fields_)   # trailing shape: () for the first three, (3,) for the rgb_* maps
 
 
@@ -136,6 +142,9 @@ SIGNATURES = {
     "dfn_frame_prep": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "dfn_frame_post_scratch_bytes": (c_size_t, [c_int]),
     "dfn_frame_post": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "dfn_frame_post_maps_scratch_bytes": (c_size_t, [c_int]),
+    "dfn_frame_post_maps": (c_int, [POINTER(RenderMaps), _P, c_int, c_int, c_int, c_int, c_float, c_float, POINTER(FrameMapsOut), _P, _P,
+                                    _P, _P]),
     "dfn_dfnet_forward_train_pyramid": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "dfn_dfnet_triplet_pyramid_state_bytes": (c_size_t, [_P, c_int, c_int]),
     "dfn_dfnet_triplet_pyramid_forward": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, c_size_t, _P,

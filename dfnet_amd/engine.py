@@ -1118,3 +1118,44 @@ def frame_post(rgb, disp, gt=None, want_gt8=True):
     check(lib.dfn_frame_post(ptr(rgb), ptr(disp), ptr(gt), 1 if per_frame else 0, n, H, W, raw(rgb8), raw(disp8), raw(gt8), ptr(mse),
                              ptr(dmax), raw(scratch), current_stream()), "dfn_frame_post")
     return {"rgb8": rgb8, "disp8": disp8, "gt8": gt8, "mse": mse, "disp_max": dmax}
+
+
+def frame_post_maps(maps, near, far, gt=None, want=None):
+    """render_path's per-frame back-end for the render maps on the device (dfn_frame_post_maps).  maps: {name: fp32 CUDA tensor} with names out
+    of MAP_NAMES, depth / depth_static / beta [n,H,W], rgb_static / rgb_transient [n,H,W,3]; gt None | [n,H,W,3] | [H,W,3] as in frame_post;
+    want: the names to quantise (None = every given one).  Returns a dict with, for what the names and gt allow: depth16, depth_static16
+    uint16 [n,H,W] on the fixed scale (d - near) / (far - near); beta8 uint8 [n,H,W] with beta_max fp32 [n]; rgb_static8, rgb_transient8
+    uint8 [n,H,W,3]; mse_static fp32 [n] (rgb_static against gt)."""
+    lib = _lib.load()
+    names = map_names(tuple(maps))
+    want = names if want is None else map_names(want)
+    missing = [m for m in want if m not in names]
+    if missing:
+        raise ValueError(f"frame_post_maps: {missing} wanted but not among the given maps {list(names)}")
+    if not names:
+        return {}
+    held = {m: _f32c(maps[m]) for m in names}
+    n, H, W = held[names[0]].shape[:3]
+    for m, t in held.items():
+        if tuple(t.shape) != ((n, H, W, 3) if m.startswith("rgb_") else (n, H, W)):
+            raise ValueError(f"frame_post_maps: {m} has shape {tuple(t.shape)}, expected [{n},{H},{W}" + (",3]" if m.startswith("rgb_") else "]"))
+    dev = held[names[0]].device
+    per_frame = gt is not None and gt.dim() == 4
+    if gt is not None:
+        gt = _f32c(gt)
+    suffix = lambda m: "16" if m.startswith("depth") else "8"
+    res = {m + suffix(m): torch.empty(held[m].shape, dtype=torch.uint16 if suffix(m) == "16" else torch.uint8, device=dev) for m in want}
+    if "beta" in want:
+        res["beta_max"] = torch.empty(n, device=dev)
+    if gt is not None and "rgb_static" in want:
+        res["mse_static"] = torch.empty(n, device=dev)
+    if not res:
+        return res
+    scratch = torch.empty(lib.dfn_frame_post_maps_scratch_bytes(n), dtype=torch.uint8, device=dev)
+    raw = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    m_in = _lib.RenderMaps(**{m: t.data_ptr() for m, t in held.items()})
+    m_out = _lib.FrameMapsOut(**{m + suffix(m): res[m + suffix(m)].data_ptr() for m in want})
+    check(lib.dfn_frame_post_maps(ctypes.byref(m_in), ptr(gt) if "mse_static" in res else None, 1 if per_frame else 0, n, H, W, float(near),
+                                  float(far), ctypes.byref(m_out), raw(res.get("beta_max")), raw(res.get("mse_static")), raw(scratch),
+                                  current_stream()), "dfn_frame_post_maps")
+    return res

@@ -72,6 +72,9 @@ _T = [
     ("precision", "str", "f16x3", "nfd"),      # MFMA arithmetic of the HIP path: f16x3 (split-f16: fp32-grade, the default — the
                                                # reference computes in fp32) | f32 (exact fp32 MFMA) | f16 (fast; inside north_star's 1e-3
                                                # on random-init weights ONLY: 1e-2-level worst pixels on trained checkpoints)
+    ("render_maps", "str", "", "nfd"),         # render maps of --render_test / render_path beside rgb and disparity: "" (off) | all |
+                                               # a comma-separated list out of depth, depth_static, beta, rgb_static, rgb_transient
+                                               # (render_map_names below turns the value into render_path's ret_maps)
 ]
 _TYPES = {"int": int, "float": float, "str": str}
 
@@ -163,6 +166,16 @@ def feature_parser():
 def dm_parser():
     """Flags of train.py (/root/reference/script/dm/options.py)."""
     return _build("d")
+
+
+def render_map_names(value):
+    """--render_maps as render_path's ret_maps: "" -> () (off), "all" -> the five maps, otherwise the comma-separated names in the
+    library's order; an unknown name raises engine.map_names' ValueError."""
+    from .engine import map_names
+    value = (value or "").strip()
+    if value == "all":
+        return map_names(True)
+    return map_names(tuple(s.strip() for s in value.split(",") if s.strip()))
 
 
 config_parser = nerf_parser  # the name every reference options module exports

@@ -397,42 +397,66 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     return _shaped(lead, *out[:3], extras)
 
 
+def _png_bytes(arr):
+    """A PNG file as bytes from the minimal zlib writer (level 6, filter 0): uint8 gray [H,W] or RGB [H,W,3], or uint16 gray [H,W]
+    (bit depth 16, big-endian samples)."""
+    import struct
+    import zlib
+    a = np.ascontiguousarray(arr)
+    h, w = a.shape[:2]
+    ctype, depth = (2 if a.ndim == 3 else 0), 8
+    if a.dtype == np.uint16:
+        if a.ndim != 2:
+            raise ValueError(f"16-bit PNGs are gray [H,W], got shape {a.shape}")
+        a, depth = a.astype(">u2"), 16
+    raw = b"".join(b"\x00" + a[r].tobytes() for r in range(h))
+    chunk = lambda t, d: struct.pack(">I", len(d)) + t + d + struct.pack(">I", zlib.crc32(t + d) & 0xffffffff)
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, depth, ctype, 0, 0, 0)) +
+            chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
 def _write_png(path, arr8):
+    """uint8 gray / RGB, or uint16 gray (PIL mode I;16), to `path`; PIL's default zlib level is 6 as well."""
     try:
         from PIL import Image
         Image.fromarray(arr8).save(path)
-    except ImportError:  # minimal zlib PNG writer (8-bit gray or RGB)
-        import struct
-        import zlib
-        a = np.ascontiguousarray(arr8)
-        h, w = a.shape[:2]
-        ctype = 2 if a.ndim == 3 else 0
-        raw = b"".join(b"\x00" + a[r].tobytes() for r in range(h))
-        chunk = lambda t, d: struct.pack(">I", len(d)) + t + d + struct.pack(">I", zlib.crc32(t + d) & 0xffffffff)
+    except ImportError:  # minimal zlib PNG writer
         with open(path, "wb") as fh:
-            fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, ctype, 0, 0, 0)) +
-                     chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+            fh.write(_png_bytes(arr8))
 
 
 POST_BATCH = 16     # frames per dfn_frame_post call / device -> host copy / PNG job
 PNG_WORKERS = 8     # host threads encoding PNGs while the GPU renders on (zlib releases the GIL)
 
+# render map -> (its quantised plane out of engine.frame_post_maps, the PNG's suffix): 16-bit gray depths on the fixed near..far scale,
+# 8-bit gray beta / max(beta), 8-bit RGB colours
+MAP_PNGS = {"depth": ("depth16", "_depth"), "depth_static": ("depth_static16", "_depth_static"), "beta": ("beta8", "_beta"),
+            "rgb_static": ("rgb_static8", "_static"), "rgb_transient": ("rgb_transient8", "_transient")}
 
-def _write_frames(ev, host, savedir, first):
+
+def _write_frames(ev, host, savedir, first, maps_host=None):
     """PNG job of one batch (runs on a pool thread): wait for the batch's device -> host copy, then `{:03d}.png`,
-    `{:03d}_GT.png`, `{:03d}_disp.png` per frame, numbered by GLOBAL frame index (rendering.py:438-452)."""
+    `{:03d}_GT.png`, `{:03d}_disp.png` per frame, numbered by GLOBAL frame index (rendering.py:438-452).  maps_host: {map name: quantised
+    host tensor [n, ...]} of render_path(ret_maps=...) -> `{:03d}_depth.png` ... per MAP_PNGS as well."""
     ev.synchronize()
     rgb8, disp8, gt8 = (None if t is None else t.numpy() for t in host)
+    planes = {m: t.numpy() for m, t in (maps_host or {}).items()}
     for k in range(rgb8.shape[0]):
         i = first + k
         _write_png(os.path.join(savedir, '{:03d}.png'.format(i)), rgb8[k])
         if gt8 is not None:
             _write_png(os.path.join(savedir, '{:03d}_GT.png'.format(i)), gt8[k] if gt8.ndim == 4 else gt8)
         _write_png(os.path.join(savedir, '{:03d}_disp.png'.format(i)), disp8[k])
+        for m, a in planes.items():
+            _write_png(os.path.join(savedir, '{:03d}{}.png'.format(i, MAP_PNGS[m][1])), a[k])
+
+
+def _map_tail(m, H, W):
+    return (H, W, 3) if m.startswith("rgb_") else (H, W)
 
 
 def render_path(args, render_poses, hwf, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0,
-                single_gt_img=False, img_ids=torch.Tensor(0)):
+                single_gt_img=False, img_ids=torch.Tensor(0), ret_maps=False):
     """Drop-in for rendering.py:403-458: returns (rgbs [N,H,W,3], disps [N,H,W]) as float32 numpy.
 
     With torch.distributed initialised (world > 1) each rank renders its contiguous block of frames.  The per-frame back-end
@@ -440,9 +464,17 @@ def render_path(args, render_poses, hwf, chunk, render_kwargs, gt_imgs=None, sav
     of POST_BATCH frames (dfn_frame_post); what comes back to the host is uint8, and EVERY RANK writes the PNGs of its own
     block (`{:03d}.png`, `{:03d}_GT.png`, `{:03d}_disp.png` by global frame index) on a thread pool while its GPU renders the
     next batch.  One gather at the end brings the fp32 frames (the returned arrays) and the per-frame errors to rank 0, which
-    prints the mean PSNR; ranks != 0 return (None, None)."""
+    prints the mean PSNR; ranks != 0 return (None, None).
+
+    ret_maps (beyond the reference): True, or an iterable of names out of depth, depth_static, beta, rgb_static, rgb_transient — every frame
+    is rendered with render(ret_maps=names) (rgb and disp keep their bits), the maps ride beside rgbs / disps through the same gather,
+    and the return value becomes (rgbs, disps, {name: float32 numpy [N,H,W] / [N,H,W,3]}) on rank 0, (None, None, None) elsewhere.  With
+    savedir their PNGs (MAP_PNGS; dfn_frame_post_maps per batch: depths 16-bit gray on the fixed near..far scale of render_kwargs, beta /
+    max(beta) 8-bit gray, the colours 8-bit RGB) are written by the same pool job; with gt_imgs and rgb_static the static-only PSNR is
+    printed too."""
     from concurrent.futures import ThreadPoolExecutor
     from . import engine as eng
+    names = eng.map_names(ret_maps)
     H, W, focal = hwf
     if render_factor != 0:
         H, W, focal = int(H // render_factor), int(W // render_factor), focal / render_factor
@@ -453,12 +485,19 @@ def render_path(args, render_poses, hwf, chunk, render_kwargs, gt_imgs=None, sav
     N = render_poses.shape[0]
     rank, world = ddist.rank_world()
     if ddist.active() and ddist.band_mode(N, world):
-        return _render_path_bands(render_poses, img_ids, H, W, focal, chunk, render_kwargs, gt_imgs, savedir, single_gt_img)
+        return _render_path_bands(render_poses, img_ids, H, W, focal, chunk, render_kwargs, gt_imgs, savedir, single_gt_img, names)
     lo, hi = ddist.frame_block(N, rank, world)
     n_loc = hi - lo
+    near, far = float(render_kwargs.get('near', 0.)), float(render_kwargs.get('far', 1.))   # render()'s own defaults
+    static_psnr = "rgb_static" in names and gt_imgs is not None
     # rank 0 renders straight into its block of the final [N, ...] tensors: the end gather receives the other blocks in place
-    outs, (rgbs, disps, mse) = ddist.root_buffers([(H, W, 3), (H, W), ()], N, dev)
+    outs, bufs = ddist.root_buffers([(H, W, 3), (H, W), ()] + [_map_tail(m, H, W) for m in names] + [()] * static_psnr, N, dev)
+    rgbs, disps, mse = bufs[:3]
+    mbufs = dict(zip(names, bufs[3:]))
     mse.zero_()
+    if static_psnr:
+        bufs[-1].zero_()
+    frame_kwargs = dict(render_kwargs, ret_maps=names) if names else render_kwargs   # the same call per frame, with the maps named
     gt_one = None
     if gt_imgs is not None and single_gt_img:
         gt_one = torch.as_tensor(np.asarray(gt_imgs), dtype=torch.float32).to(dev)
@@ -470,9 +509,11 @@ def render_path(args, render_poses, hwf, chunk, render_kwargs, gt_imgs=None, sav
         j1 = min(n_loc, j0 + POST_BATCH)
         for j in range(j0, j1):
             i = lo + j
-            rgb, disp, _, _ = render(H, W, focal, chunk=chunk, c2w=render_poses[i][:3, :4], img_idx=img_ids[i], **render_kwargs)
+            rgb, disp, _, extras = render(H, W, focal, chunk=chunk, c2w=render_poses[i][:3, :4], img_idx=img_ids[i], **frame_kwargs)
             rgbs[j].copy_(rgb)
             disps[j].copy_(disp)
+            for m in names:
+                mbufs[m][j].copy_(extras[m])
             if i == 0:
                 print(rgb.shape, disp.shape)
         if savedir is None and gt_imgs is None:
@@ -484,13 +525,19 @@ def render_path(args, render_poses, hwf, chunk, render_kwargs, gt_imgs=None, sav
         post = eng.frame_post(rgbs[j0:j1], disps[j0:j1], gt, want_gt8=savedir is not None)
         if gt is not None:
             mse[j0:j1].copy_(post["mse"])
+        if names and (savedir is not None or static_psnr):   # without a save directory only the static-only error is needed
+            mpost = eng.frame_post_maps({m: mbufs[m][j0:j1] for m in names}, near, far, gt, want=None if savedir is not None else ("rgb_static",))
+            if static_psnr:
+                bufs[-1][j0:j1].copy_(mpost["mse_static"])
         if savedir is not None:
             host = []
             for t in (post["rgb8"], post["disp8"], post["gt8"]):
                 host.append(None if t is None else torch.empty(t.shape, dtype=torch.uint8, pin_memory=True).copy_(t, non_blocking=True))
+            mhost = {m: torch.empty(mpost[MAP_PNGS[m][0]].shape, dtype=mpost[MAP_PNGS[m][0]].dtype, pin_memory=True)
+                     .copy_(mpost[MAP_PNGS[m][0]], non_blocking=True) for m in names}
             ev = torch.cuda.Event()
             ev.record()
-            jobs.append(pool.submit(_write_frames, ev, host, savedir, lo + j0))
+            jobs.append(pool.submit(_write_frames, ev, host, savedir, lo + j0, mhost))
         t_post += time.time() - tp
     torch.cuda.synchronize()
     t_render = time.time() - t0
@@ -503,7 +550,7 @@ def render_path(args, render_poses, hwf, chunk, render_kwargs, gt_imgs=None, sav
     all_flags = [my_flags]
     tg = time.time()
     try:
-        (all_rgb, all_disp, all_mse), _ = ddist.gather_frames_direct([rgbs, disps, mse], N, outs=outs)   # the path's ONE data collective
+        (all_rgb, all_disp, all_mse, *all_more), _ = ddist.gather_frames_direct(bufs, N, outs=outs)   # the path's ONE data collective
         all_flags = ddist.all_gather_flags(my_flags, dev)
         torch.cuda.synchronize()
     finally:
@@ -528,31 +575,42 @@ def render_path(args, render_poses, hwf, chunk, render_kwargs, gt_imgs=None, sav
                           "render_path: ranks " + ", ".join(f"{r} (flags {f:#x})" for r, f in enumerate(all_flags) if f))
     if gt_imgs is None:
         all_mse = None
-    n_gathered = ddist.gathered_bytes([rgbs, disps, mse], N)
+    n_gathered = ddist.gathered_bytes(bufs, N)
     if rank != 0:
-        return None, None
+        return (None, None, None) if names else (None, None)
     rgbs = all_rgb.cpu().numpy()
     disps = all_disp.cpu().numpy()
+    maps = {m: t.cpu().numpy() for m, t in zip(names, all_more)}
     print(f"rendered {N} frames of {W}x{H} on {world} GPU(s) in {t_render:.2f} s (post-processing launches {t_post:.2f} s inside it, "
           f"PNG tail after the last frame {t_tail:.2f} s)")
     if all_mse is not None:
         psnr = -10. * np.log10(all_mse.cpu().numpy())
         print("Mean PSNR of this run is:", np.mean(psnr, 0))
+        if static_psnr:   # the transient-free render against the same ground truth
+            print("Mean static-only PSNR of this run is:", np.mean(-10. * np.log10(all_more[-1].cpu().numpy()), 0))
     render_path.last_timing = {"render_s": t_render, "post_launch_s": t_post, "gather_s": t_gather, "png_tail_s": t_tail, "frames": N, "world": world,
                                "gathered_bytes": n_gathered}
+    if names:
+        render_path.last_timing["maps"] = list(names)
+        return rgbs, disps, maps
     return rgbs, disps
 
 
-def render_band(H, W, focal, chunk, c2w, img_idx, r0, r1, render_kwargs):
+def render_band(H, W, focal, chunk, c2w, img_idx, r0, r1, render_kwargs, ret_maps=()):
     """Rows [r0, r1) of the frame at pose c2w: the band's rays out of get_rays (models/ray_utils.py:5-15) through render(rays=...).
-    Rays are independent, so a band is bit-identical to the same rows of the full-frame render (tests/test_gpu_dist.py)."""
+    Rays are independent, so a band is bit-identical to the same rows of the full-frame render (tests/test_gpu_dist.py).
+    ret_maps naming render maps: (rgb, disp, {name: the band's map}) — the same rows of the full frame's maps, bit for bit."""
+    from .engine import map_names
+    names = map_names(ret_maps)
     rays_o, rays_d = get_rays(H, W, focal, c2w)
-    rgb, disp, _, _ = render(H, W, focal, chunk=chunk, rays=(rays_o[r0:r1].contiguous(), rays_d[r0:r1].contiguous()), img_idx=img_idx,
-                             **render_kwargs)
+    rgb, disp, _, extras = render(H, W, focal, chunk=chunk, rays=(rays_o[r0:r1].contiguous(), rays_d[r0:r1].contiguous()), img_idx=img_idx,
+                                  **(dict(render_kwargs, ret_maps=names) if names else render_kwargs))
+    if names:
+        return rgb, disp, {m: extras[m] for m in names}
     return rgb, disp
 
 
-def _render_path_bands(render_poses, img_ids, H, W, focal, chunk, render_kwargs, gt_imgs, savedir, single_gt_img):
+def _render_path_bands(render_poses, img_ids, H, W, focal, chunk, render_kwargs, gt_imgs, savedir, single_gt_img, names=()):
     """SURVEY 8(e)'s small-batch fallback of render_path — fewer frames than ranks (the single validation frames of run_nerf.py:200,228;
     configs[0]'s four frames on eight GPUs): every rank renders ONE row band of one frame (dist.band_unit), the bands are gathered in
     place into rank 0's final [N, H, ...] tensors (dist.gather_bands_direct: the same single grouped send / receive batch), and the
@@ -565,9 +623,11 @@ def _render_path_bands(render_poses, img_ids, H, W, focal, chunk, render_kwargs,
     f, r0, r1 = ddist.band_unit(N, H, rank, world)
     t0 = time.time()
     if r1 > r0:
-        rgb, disp = render_band(H, W, focal, chunk, render_poses[f][:3, :4], img_ids[f], r0, r1, render_kwargs)
+        rgb, disp, *band_maps = render_band(H, W, focal, chunk, render_poses[f][:3, :4], img_ids[f], r0, r1, render_kwargs, names)
+        band_maps = [band_maps[0][m] for m in names]
     else:   # more ranks on this frame than rows
         rgb, disp = torch.empty(0, W, 3, device=dev), torch.empty(0, W, device=dev)
+        band_maps = [torch.empty((0,) + _map_tail(m, H, W)[1:], device=dev) for m in names]
     if rank == 0:
         print(torch.Size([H, W, 3]), torch.Size([H, W]))
     torch.cuda.synchronize() if dev.type == "cuda" else None
@@ -575,7 +635,7 @@ def _render_path_bands(render_poses, img_ids, H, W, focal, chunk, render_kwargs,
     eng_h = _engine_of(render_kwargs)
     my_flags = eng_h.range_flags()
     tg = time.time()
-    all_rgb, all_disp = ddist.gather_bands_direct([rgb, disp], N, H)      # the path's ONE data collective
+    all_rgb, all_disp, *all_maps = ddist.gather_bands_direct([rgb, disp] + band_maps, N, H)      # the path's ONE data collective
     all_flags = ddist.all_gather_flags(my_flags, dev)
     t_gather = time.time() - tg
     bad = 0
@@ -584,9 +644,9 @@ def _render_path_bands(render_poses, img_ids, H, W, focal, chunk, render_kwargs,
     if bad:   # the same message on every rank, after the collective
         eng_h.raise_range(bad, where="render_path (row bands): ranks " + ", ".join(f"{r} (flags {fl:#x})" for r, fl in enumerate(all_flags) if fl))
     if rank != 0:
-        return None, None
+        return (None, None, None) if names else (None, None)
     tp = time.time()
-    mse = None
+    mse = mse_static = None
     if savedir is not None or gt_imgs is not None:
         gt = None
         if gt_imgs is not None:
@@ -594,22 +654,33 @@ def _render_path_bands(render_poses, img_ids, H, W, focal, chunk, render_kwargs,
             gt = torch.as_tensor(g if single_gt_img else g[:N], dtype=torch.float32).to(dev)
         post = eng.frame_post(all_rgb, all_disp, gt, want_gt8=savedir is not None)
         mse = post["mse"] if gt is not None else None
+        mhost = {}
+        if names:   # the maps' back-end on the assembled frames too: beta's maximum is the whole frame's
+            mpost = eng.frame_post_maps(dict(zip(names, all_maps)), float(render_kwargs.get('near', 0.)), float(render_kwargs.get('far', 1.)), gt)
+            mse_static = mpost.get("mse_static")
+            mhost = {m: mpost[MAP_PNGS[m][0]].cpu() for m in names} if savedir is not None else {}
         if savedir is not None:
             host = [None if t is None else t.cpu() for t in (post["rgb8"], post["disp8"], post["gt8"])]
 
             class _Done:
                 def synchronize(self):
                     pass
-            _write_frames(_Done(), host, savedir, 0)
+            _write_frames(_Done(), host, savedir, 0, mhost)
     t_post = time.time() - tp
     print(f"rendered {N} frames of {W}x{H} as row bands on {world} GPU(s) in {t_render:.2f} s (gather {t_gather:.2f} s, frame back-end on "
           f"rank 0 {t_post:.2f} s)")
     if mse is not None:
         print("Mean PSNR of this run is:", np.mean(-10. * np.log10(mse.cpu().numpy()), 0))
-    per_frame = (H * W * 4) * 4
+    if mse_static is not None:
+        print("Mean static-only PSNR of this run is:", np.mean(-10. * np.log10(mse_static.cpu().numpy()), 0))
+    per_pixel = 4 + sum(3 if m.startswith("rgb_") else 1 for m in names)   # floats: rgb + disp (+ the maps)
+    per_frame = (H * W * per_pixel) * 4
     own = r1 - r0
     render_path.last_timing = {"render_s": t_render, "post_launch_s": t_post, "gather_s": t_gather, "png_tail_s": 0.0, "frames": N, "world": world,
-                               "gathered_bytes": N * per_frame - own * W * 16, "row_bands": True}
+                               "gathered_bytes": N * per_frame - own * W * per_pixel * 4, "row_bands": True}
+    if names:
+        render_path.last_timing["maps"] = list(names)
+        return all_rgb.cpu().numpy(), all_disp.cpu().numpy(), {m: t.cpu().numpy() for m, t in zip(names, all_maps)}
     return all_rgb.cpu().numpy(), all_disp.cpu().numpy()
 
 
@@ -628,7 +699,9 @@ def _drain(dl):
 def render_test(args, train_dl, val_dl, hwf, start, render_kwargs_test, decoder_coarse=None, decoder_fine=None):
     """Drop-in for rendering.py:460-530: render the train split then the val split, write PNGs under
     basedir/expname/evaluate_{train,val}_{test|path}_{start:06d}."""
+    from .options import render_map_names
     tag = 'test' if args.render_test else 'path'
+    maps = render_map_names(getattr(args, 'render_maps', ''))   # --render_maps: () = off, exactly the call without the keyword
     for name, dl in (("train", train_dl), ("val", val_dl)):
         savedir = os.path.join(args.basedir, args.expname, 'evaluate_{}_{}_{:06d}'.format(name, tag, start))
         os.makedirs(savedir, exist_ok=True)
@@ -636,6 +709,6 @@ def render_test(args, train_dl, val_dl, hwf, start, render_kwargs_test, decoder_
         print(f'{name} poses shape', poses.shape)
         with torch.no_grad():
             render_path(args, poses, hwf, args.chunk, render_kwargs_test, gt_imgs=images, savedir=savedir,
-                        img_ids=index)
+                        img_ids=index, ret_maps=maps)
         print(f'Saved {name} set')
     return

@@ -445,6 +445,30 @@ size_t dfn_frame_post_scratch_bytes(int n_frames);
 int dfn_frame_post(const float* rgb, const float* disp, const float* gt, int gt_per_frame, int n_frames, int H, int W,
                    uint8_t* rgb8, uint8_t* disp8, uint8_t* gt8, float* mse, float* disp_max, void* scratch, void* stream);
 
+/* ---- the same back-end for the render maps (dfn_render_maps: what render_path(ret_maps=...) renders beside rgb and disp; the maps are
+ * rendering.py:196-241's, the conversions follow rendering.py:423-452: to8b, x / max(x) per frame, the PSNR's squared error).
+ *
+ * maps: device fp32, depth / depth_static / beta [n, H, W], rgb_static / rgb_transient [n, H, W, 3], every member optional; gt and
+ * gt_per_frame as in dfn_frame_post (gt may be NULL).  Outputs, device, every member of `out` optional (NULL = not wanted):
+ *   depth16, depth_static16 [n, H, W] uint16 = (uint16)(int)(65535 * clip((d - near) / (far - near), 0, 1)): a FIXED scale, so the
+ *                            image is metric and comparable across frames and ranks (NaN -> 0)
+ *   beta8          [n, H, W]    uint8 = to8b(beta / max(beta over the frame)), the convention of disp8
+ *   rgb_static8, rgb_transient8 [n, H, W, 3] uint8 = to8b, the truncating conversion of dfn_frame_post
+ *   beta_max   (optional, needs maps->beta) fp32 [n]: that maximum
+ *   mse_static (optional, needs gt and maps->rgb_static) fp32 [n] = mean((rgb_static - gt)^2) per frame (fp32 differences, fp64 sum):
+ *              the PSNR of the transient-free render
+ * All arithmetic fp32, every operation rounded on its own, IEEE division.  DFN_ERR_ARG: an `out` member without its `maps` member,
+ * beta8 / beta_max without maps->beta, mse_static without gt or maps->rgb_static, far <= near, n_frames outside 0..65535, H < 1,
+ * W < 1, scratch NULL.  n_frames == 0 is DFN_OK; nothing asked for launches nothing; the maximum pass runs only for beta.
+ * scratch: dfn_frame_post_maps_scratch_bytes(n_frames) of device memory (zeroed by the call). */
+typedef struct {
+  uint16_t *depth16, *depth_static16;
+  uint8_t *beta8, *rgb_static8, *rgb_transient8;
+} dfn_frame_maps_out;
+size_t dfn_frame_post_maps_scratch_bytes(int n_frames);
+int dfn_frame_post_maps(const dfn_render_maps* maps, const float* gt, int gt_per_frame, int n_frames, int H, int W, float near,
+                        float far, const dfn_frame_maps_out* out, float* beta_max, float* mse_static, void* scratch, void* stream);
+
 /* ---- the triplet loss of DFNet's training on the two feature stacks (feature/misc.py:355-435), fused.
  *
  * f1 (anchor, the rendered stream in run_feature.py:155) and f2 (positive, the target stream): fp32 device stacks
