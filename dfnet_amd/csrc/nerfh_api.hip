@@ -133,6 +133,7 @@ extern "C" int dfn_nerfh_destroy(dfn_nerfh_t h) {
   for (hipEvent_t e : h->side_ev) if (e) (void)hipEventDestroy(e);
   if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
   if (h->range_flag) (void)hipFree(h->range_flag);
+  if (h->tile_counter) (void)hipFree(h->tile_counter);
   delete h;
   return DFN_OK;
 }
@@ -559,6 +560,12 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
     }
     if (hipMemset(h->range_flag, 0, 3 * sizeof(int)) != hipSuccess) return set_error(DFN_ERR_HIP, "dfn_nerfh_commit: clearing the range-guard flag failed");
   }
+  if (!h->tile_counter) {   // kernel variant 8: the tile heads of the coarse and the fine kernel (zeroed in front of every pass that claims from them)
+    if (hipMalloc(reinterpret_cast<void**>(&h->tile_counter), 2 * sizeof(uint32_t)) != hipSuccess) {
+      h->tile_counter = nullptr;
+      return set_error(DFN_ERR_HIP, "dfn_nerfh_commit: allocating the tile counters failed");
+    }
+  }
   {  // generic-width path: plain device copies in canonical order
     std::vector<float> all;
     std::vector<size_t> offs;
@@ -829,21 +836,34 @@ static int check_grad_prec(int prec, const char* fn) {
   return DFN_OK;
 }
 
-// Kernel variant: DFN_MLP_VARIANT=0..7 (A/B aid, see nerfh_layout.h).  Default 7: split-f16 on 16x16x32 MFMAs (f16 / exact fp32 run their
+// Kernel variant: DFN_MLP_VARIANT=0..8 (A/B aid, see nerfh_layout.h).  Variant 7: split-f16 on 16x16x32 MFMAs (f16 / exact fp32 run their
 // variant-0 kernels under it) with the fine render kernel's tail folded (fold_fine, base_variant), half-height head blocks in the
 // render kernels (half_heads) and the small tail layers resident in LDS in the coarse and the plain fused fine kernel (resident_layers);
 // DFN_MLP_VARIANT=6 is the same with every layer streamed, DFN_MLP_VARIANT=5 also with full-height head blocks, DFN_MLP_VARIANT=4 also
-// without the fold, DFN_MLP_VARIANT=0 keeps the 32x32x16 split-f16 kernels.
+// without the fold, DFN_MLP_VARIANT=0 keeps the 32x32x16 split-f16 kernels.  What a process runs without DFN_MLP_VARIANT is variant 8
+// (kSelectedByDefault): variant 7 with the tiles of its two kernels claimed from a device counter; it resolves to kDefaultVariant
+// everywhere else (resolved_variant), and DFN_MLP_VARIANT=7 keeps the dealt tiles.
 constexpr int kDefaultVariant = kResidentVariant;
+constexpr int kSelectedByDefault = kDynVariant;
 static int mlp_variant_128();
 static int mlp_variant_of(dfn_nerfh_t h) { return h->desc.width == kWidth ? mlp_variant_128() : 0; }
 static int mlp_variant_128() {
   static int v = -1;
   if (v < 0) {
     const char* e = getenv("DFN_MLP_VARIANT");
-    v = (e && e[0] >= '0' && e[0] < '0' + kVariants) ? e[0] - '0' : kDefaultVariant;
+    v = (e && e[0] >= '0' && e[0] <= '0' + kDynVariant) ? e[0] - '0' : kSelectedByDefault;
   }
   return v;
+}
+// Variant 8 is variant 7 with the tiles of the two kernels launch_mlp_res has claimed from a device counter (launch_mlp_dyn, on variant
+// 7's networks): it is folded into variant 7 wherever a variant is resolved, and dyn_tiles() says which launcher those two kernels get.
+static bool dyn_tiles(dfn_nerfh_t h) { return mlp_variant_of(h) == kDynVariant; }
+static int resolved_variant(dfn_nerfh_t h) { return dyn_tiles(h) ? kResidentVariant : mlp_variant_of(h); }
+static MlpDynArgs dyn_args(const MlpResArgs& r, uint32_t* counter) {
+  MlpDynArgs d{};
+  static_cast<MlpResArgs&>(d) = r;
+  d.tile_counter = counter;
+  return d;
 }
 // Variant 5 differs from variant 4 in ONE kernel: the split-f16 netwidth-128 fine render kernel (launch_mlp_fold), which reads its own
 // packed network (net[1][F16X3][5]) and a per-ray table written from rb_fold.  Every other launch under it, the gradient paths' forward
@@ -891,14 +911,17 @@ extern "C" int dfn_mlp_coarse(dfn_nerfh_t h, int prec, const float* rays_o, cons
   if (int rc = check_net(h, prec, "dfn_mlp_coarse", true)) return rc;
   if (!n_rays) return DFN_OK;
   if (!rays_o || !rays_d || !sigma || Nc < 1) return set_error(DFN_ERR_ARG, "dfn_mlp_coarse: bad argument");
-  const bool half = half_heads(mlp_variant_of(h), prec), res = resident_layers(mlp_variant_of(h), prec);
-  const int var = base_variant(mlp_variant_of(h));
+  const bool half = half_heads(resolved_variant(h), prec), res = resident_layers(resolved_variant(h), prec);
+  const int var = base_variant(resolved_variant(h));
   const PackedNet& n = h->net[0][prec][res ? kResidentVariant : (half ? kHalfVariant : var)];
   MlpArgs a{n.blob, n.tab, n.n_units, rays_o, rays_d, nullptr, nullptr, sigma, nullptr, (long long)n_rays, Nc, near, far, nullptr, n.in_scale,
             h->render_flags & DFN_RENDER_LINDISP};
   a.status = range_flag_of(h);
+  const bool dyn = res && dyn_tiles(h);
+  if (dyn) CHECK_HIP(hipMemsetAsync(h->tile_counter, 0, 2 * sizeof(uint32_t), HS(stream)), "dfn_mlp_coarse(tile counters)");
   ScopedTimer t(0, HS(stream));
-  if (res) CHECK_HIP(launch_mlp_res(false, res_args(a, n), device_cu_count(), HS(stream)), "dfn_mlp_coarse");
+  if (dyn) CHECK_HIP(launch_mlp_dyn(false, dyn_args(res_args(a, n), h->tile_counter), device_cu_count(), HS(stream)), "dfn_mlp_coarse");
+  else if (res) CHECK_HIP(launch_mlp_res(false, res_args(a, n), device_cu_count(), HS(stream)), "dfn_mlp_coarse");
   else if (half) CHECK_HIP(launch_mlp_half(false, false, a, device_cu_count(), HS(stream)), "dfn_mlp_coarse");
   else CHECK_HIP(launch_mlp(false, prec, var, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_coarse");
   return DFN_OK;
@@ -981,8 +1004,8 @@ extern "C" int dfn_mlp_fine(dfn_nerfh_t h, int prec, const float* rays_o, const 
       (hist_rows != 1 && hist_rows != n_rays))
     return set_error(DFN_ERR_ARG, "dfn_mlp_fine: bad argument (hist_rows must be 1 or n_rays)");
   float* table = static_cast<float*>(bias_ws);
-  const bool fold = fold_fine(mlp_variant_of(h), prec);
-  const int var = fold ? kFoldVariant : base_variant(mlp_variant_of(h));
+  const bool fold = fold_fine(resolved_variant(h), prec);
+  const int var = fold ? kFoldVariant : base_variant(resolved_variant(h));
   CHECK_HIP(launch_ray_bias(fold ? h->rb_fold : h->rb, viewdirs, hist, hist_rows, n_rays, table, HS(stream)), "dfn_mlp_fine(ray_bias)");
   const PackedNet& n = h->net[1][prec][var];
   MlpArgs a{n.blob, n.tab, n.n_units, rays_o, rays_d, z_fine, table, raw, nullptr, (long long)n_rays, Nf, 0.f, 0.f, g_timing_buf, n.in_scale};
@@ -1017,20 +1040,34 @@ extern "C" int dfn_composite_fine_maps(const float* raw, const float* z, size_t 
 
 // ------------------------------------------------------------------------------------------ whole path
 namespace {
-constexpr size_t kMaxChunkRays = 65536;  // rays per internal pass (bounds the raw buffer)
+constexpr size_t kMaxChunkRays = 65536;  // rays per internal pass where raw lives in the workspace (bounds the raw buffer)
+// ... and on the fused route, where raw never reaches memory and only sigma, z, the per-ray table and the segment records scale with
+// the pass.  A bound of its own: 327 680 (a 640x480 frame in ONE pass; 327 680 rays x 512 samples = 1.7e8 points, inside the kernels'
+// 32-bit point indices; every output bit for bit) was built and measured -0.11 ms of 52.07 per frame, inside three times the parent's
+// spread (LABBOOK R16.1), for 150 MB more workspace: not a gain by the project's rule, so the bound stays the raw route's.
+constexpr size_t kMaxFusedChunkRays = 65536;
 inline size_t al(size_t b) { return (b + 255) & ~size_t(255); }
-// Equal passes of at most kMaxChunkRays rays (multiple of 64 rays so MLP tiles stay aligned).
-inline size_t chunk_rays(size_t n_rays) {
-  const size_t passes = (n_rays + kMaxChunkRays - 1) / kMaxChunkRays;
+// Equal passes of at most max_rays rays (multiple of 64 rays so MLP tiles stay aligned).
+inline size_t chunk_rays(size_t n_rays, size_t max_rays = kMaxChunkRays) {
+  const size_t passes = (n_rays + max_rays - 1) / max_rays;
   const size_t c = passes ? (n_rays + passes - 1) / passes : 1;
   return (c + 63) & ~size_t(63);
+}
+// The route of a render call, as render_core takes it.  Compositing is fused into the fine kernel when a wave's points are one ray
+// segment and raw is not wanted: 64 samples per wave in the f16 variants 0/1/3, 32 in the split-f16 and fp32 kernels (one point block
+// per wave); the 3-block f16 variant and netwidth 256 keep the separate compositor.
+inline int fused_segment(int prec) { return prec == DFN_PREC_F16 ? 64 : 32; }
+bool fused_route(dfn_nerfh_t h, int prec, int Nf, bool want_raw) {
+  return !want_raw && Nf % fused_segment(prec) == 0 && !(prec == DFN_PREC_F16 && base_variant(resolved_variant(h)) == 2) && h->desc.width == kWidth;
 }
 struct Workspace {
   float *o, *d, *v, *sigma, *z, *raw, *bias, *partial;
   size_t total;
+  size_t chunk;   // rays per pass of this layout
 };
-Workspace carve(char* base, size_t n_rays, int Nc, int Ni, bool own_rays, int rec_floats = 12) {
-  const size_t chunk = chunk_rays(n_rays);
+// fused: the layout of the fused route -- passes of up to kMaxFusedChunkRays rays and no raw slot (w.raw = nullptr)
+Workspace carve(char* base, size_t n_rays, int Nc, int Ni, bool own_rays, int rec_floats = 12, bool fused = false) {
+  const size_t chunk = chunk_rays(n_rays, fused ? kMaxFusedChunkRays : kMaxChunkRays);
   const size_t Nf = size_t(Nc) + Ni;
   Workspace w{};
   size_t off = 0;
@@ -1040,11 +1077,18 @@ Workspace carve(char* base, size_t n_rays, int Nc, int Ni, bool own_rays, int re
   w.v = take(n_rays * 12);
   w.sigma = take(chunk * Nc * 4);
   w.z = take(chunk * Nf * 4);
-  w.raw = take(chunk * Nf * 9 * 4);
+  w.raw = fused ? nullptr : take(chunk * Nf * 9 * 4);
   w.bias = take(chunk * ray_bias_floats(kMaxWidth) * 4);
   w.partial = take(chunk * ((Nf + 31) / 32) * rec_floats * 4);   // kMapsRecFloats per segment for the render-maps entries
   w.total = off;
+  w.chunk = chunk;
   return w;
+}
+// What the size queries return: they take no route, so the larger of the two layouts -- a buffer of that size serves whichever
+// route the call takes.
+size_t workspace_bytes_any_route(size_t n_rays, int Nc, int Ni, int rec_floats) {
+  const size_t a = carve(nullptr, n_rays, Nc, Ni, true, rec_floats, false).total, b = carve(nullptr, n_rays, Nc, Ni, true, rec_floats, true).total;
+  return a > b ? a : b;
 }
 
 int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const float* v, const float* hist,
@@ -1052,23 +1096,22 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
                 float* acc, float* raw_out, const Workspace& w, hipStream_t s, const MapPtrs& maps = MapPtrs{}) {
   const int Nf = Nc + Ni;
   const bool want_maps = maps.any();   // w.partial then holds kMapsRecFloats floats per segment (carve)
-  // Compositing is fused into the fine kernel when a wave's points are one ray segment and raw is not wanted: 64 samples per wave in
-  // the f16 variants 0/1/3, 32 in the split-f16 and fp32 kernels (one point block per wave); the 3-block f16 variant and netwidth
-  // 256 keep the separate compositor.
-  const bool fold = fold_fine(mlp_variant_of(h), prec);
-  const int var = base_variant(mlp_variant_of(h));
-  const int seg = prec == DFN_PREC_F16 ? 64 : 32;
-  const bool fused = !raw_out && Nf % seg == 0 && !(prec == DFN_PREC_F16 && var == 2) && h->desc.width == kWidth;
+  const bool fold = fold_fine(resolved_variant(h), prec);
+  const int var = base_variant(resolved_variant(h));
+  const int seg = fused_segment(prec);
+  const bool fused = fused_route(h, prec, Nf, raw_out != nullptr);   // the caller carved w for this route
   const int cprec = (h->render_flags & DFN_RENDER_COARSE_F16) ? DFN_PREC_F16 : prec;   // the coarse pass only places the fine samples
   // kernel variant 6: its coarse kernel, and its fine kernel where the compositing is fused (the raw route keeps variant 5's)
-  const bool half_c = half_heads(mlp_variant_of(h), cprec), half_f = half_heads(mlp_variant_of(h), prec) && fused;
+  const bool half_c = half_heads(resolved_variant(h), cprec), half_f = half_heads(resolved_variant(h), prec) && fused;
   // kernel variant 7: its coarse kernel, and its fine kernel where variant 6's plain fused one would run (the maps flavour keeps variant 6's)
-  const bool res_c = resident_layers(mlp_variant_of(h), cprec), res_f = resident_layers(mlp_variant_of(h), prec) && fused && !want_maps;
+  const bool res_c = resident_layers(resolved_variant(h), cprec), res_f = resident_layers(resolved_variant(h), prec) && fused && !want_maps;
   const PackedNet& nc = h->net[0][cprec][res_c ? kResidentVariant : (half_c ? kHalfVariant : var)];
   const PackedNet& nf = res_f ? h->net[1][prec][kResidentVariant]
                       : half_f ? (want_maps ? h->half_maps : h->net[1][prec][kHalfVariant]) : h->net[1][prec][fold ? kFoldVariant : var];
+  // kernel variant 8: variant 7's two kernels with their tiles claimed from the handle's counters, zeroed in front of each pass
+  const bool dyn_c = res_c && dyn_tiles(h), dyn_f = res_f && dyn_tiles(h);
   const int cus = device_cu_count();
-  const size_t chunk = chunk_rays(n_rays);
+  const size_t chunk = w.chunk;
   for (size_t r0 = 0; r0 < n_rays; r0 += chunk) {
     const size_t n = n_rays - r0 < chunk ? n_rays - r0 : chunk;
     const float* co = o + r0 * 3;
@@ -1080,8 +1123,10 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
       MlpArgs a{nc.blob, nc.tab, nc.n_units, co, cd, nullptr, nullptr, w.sigma, nullptr, (long long)n, Nc, near, far, nullptr, nc.in_scale,
                  h->render_flags & DFN_RENDER_LINDISP};
       a.status = range_flag_of(h);
+      if (dyn_c || dyn_f) CHECK_HIP(hipMemsetAsync(h->tile_counter, 0, 2 * sizeof(uint32_t), s), "render: tile counters");
       ScopedTimer t(0, s);
-      if (res_c) CHECK_HIP(launch_mlp_res(false, res_args(a, nc), cus, s), "render: coarse MLP (resident layers)");
+      if (dyn_c) CHECK_HIP(launch_mlp_dyn(false, dyn_args(res_args(a, nc), h->tile_counter), cus, s), "render: coarse MLP (claimed tiles)");
+      else if (res_c) CHECK_HIP(launch_mlp_res(false, res_args(a, nc), cus, s), "render: coarse MLP (resident layers)");
       else if (half_c) CHECK_HIP(launch_mlp_half(false, false, a, cus, s), "render: coarse MLP (half-height heads)");
       else CHECK_HIP(launch_mlp(false, cprec, var, a, cus, s, h->desc.width), "render: coarse MLP");
     }
@@ -1098,7 +1143,8 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
       MlpArgs a{nf.blob, nf.tab, nf.n_units, co, cd, w.z, w.bias, raw, fused ? w.partial : nullptr, (long long)n, Nf, 0.f, 0.f, g_timing_buf, nf.in_scale};
       a.status = range_flag_of(h);
       ScopedTimer t(1, s);
-      if (res_f) CHECK_HIP(launch_mlp_res(true, res_args(a, nf), cus, s), "render: fine MLP (resident layers)");
+      if (dyn_f) CHECK_HIP(launch_mlp_dyn(true, dyn_args(res_args(a, nf), h->tile_counter + 1), cus, s), "render: fine MLP (claimed tiles)");
+      else if (res_f) CHECK_HIP(launch_mlp_res(true, res_args(a, nf), cus, s), "render: fine MLP (resident layers)");
       else if (half_f) CHECK_HIP(launch_mlp_half(true, want_maps, a, cus, s), "render: fine MLP (half-height heads)");
       else if (fold) CHECK_HIP(launch_mlp_fold(fused && want_maps, a, cus, s), "render: fine MLP (folded)");
       else if (fused && want_maps) CHECK_HIP(launch_mlp_maps(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP (maps)");
@@ -1133,7 +1179,7 @@ int check_render_args(int Nc, int Ni, const char* fn) {
 }  // namespace
 
 extern "C" size_t dfn_render_workspace_bytes(size_t n_rays, int Nc, int Ni) {
-  return carve(nullptr, n_rays ? n_rays : 1, Nc, Ni, true).total;
+  return workspace_bytes_any_route(n_rays ? n_rays : 1, Nc, Ni, 12);
 }
 
 // dfn_render_rays / dfn_render_rays_maps (`fn`: the name the messages carry; no map requested: the plain entry's launches)
@@ -1146,7 +1192,8 @@ static int render_rays_entry(const char* fn, dfn_nerfh_t h, int prec, const floa
   if (!n_rays) return DFN_OK;  // an empty batch is valid (its buffers may be null)
   if (!rays_o || !rays_d || !hist || !rgb || !disp || !acc || !workspace || (hist_rows != 1 && hist_rows != n_rays))
     return set_error(DFN_ERR_ARG, "%s: bad argument (hist_rows must be 1 or n_rays)", fn);
-  const Workspace w = carve(static_cast<char*>(workspace), n_rays, Nc, Ni, true, maps.any() ? kMapsRecFloats : 12);
+  const Workspace w = carve(static_cast<char*>(workspace), n_rays, Nc, Ni, true, maps.any() ? kMapsRecFloats : 12,
+                            fused_route(h, prec, Nc + Ni, raw != nullptr));
   if (w.total > workspace_bytes)
     return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.total);
   const float* v = viewdirs;
@@ -1167,7 +1214,8 @@ static int render_image_entry(const char* fn, dfn_nerfh_t h, int prec, const flo
   if (!c2w || !hist || !rgb || !disp || !acc || !workspace || H < 1 || W < 1 || !(focal > 0))
     return set_error(DFN_ERR_ARG, "%s: bad argument", fn);
   const size_t n_rays = size_t(H) * W;
-  const Workspace w = carve(static_cast<char*>(workspace), n_rays, Nc, Ni, true, maps.any() ? kMapsRecFloats : 12);
+  const Workspace w = carve(static_cast<char*>(workspace), n_rays, Nc, Ni, true, maps.any() ? kMapsRecFloats : 12,
+                            fused_route(h, prec, Nc + Ni, false));
   if (w.total > workspace_bytes)
     return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.total);
   if (hipError_t e = launch_raygen(H, W, focal, c2w, w.o, w.d, w.v, HS(stream)); e != hipSuccess)
@@ -1191,7 +1239,7 @@ extern "C" int dfn_render_image(dfn_nerfh_t h, int prec, const float* c2w, int H
 }
 
 extern "C" size_t dfn_render_maps_workspace_bytes(size_t n_rays, int Nc, int Ni) {
-  return carve(nullptr, n_rays ? n_rays : 1, Nc, Ni, true, kMapsRecFloats).total;
+  return workspace_bytes_any_route(n_rays ? n_rays : 1, Nc, Ni, kMapsRecFloats);
 }
 
 extern "C" int dfn_render_rays_maps(dfn_nerfh_t h, int prec, const float* rays_o, const float* rays_d, const float* viewdirs,
@@ -1409,7 +1457,7 @@ BwdWorkspace carve_bwd(char* base, size_t n_rays, int Nc, int Ni) {
 int render_backward_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const float* v, bool derive_v,
                          const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
                          const float* grad_rgb, float* go, float* gd, float* gv, const BwdWorkspace& w, hipStream_t s) {
-  const int Nf = Nc + Ni, var = base_variant(mlp_variant_of(h)), cus = device_cu_count();
+  const int Nf = Nc + Ni, var = base_variant(resolved_variant(h)), cus = device_cu_count();
   const PackedNet& nc = h->net[0][prec][var];
   const PackedNet& nf = h->net[1][prec][var];
   const PackedNet& nb = h->bwd[prec];

@@ -50,6 +50,13 @@ struct MlpResArgs : MlpArgs {
   uint32_t res_bytes;
 };
 hipError_t launch_mlp_res(bool fine, const MlpResArgs& a, int n_cu, hipStream_t stream);
+// Kernel variant 8 (nerfh_mlp_dyn.hip): variant 7's two kernels with the tiles claimed dynamically.  A workgroup starts on tile
+// blockIdx.x and takes every later one as gridDim.x + atomicAdd(tile_counter, 1); *tile_counter (device) must be 0 when the kernel
+// starts and belongs to this launch alone until it ends.  The pointer rides behind MlpResArgs for the reason given there.
+struct MlpDynArgs : MlpResArgs {
+  uint32_t* tile_counter;
+};
+hipError_t launch_mlp_dyn(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
 
 // The points flavour (nerfh_mlp_pts*.hip): a.rays_o is pts [n_rays, n_samples, 3] (n_rays = query rows), a.rays_d, a.z and a.partial
 // are unused (a.partial must be null: the raw route only), a.ray_bias has one row per query row.  launch_mlp_pts: f16 / exact fp32 at

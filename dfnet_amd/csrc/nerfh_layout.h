@@ -152,10 +152,15 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //              units, fine 26 -> 22 per 256-point tile) with their barriers and DMA round trips; the same fragments, MFMAs and
 //              conversion pieces in the same order: variant 6's outputs bit for bit.  The maps flavour, the raw route and everything
 //              else resolve as under variant 6
-constexpr int kVariants = 8;
+//   variant 8: variant 7 with the tiles of its two kernels CLAIMED from a device counter instead of dealt blockIdx.x, + gridDim.x, ...
+//              (nerfh_mlp_dyn.hip: nerfh_coarse_dyn_kernel / nerfh_fine_dyn_kernel): scheduling only -- the same code computes every
+//              tile from the same inputs into the same place, on variant 7's packed networks (it packs none of its own, so it is no
+//              index of dfn_nerfh_s::net): variant 7's outputs bit for bit.  Everything else resolves as under variant 7
+constexpr int kVariants = 8;   // packed networks per (coarse | fine, arithmetic): dfn_nerfh_s::net
 constexpr int kFoldVariant = 5;
 constexpr int kHalfVariant = 6;
 constexpr int kResidentVariant = 7;
+constexpr int kDynVariant = 8;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));
 }

@@ -47,6 +47,9 @@ constexpr bool kMapsTU = false;
 // DFN_MLP_RES_TU on top of DFN_MLP_HALF_TU.  It gets launch_mlp_res, the coarse kernel as nerfh_coarse_res_kernel and the plain fused
 // fine kernel as nerfh_fine_res_kernel, both taking MlpResArgs; in every other unit kResident is false, every res_base() is -1 and
 // every layer<> and trunk<> below names the instantiation it named before.
+// Kernel variant 8 (claimed tiles: Stager::claim / next, DFN_NEXT_TILE) is nerfh_mlp_dyn.hip: DFN_MLP_DYN_TU on top of DFN_MLP_RES_TU.
+// It gets launch_mlp_dyn and variant 7's two kernels as nerfh_coarse_dyn_kernel / nerfh_fine_dyn_kernel, both taking MlpDynArgs; in
+// every other unit DFN_NEXT_TILE is `tile + gridDim.x` and the tile loops are the tokens they were.
 // The points flavour (dfn_mlp_coarse_points, dfn_mlp_fine_points: DFN_MLP_PTS_TU, on top of none, DFN_MLP_FOLD_TU or DFN_MLP_HALF_TU) is
 // compiled in three more units, nerfh_mlp_pts.hip, nerfh_mlp_pts_fold.hip and nerfh_mlp_pts_half.hip: the three inputs of a point are
 // loaded from pts [n_rows, n_samples, 3] (MlpArgs::rays_o) instead of being formed as o + d z, and everything behind x[..][3] is the
@@ -66,6 +69,10 @@ constexpr bool kHalfHeads = false;
 #define DFN_COARSE_KERNEL nerfh_coarse_pts_kernel
 constexpr bool kHalfHeads = false;
 #endif
+#elif defined(DFN_MLP_DYN_TU)
+#define DFN_FINE_KERNEL nerfh_fine_dyn_kernel
+#define DFN_COARSE_KERNEL nerfh_coarse_dyn_kernel
+constexpr bool kHalfHeads = true;
 #elif defined(DFN_MLP_RES_TU)
 #define DFN_FINE_KERNEL nerfh_fine_res_kernel
 #define DFN_COARSE_KERNEL nerfh_coarse_res_kernel
@@ -89,10 +96,23 @@ constexpr bool kHalfHeads = false;
 #error "the resident layers exist in the half-height render kernels"
 #endif
 constexpr bool kResident = true;
-#define DFN_MLP_KARGS MlpResArgs
+#if defined(DFN_MLP_DYN_TU)
+#define DFN_MLP_KARGS MlpDynArgs
 #else
+#define DFN_MLP_KARGS MlpResArgs
+#endif
+#else
+#if defined(DFN_MLP_DYN_TU)
+#error "the claimed tiles exist in the kernels with resident layers"
+#endif
 constexpr bool kResident = false;
 #define DFN_MLP_KARGS MlpArgs
+#endif
+// the tile a workgroup computes after `tile` (inside the kernels' tile loops): dealt, or claimed (kernel variant 8: Stager::next)
+#if defined(DFN_MLP_DYN_TU)
+#define DFN_NEXT_TILE (static_cast<long long>(st.next))
+#else
+#define DFN_NEXT_TILE (tile + gridDim.x)
 #endif
 
 // Head activations per arithmetic mode: f16 = hardware transcendentals (1e-6), split-f16 = the fp32-grade hardware forms
@@ -128,6 +148,11 @@ static_assert(resident_set_supported(false) && resident_set_supported(true), "a 
 static_assert(lds_bytes<PrecX3M16, unit_mb<PrecX3M16>(0), 8, 1>() + resident_bytes<PrecX3M16>(true) <= kLdsBytes &&
               lds_bytes<PrecX3M16, unit_mb<PrecX3M16>(0), 8, 1>() + resident_bytes<PrecX3M16>(false) <= kLdsBytes,
               "ring + input slots + resident layers must fit the LDS of a CU");
+// Kernel variant 8: the word the claimed tile is published through, behind the resident region (16 bytes keep the region's alignment)
+constexpr uint32_t kClaimBytes = 16;
+static_assert(lds_bytes<PrecX3M16, unit_mb<PrecX3M16>(0), 8, 1>() + resident_bytes<PrecX3M16>(true) + kClaimBytes <= kLdsBytes &&
+              lds_bytes<PrecX3M16, unit_mb<PrecX3M16>(0), 8, 1>() + resident_bytes<PrecX3M16>(false) + kClaimBytes <= kLdsBytes,
+              "ring + input slots + resident layers + the claimed-tile word must fit the LDS of a CU");
 
 // Workgroups per CU the register allocation is sized for.  netwidth 256 in split-f16 / exact fp32 holds 2 x 128 registers of
 // activations per point block: four waves per workgroup, ONE workgroup per CU (512 registers per lane).
@@ -169,8 +194,18 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   stage_resident(st, smem, a.res_blob, resident_bytes<P>(false), lds_bytes<P, UMB, WAVES, NB, W>());
 #endif
   stage_prime(st, smem, max_unit_bytes<P>(UMB, W), ring_slots<P, W>());
+#ifdef DFN_MLP_DYN_TU
+  // claimed tiles: blockIdx.x first, then gridDim.x + (the counter before this workgroup's add); see Stager.  A workgroup without a
+  // first tile has returned above without claiming.
+  st.claim = 0; st.grid = gridDim.x; st.next = 0; st.n_tiles = uint32_t(n_tiles); st.more = false;
+  st.claim_lds = lds_bytes<P, UMB, WAVES, NB, W>() + resident_bytes<P>(false);
+  for (; tile < n_tiles; tile = st.next) {
+    if (st.wave == 0 && st.lane == 0) st.claim = claim_tile(a.tile_counter);
+    st.claiming = true;
+#else
   for (; tile < n_tiles; tile += gridDim.x) {
     st.more = tile + gridDim.x < n_tiles;
+#endif
     constexpr int LP = lane_pts<P>(NB);
     float x[LP][3];
     uint32_t pt[NB];   // launch_one() bounds a launch to < 2^31 points: 32-bit indices (64-bit ones cost 2 registers each and spilled)
@@ -298,8 +333,18 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     for (int c = 0; c < 3; ++c) { oin[nb][c] = a.rays_o[ray_of[nb] * 3 + c]; din[nb][c] = a.rays_d[ray_of[nb] * 3 + c]; }
 #endif
   }
+#ifdef DFN_MLP_DYN_TU
+  // claimed tiles, as in the coarse kernel: st.next replaces tile + gridDim.x in the three places that name the next tile -- st.more
+  // (mid_sync), the input prefetch behind LY_TE0F's mid_sync and tile_coords at the tile's end, all far behind the tile's first mid_sync
+  st.claim = 0; st.grid = gridDim.x; st.next = 0; st.n_tiles = uint32_t(n_tiles); st.more = false;
+  st.claim_lds = lds_bytes<P, UMB, WAVES, NB, W>() + resident_bytes<P>(true);
+  for (; tile < n_tiles; tile = st.next) {
+    if (st.wave == 0 && st.lane == 0) st.claim = claim_tile(a.tile_counter);
+    st.claiming = true;
+#else
   for (; tile < n_tiles; tile += gridDim.x) {
     st.more = tile + gridDim.x < n_tiles;
+#endif
     float x[LP][3];
     uint32_t pt_cur[LP], ray_cur[LP];
 #pragma unroll
@@ -400,7 +445,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
         // Prefetch the next tile's inputs by LDS-DMA (no destination registers).  Issued AFTER this unit's mid_sync so
         // that nothing younger than a weight DMA is ever waited for before the tile's end:
         // lane l of round r fetches z, o, d and the next sample's z of the wave's point 64 r + l into this wave's LDS slot.
-        const uint32_t base = uint32_t(tile + gridDim.x) * uint32_t(PPT) + st.wave * (NB * 32);
+        const uint32_t base = uint32_t(DFN_NEXT_TILE) * uint32_t(PPT) + st.wave * (NB * 32);
         char* slot = smem + ring_slots<P, W>() * USTRIDE + st.wave * (PF_ROUNDS * 8 * 256);
 #pragma unroll
         for (int r = 0; r < PF_ROUNDS; ++r) {
@@ -543,7 +588,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     if (st.more) {  // pick up the prefetched inputs of the next tile (this wave's own LDS slot: no barrier needed)
       __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
       asm volatile("" ::: "memory");
-      tile_coords(tile + gridDim.x);
+      tile_coords(DFN_NEXT_TILE);
       const char* slot = smem + ring_slots<P, W>() * USTRIDE + st.wave * (PF_ROUNDS * 8 * 256);
 #pragma unroll
       for (int nb = 0; nb < LP; ++nb) {
@@ -642,6 +687,36 @@ hipError_t launch_mlp_pts(bool fine, int prec, const MlpArgs& a, int n_cu, hipSt
               : launch_pts_one<PrecF32, false, 8, 1, 1, false, kWidth, false>(a, n_cu, stream);
 }
 #endif
+#elif defined(DFN_MLP_DYN_TU)
+// variant 8's kernels: variant 7's (geometry, networks, resident region) with the claimed-tile word behind the region.  The grid is
+// variant 7's: min(tiles, CUs) workgroups, each starting on tile blockIdx.x; *a.tile_counter is 0 at the start (the caller's memset).
+hipError_t launch_mlp_dyn(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream) {
+  using P = PrecX3M16;
+  constexpr int WAVES = 8, UMB = unit_mb<P>(0), NB = 1, PPT = WAVES * NB * 32;
+  const long long n_pts = (long long)a.n_rays * a.n_samples;
+  if (n_pts <= 0) return hipSuccess;
+  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
+  if (a.masks || (fine && !a.partial) || !a.tile_counter) return hipErrorInvalidValue;
+  if (!a.res_blob || a.res_bytes != resident_bytes<P>(fine)) return hipErrorInvalidValue;   // the kernels copy exactly this many bytes
+  const long long n_tiles = (n_pts + PPT - 1) / PPT;
+  const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
+  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB>() + resident_bytes<P>(fine) + kClaimBytes;
+  void (*kern)(MlpDynArgs) = fine ? nerfh_fine_dyn_kernel<P, false, WAVES, UMB, NB, true> : nerfh_coarse_dyn_kernel<P, false, WAVES, UMB, NB, true>;
+  static bool attr_done[2] = {false, false};
+  if (!attr_done[fine]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    if (e != hipSuccess) return e;
+    attr_done[fine] = true;
+  }
+  MlpDynArgs b = a;
+  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid, as launch_mlp
+    static int env = -1;
+    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
+    b.dma_waves = env > 0 ? env : 4;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
+  return hipGetLastError();
+}
 #elif defined(DFN_MLP_RES_TU)
 // variant 7's kernels: variant 6's geometry with the resident region behind the input slots.  coarse; fine with the compositing fused,
 // plain flavour -- the maps flavour stays with launch_mlp_half, the raw route with launch_mlp_fold.

@@ -54,6 +54,18 @@ struct Stager {
   unsigned long long* trace;
   int n_trace;
   bool more;           // another tile follows this one (wave-uniform)
+#ifdef DFN_MLP_DYN_TU
+  // Kernel variant 8 (nerfh_mlp_dyn.hip): the tile after this one is CLAIMED -- lane 0 of wave 0 issues a returning atomic add on the
+  // launch's tile counter at the top of the tile; the first mid_sync() of the tile publishes the result through one LDS word around
+  // its barrier and sets `next` and `more` in every wave.  `more` is first read by the mid_sync() of the tile's second-to-last
+  // streamed unit (the wrap to the next tile), many units later.
+  uint32_t claim;      // lane 0 of wave 0: the counter's value before the add (pending until the first mid_sync's vmcnt(0))
+  uint32_t grid;       // gridDim.x: tile = grid + claim
+  uint32_t next;       // the tile this workgroup computes after the current one (wave-uniform; >= n_tiles: none)
+  uint32_t n_tiles;
+  uint32_t claim_lds;  // LDS byte offset of the published word (behind the resident region)
+  bool claiming;       // a claim was issued at the top of this tile and is not published yet (wave-uniform)
+#endif
   float in_scale, out_scale;  // split-f16: accumulators carry in_scale x the true value (MlpArgs), out_scale = 1 / in_scale
   float lane_mul;             // split-f16: extra per-LANE power-of-two factor on the next layer's outputs (gradient renormalisation)
   uint32_t rmax;              // range guard: running unsigned maximum of the packed f16 activations (hi halves for split-f16) this
@@ -95,6 +107,22 @@ DFN_DEV void lds_dma_b32(const void* gptr, const char* lds_dst) {
   const uint32_t off = (uint32_t)(size_t)DFN_LDS_PTR(lds_dst);
   asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dword %0, off" ::"v"(gptr), "s"(off) : "memory");
 }
+
+#ifdef DFN_MLP_DYN_TU
+// Kernel variant 8: one lane's claim, a returning device-scope atomic add whose result nobody waits for here (mid_sync's vmcnt(0) does).
+// The pointer goes through an opaque vector register: on an address it can prove wave-uniform LLVM's atomic optimiser rewrites the add
+// as a wave reduction + v_readfirstlane of the result, and with that a wait for the whole L2 round trip right behind the atomic.
+// Named a GLOBAL address again behind it: a flat atomic counts in vmcnt and lgkmcnt both and turns every counted wait behind it into 0.
+// The LDS word the claim is published through, named in the LDS address space (through the generic pointer it is a flat access).
+typedef volatile uint32_t __attribute__((address_space(3))) lds_vu32;
+DFN_DEV lds_vu32* claim_word(char* smem, uint32_t off) { return reinterpret_cast<lds_vu32*>(DFN_LDS_PTR(smem + off)); }
+DFN_DEV uint32_t claim_tile(uint32_t* counter) {
+  typedef uint32_t __attribute__((address_space(1))) global_u32;
+  uint64_t p = reinterpret_cast<uint64_t>(counter);
+  asm volatile("" : "+v"(p));
+  return __hip_atomic_fetch_add(reinterpret_cast<global_u32*>(p), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+#endif
 
 DFN_DEV void stage_issue_at(const Stager& st, char* smem, uint32_t off, uint32_t size, uint32_t lds_off) {
   const char* src = st.blob + off + st.lane * 16;
@@ -144,6 +172,10 @@ DFN_DEV void stage_prime(Stager& st, char* smem, uint32_t unit_stride, uint32_t 
 // STREAMED unit, which every wave has left once it is past u's barrier -- a resident layer between two streamed units is computed
 // out of this region and touches no ring slot, and `st.u == 0` still names the tile's last streamed unit whether or not resident
 // layers follow it, so the wrap to the next tile (units 0 and 1 issued from the last two streamed units' mid_sync) is unchanged.
+// Kernel variant 8 (claimed tiles) leaves this as it is too: units 0 and 1 are the same bytes whichever tile comes next, so the wrap
+// asks only WHETHER a tile follows (st.more), never which; st.more is set by the tile's first mid_sync (streamed unit 0 or 1 of 14 / 22)
+// and read from the second-to-last streamed unit's on, st.u == 0 names the same unit, and a workgroup whose claim is past the last
+// tile sees more == false exactly where the static deal's last tile did: nothing is issued into a ring nobody will read.
 DFN_DEV void stage_resident(const Stager& st, char* smem, const char* res_blob, uint32_t bytes, uint32_t lds_off) {
   const char* src = res_blob + st.lane * 16;
   if (st.wave >= st.dma_waves) return;
@@ -170,6 +202,16 @@ DFN_DEV void mid_sync(Stager& st, char* smem) {
   // does not re-wait for them later with a count that the untracked DMA loads would turn into a wait for the DMA)
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   asm volatile("" ::: "memory");
+#ifdef DFN_MLP_DYN_TU
+  // the tile's first mid_sync: the claim issued at the top of the tile has returned with the wait above.  Wave 0 puts the claimed tile
+  // into the LDS word and sees it written (lgkmcnt(0)) BEFORE it signals this unit's barrier; no barrier is added.  The word is
+  // rewritten one tile later, behind every barrier of this tile: every wave has read it by then (it reads right behind this barrier).
+  if (st.claiming && st.wave == 0) {
+    if (st.lane == 0) *claim_word(smem, st.claim_lds) = st.grid + st.claim;
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+    asm volatile("" ::: "memory");
+  }
+#endif
 #ifdef DFN_TIMING
   const unsigned long long c1 = __builtin_amdgcn_s_memtime();
 #endif
@@ -190,6 +232,13 @@ DFN_DEV void mid_sync(Stager& st, char* smem) {
     st.trace[2 * st.n_trace + 1] = c2;
   }
   ++st.n_trace;
+#endif
+#ifdef DFN_MLP_DYN_TU
+  if (st.claiming) {   // every wave, behind the barrier wave 0 wrote in front of
+    st.next = __builtin_amdgcn_readfirstlane(*claim_word(smem, st.claim_lds));
+    st.more = st.next < st.n_tiles;
+    st.claiming = false;
+  }
 #endif
   if (!next_tile || st.more) stage_issue_at(st, smem, st.pf_off, st.pf_size, dst);
   {  // fetch the table entry needed by the next call now, so its scalar-load latency is off the critical path

@@ -160,7 +160,11 @@ int dfn_composite_fine(const float* raw, const float* z, size_t n_rays, int Nf, 
 
 /* ------------------------------------------------------------------ whole-path entry points */
 
-/* Scratch needed by dfn_render_rays / dfn_render_image for up to n_rays rays. */
+/* Scratch needed by dfn_render_rays / dfn_render_image for up to n_rays rays: the larger of the two internal layouts (raw kept in the
+ * workspace; compositing fused into the fine kernel, no raw slot), so one buffer serves whichever route a call takes.  640x480 at
+ * 64 + 128: 579 MB (the raw layout; a call on the fused route uses the first 155 MB and accepts a buffer of that size).
+ * A handle renders ONE call at a time: the default kernels claim their tiles from two counters the handle owns, zeroed on the call's
+ * stream in front of each pass (calls on one stream, or ordered across streams, are fine; so are concurrent calls on different handles). */
 size_t dfn_render_workspace_bytes(size_t n_rays, int Nc, int Ni);
 
 /* rendering.py:245-337 render_rays at test time (perturb=0, raw_noise_std=0, white_bkgd=False, test_time=True; lindisp as set
