@@ -19,8 +19,10 @@
 #include "nerfh_handle.h"
 #include "nerfh_kernels.h"
 #include "nerfh_layout.h"
+#include "nerfh_route.h"
 
 using namespace dfn;
+static_assert(kPrecF16 == DFN_PREC_F16 && kPrecF32 == DFN_PREC_F32 && kPrecF16X3 == DFN_PREC_F16X3, "nerfh_route.h names the ABI's precisions");
 
 // ------------------------------------------------------------------------------------------ errors
 namespace dfn {
@@ -616,16 +618,13 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
   for (int f = 0; f < 2; ++f)
     for (int prec = 0; prec < 3; ++prec)
       for (int var = 0; var < kVariants; ++var) {
-        // variant 5 has one network of its own, the split-f16 fine one; everything else of it is variant 4's (net_of).  Variant 6 has
-        // three, all split-f16 with half-height head blocks: the coarse one, the folded fine one without transient_beta's half (fused
-        // compositing, no maps) and, in h->half_maps, the folded fine one with it (the maps flavour); the rest is variant 5's
-        // Variant 7 has two, variant 6's coarse and plain fine one with the resident layers taken out of the unit table into a blob of
-        // their own (res_blob); its maps flavour reads variant 6's half_maps
-        const bool resident = var == kResidentVariant;
-        const bool half = var == kHalfVariant || resident;
-        const bool fold = var == kFoldVariant || (half && f == 1);
-        if (var == kFoldVariant && !(f == 1 && prec == DFN_PREC_F16X3)) continue;
-        if (half && prec != DFN_PREC_F16X3) continue;
+        // A variant with kernels of its own (kVariantFacts: base != var) packs the split-f16 networks they read and nothing else: the
+        // fine one from the fold on, the coarse one from the half-height heads on; the rest of it is its base's (nerfh_route.h).
+        // Half heads: also h->half_maps, the folded fine network with transient_beta's half (the maps flavour; variant 7 reads variant
+        // 6's).  Resident: the resident layers leave the unit table for a blob of their own (res_blob).
+        const VariantFacts vf = kVariantFacts[var];
+        const bool resident = vf.resident, half = vf.half, fold = vf.fold && f == 1;
+        if (vf.base != var && !(prec == DFN_PREC_F16X3 && (f == 1 ? vf.fold : vf.half))) continue;
         Packer pk{h, f ? "fine." : "coarse."};
         pk.half_heads = half;
         pk.half_thead = half;
@@ -670,7 +669,7 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
               if (rc) return rc;
               m.n_units = int(mtab.size() / 2);
             }
-          } else if (var == 4 || half) pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)), false, res);
+          } else if (vf.base == 4) pk.pack<PrecX3M16>(f, unit_mb<PrecX3M16>(var), false, blob, tab, l5_unit_mb_p<PrecX3M16>(unit_mb<PrecX3M16>(var)), false, res);
           else pk.pack<PrecX3>(f, unit_mb<PrecX3>(var), false, blob, tab, l5_unit_mb_p<PrecX3>(unit_mb<PrecX3>(var)));
         }
         int rc = upload(blob.data(), blob.size(), reinterpret_cast<void**>(&n.blob));
@@ -836,17 +835,13 @@ static int check_grad_prec(int prec, const char* fn) {
   return DFN_OK;
 }
 
-// Kernel variant: DFN_MLP_VARIANT=0..8 (A/B aid, see nerfh_layout.h).  Variant 7: split-f16 on 16x16x32 MFMAs (f16 / exact fp32 run their
-// variant-0 kernels under it) with the fine render kernel's tail folded (fold_fine, base_variant), half-height head blocks in the
-// render kernels (half_heads) and the small tail layers resident in LDS in the coarse and the plain fused fine kernel (resident_layers);
-// DFN_MLP_VARIANT=6 is the same with every layer streamed, DFN_MLP_VARIANT=5 also with full-height head blocks, DFN_MLP_VARIANT=4 also
-// without the fold, DFN_MLP_VARIANT=0 keeps the 32x32x16 split-f16 kernels.  What a process runs without DFN_MLP_VARIANT is variant 8
-// (kSelectedByDefault): variant 7 with the tiles of its two kernels claimed from a device counter; it resolves to kDefaultVariant
-// everywhere else (resolved_variant), and DFN_MLP_VARIANT=7 keeps the dealt tiles.
-constexpr int kDefaultVariant = kResidentVariant;
-constexpr int kSelectedByDefault = kDynVariant;
-static int mlp_variant_128();
-static int mlp_variant_of(dfn_nerfh_t h) { return h->desc.width == kWidth ? mlp_variant_128() : 0; }
+// The handle's range-guard flag (device int): allocated and cleared by dfn_nerfh_commit, which fails loudly when it cannot be —
+// every kernel launch that carries the guard runs on a committed handle.
+static int* range_flag_of(dfn_nerfh_t h) { return h->range_flag; }
+
+// Kernel variant: DFN_MLP_VARIANT=0..8 (A/B aid; nerfh_layout.h: kVariantFacts, kSelectedByDefault), read once.  What it means for a call
+// is nerfh_route.h; the gradient paths (render backward, dfn_mlp_fine_saving) run the base variant's / variant 0's plain kernels on
+// the plain table, which their backward kernels read.
 static int mlp_variant_128() {
   static int v = -1;
   if (v < 0) {
@@ -855,39 +850,33 @@ static int mlp_variant_128() {
   }
   return v;
 }
-// Variant 8 is variant 7 with the tiles of the two kernels launch_mlp_res has claimed from a device counter (launch_mlp_dyn, on variant
-// 7's networks): it is folded into variant 7 wherever a variant is resolved, and dyn_tiles() says which launcher those two kernels get.
-static bool dyn_tiles(dfn_nerfh_t h) { return mlp_variant_of(h) == kDynVariant; }
-static int resolved_variant(dfn_nerfh_t h) { return dyn_tiles(h) ? kResidentVariant : mlp_variant_of(h); }
-static MlpDynArgs dyn_args(const MlpResArgs& r, uint32_t* counter) {
+static const PackedNet& route_net(dfn_nerfh_t h, bool fine, int prec, const Route& r) {
+  return r.net == kNetHalfMaps ? h->half_maps : h->net[fine][prec][r.net];
+}
+// A route's launch.  a: the call's arguments over route_net(h, fine, prec, r); the resident blob and the tile counter (coarse [0],
+// fine [1]; zero_tile_counters in front of the pass) ride behind them for the two launchers that take them.
+static hipError_t launch_route(dfn_nerfh_t h, bool fine, int prec, const Route& r, const MlpArgs& a, hipStream_t s) {
+  const int cus = device_cu_count(), width = h->desc.width;
+  const PackedNet& n = route_net(h, fine, prec, r);
   MlpDynArgs d{};
-  static_cast<MlpResArgs&>(d) = r;
-  d.tile_counter = counter;
-  return d;
+  static_cast<MlpArgs&>(d) = a;
+  d.res_blob = n.res_blob;
+  d.res_bytes = n.res_bytes;
+  d.tile_counter = h->tile_counter + (fine ? 1 : 0);
+  switch (r.launcher) {
+    case kLaunchPlain: return launch_mlp(fine, prec, r.variant, a, cus, s, width);
+    case kLaunchMaps: return launch_mlp_maps(fine, prec, r.variant, a, cus, s, width);
+    case kLaunchFold: return launch_mlp_fold(r.maps, a, cus, s);
+    case kLaunchHalf: return launch_mlp_half(fine, r.maps, a, cus, s);
+    case kLaunchResident: return launch_mlp_res(fine, d, cus, s);
+    case kLaunchClaimed: return launch_mlp_dyn(fine, d, cus, s);
+    case kLaunchPoints: return launch_mlp_pts(fine, prec, a, cus, s, width);
+    case kLaunchPointsFold: return launch_mlp_pts_fold(a, cus, s);
+    case kLaunchPointsHalf: return launch_mlp_pts_half(a, cus, s);
+  }
+  return hipErrorInvalidValue;
 }
-// Variant 5 differs from variant 4 in ONE kernel: the split-f16 netwidth-128 fine render kernel (launch_mlp_fold), which reads its own
-// packed network (net[1][F16X3][5]) and a per-ray table written from rb_fold.  Every other launch under it, the gradient paths' forward
-// recompute included (their backward kernels read the plain table), is variant 4's: base_variant.
-// Variant 6 is variant 5 except in the split-f16 netwidth-128 render kernels that launch_mlp_half has: the coarse kernel, and the fine
-// kernel where the compositing is fused (plain: net[1][F16X3][6], maps: half_maps; coarse: net[0][F16X3][6]).  Its raw route runs
-// variant 5's fine kernel on variant 5's network, and everything else resolves as under variant 5.
-// Variant 7 is variant 6 except in the two kernels launch_mlp_res has: the coarse kernel (net[0][F16X3][7]) and the plain fused fine
-// kernel (net[1][F16X3][7]); the maps flavour runs variant 6's kernel on half_maps and everything else resolves as under variant 6.
-static int base_variant(int var) { return var == kFoldVariant || var == kHalfVariant || var == kResidentVariant ? 4 : var; }
-static bool fold_fine(int var, int prec) { return (var == kFoldVariant || var == kHalfVariant || var == kResidentVariant) && prec == DFN_PREC_F16X3; }
-static bool half_heads(int var, int prec) { return (var == kHalfVariant || var == kResidentVariant) && prec == DFN_PREC_F16X3; }
-static bool resident_layers(int var, int prec) { return var == kResidentVariant && prec == DFN_PREC_F16X3; }
-static MlpResArgs res_args(const MlpArgs& a, const PackedNet& n) {
-  MlpResArgs r{};
-  static_cast<MlpArgs&>(r) = a;
-  r.res_blob = n.res_blob;
-  r.res_bytes = n.res_bytes;
-  return r;
-}
-
-// The handle's range-guard flag (device int): allocated and cleared by dfn_nerfh_commit, which fails loudly when it cannot be —
-// every kernel launch that carries the guard runs on a committed handle.
-static int* range_flag_of(dfn_nerfh_t h) { return h->range_flag; }
+static hipError_t zero_tile_counters(dfn_nerfh_t h, hipStream_t s) { return hipMemsetAsync(h->tile_counter, 0, 2 * sizeof(uint32_t), s); }
 
 static unsigned long long* g_timing_buf = nullptr;  // DFN_TIMING builds only (tools/gpu_timing.py)
 extern "C" void dfn_debug_set_timing_buffer(void* p) { g_timing_buf = static_cast<unsigned long long*>(p); }
@@ -911,19 +900,14 @@ extern "C" int dfn_mlp_coarse(dfn_nerfh_t h, int prec, const float* rays_o, cons
   if (int rc = check_net(h, prec, "dfn_mlp_coarse", true)) return rc;
   if (!n_rays) return DFN_OK;
   if (!rays_o || !rays_d || !sigma || Nc < 1) return set_error(DFN_ERR_ARG, "dfn_mlp_coarse: bad argument");
-  const bool half = half_heads(resolved_variant(h), prec), res = resident_layers(resolved_variant(h), prec);
-  const int var = base_variant(resolved_variant(h));
-  const PackedNet& n = h->net[0][prec][res ? kResidentVariant : (half ? kHalfVariant : var)];
+  const Route r = coarse_route(mlp_variant_128(), h->desc.width, prec);
+  const PackedNet& n = route_net(h, false, prec, r);
   MlpArgs a{n.blob, n.tab, n.n_units, rays_o, rays_d, nullptr, nullptr, sigma, nullptr, (long long)n_rays, Nc, near, far, nullptr, n.in_scale,
             h->render_flags & DFN_RENDER_LINDISP};
   a.status = range_flag_of(h);
-  const bool dyn = res && dyn_tiles(h);
-  if (dyn) CHECK_HIP(hipMemsetAsync(h->tile_counter, 0, 2 * sizeof(uint32_t), HS(stream)), "dfn_mlp_coarse(tile counters)");
+  if (r.launcher == kLaunchClaimed) CHECK_HIP(zero_tile_counters(h, HS(stream)), "dfn_mlp_coarse(tile counters)");
   ScopedTimer t(0, HS(stream));
-  if (dyn) CHECK_HIP(launch_mlp_dyn(false, dyn_args(res_args(a, n), h->tile_counter), device_cu_count(), HS(stream)), "dfn_mlp_coarse");
-  else if (res) CHECK_HIP(launch_mlp_res(false, res_args(a, n), device_cu_count(), HS(stream)), "dfn_mlp_coarse");
-  else if (half) CHECK_HIP(launch_mlp_half(false, false, a, device_cu_count(), HS(stream)), "dfn_mlp_coarse");
-  else CHECK_HIP(launch_mlp(false, prec, var, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_coarse");
+  CHECK_HIP(launch_route(h, false, prec, r, a, HS(stream)), "dfn_mlp_coarse");
   return DFN_OK;
 }
 
@@ -1004,15 +988,13 @@ extern "C" int dfn_mlp_fine(dfn_nerfh_t h, int prec, const float* rays_o, const 
       (hist_rows != 1 && hist_rows != n_rays))
     return set_error(DFN_ERR_ARG, "dfn_mlp_fine: bad argument (hist_rows must be 1 or n_rays)");
   float* table = static_cast<float*>(bias_ws);
-  const bool fold = fold_fine(resolved_variant(h), prec);
-  const int var = fold ? kFoldVariant : base_variant(resolved_variant(h));
-  CHECK_HIP(launch_ray_bias(fold ? h->rb_fold : h->rb, viewdirs, hist, hist_rows, n_rays, table, HS(stream)), "dfn_mlp_fine(ray_bias)");
-  const PackedNet& n = h->net[1][prec][var];
+  const Route r = fine_route(mlp_variant_128(), h->desc.width, prec, false, false);
+  CHECK_HIP(launch_ray_bias(r.fold_table ? h->rb_fold : h->rb, viewdirs, hist, hist_rows, n_rays, table, HS(stream)), "dfn_mlp_fine(ray_bias)");
+  const PackedNet& n = route_net(h, true, prec, r);
   MlpArgs a{n.blob, n.tab, n.n_units, rays_o, rays_d, z_fine, table, raw, nullptr, (long long)n_rays, Nf, 0.f, 0.f, g_timing_buf, n.in_scale};
   a.status = range_flag_of(h);
   ScopedTimer t(1, HS(stream));
-  if (fold) CHECK_HIP(launch_mlp_fold(false, a, device_cu_count(), HS(stream)), "dfn_mlp_fine");
-  else CHECK_HIP(launch_mlp(true, prec, var, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_fine");
+  CHECK_HIP(launch_route(h, true, prec, r, a, HS(stream)), "dfn_mlp_fine");
   return DFN_OK;
 }
 
@@ -1053,13 +1035,8 @@ inline size_t chunk_rays(size_t n_rays, size_t max_rays = kMaxChunkRays) {
   const size_t c = passes ? (n_rays + passes - 1) / passes : 1;
   return (c + 63) & ~size_t(63);
 }
-// The route of a render call, as render_core takes it.  Compositing is fused into the fine kernel when a wave's points are one ray
-// segment and raw is not wanted: 64 samples per wave in the f16 variants 0/1/3, 32 in the split-f16 and fp32 kernels (one point block
-// per wave); the 3-block f16 variant and netwidth 256 keep the separate compositor.
-inline int fused_segment(int prec) { return prec == DFN_PREC_F16 ? 64 : 32; }
-bool fused_route(dfn_nerfh_t h, int prec, int Nf, bool want_raw) {
-  return !want_raw && Nf % fused_segment(prec) == 0 && !(prec == DFN_PREC_F16 && base_variant(resolved_variant(h)) == 2) && h->desc.width == kWidth;
-}
+// Whether a render call composites inside the fine kernel (nerfh_route.h), as render_core takes it; the caller carves for it.
+bool fused_route(dfn_nerfh_t h, int prec, int Nf, bool want_raw) { return fused_compositing(mlp_variant_128(), h->desc.width, prec, Nf, want_raw); }
 struct Workspace {
   float *o, *d, *v, *sigma, *z, *raw, *bias, *partial;
   size_t total;
@@ -1096,21 +1073,11 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
                 float* acc, float* raw_out, const Workspace& w, hipStream_t s, const MapPtrs& maps = MapPtrs{}) {
   const int Nf = Nc + Ni;
   const bool want_maps = maps.any();   // w.partial then holds kMapsRecFloats floats per segment (carve)
-  const bool fold = fold_fine(resolved_variant(h), prec);
-  const int var = base_variant(resolved_variant(h));
   const int seg = fused_segment(prec);
   const bool fused = fused_route(h, prec, Nf, raw_out != nullptr);   // the caller carved w for this route
   const int cprec = (h->render_flags & DFN_RENDER_COARSE_F16) ? DFN_PREC_F16 : prec;   // the coarse pass only places the fine samples
-  // kernel variant 6: its coarse kernel, and its fine kernel where the compositing is fused (the raw route keeps variant 5's)
-  const bool half_c = half_heads(resolved_variant(h), cprec), half_f = half_heads(resolved_variant(h), prec) && fused;
-  // kernel variant 7: its coarse kernel, and its fine kernel where variant 6's plain fused one would run (the maps flavour keeps variant 6's)
-  const bool res_c = resident_layers(resolved_variant(h), cprec), res_f = resident_layers(resolved_variant(h), prec) && fused && !want_maps;
-  const PackedNet& nc = h->net[0][cprec][res_c ? kResidentVariant : (half_c ? kHalfVariant : var)];
-  const PackedNet& nf = res_f ? h->net[1][prec][kResidentVariant]
-                      : half_f ? (want_maps ? h->half_maps : h->net[1][prec][kHalfVariant]) : h->net[1][prec][fold ? kFoldVariant : var];
-  // kernel variant 8: variant 7's two kernels with their tiles claimed from the handle's counters, zeroed in front of each pass
-  const bool dyn_c = res_c && dyn_tiles(h), dyn_f = res_f && dyn_tiles(h);
-  const int cus = device_cu_count();
+  const Route rc = coarse_route(mlp_variant_128(), h->desc.width, cprec), rf = fine_route(mlp_variant_128(), h->desc.width, prec, fused, want_maps);
+  const PackedNet &nc = route_net(h, false, cprec, rc), &nf = route_net(h, true, prec, rf);
   const size_t chunk = w.chunk;
   for (size_t r0 = 0; r0 < n_rays; r0 += chunk) {
     const size_t n = n_rays - r0 < chunk ? n_rays - r0 : chunk;
@@ -1123,12 +1090,9 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
       MlpArgs a{nc.blob, nc.tab, nc.n_units, co, cd, nullptr, nullptr, w.sigma, nullptr, (long long)n, Nc, near, far, nullptr, nc.in_scale,
                  h->render_flags & DFN_RENDER_LINDISP};
       a.status = range_flag_of(h);
-      if (dyn_c || dyn_f) CHECK_HIP(hipMemsetAsync(h->tile_counter, 0, 2 * sizeof(uint32_t), s), "render: tile counters");
+      if (rc.launcher == kLaunchClaimed || rf.launcher == kLaunchClaimed) CHECK_HIP(zero_tile_counters(h, s), "render: tile counters");
       ScopedTimer t(0, s);
-      if (dyn_c) CHECK_HIP(launch_mlp_dyn(false, dyn_args(res_args(a, nc), h->tile_counter), cus, s), "render: coarse MLP (claimed tiles)");
-      else if (res_c) CHECK_HIP(launch_mlp_res(false, res_args(a, nc), cus, s), "render: coarse MLP (resident layers)");
-      else if (half_c) CHECK_HIP(launch_mlp_half(false, false, a, cus, s), "render: coarse MLP (half-height heads)");
-      else CHECK_HIP(launch_mlp(false, cprec, var, a, cus, s, h->desc.width), "render: coarse MLP");
+      CHECK_HIP(launch_route(h, false, cprec, rc, a, s), "render: coarse MLP");
     }
     {
       ScopedTimer t(DFN_PROF_SAMPLE_FINE, s);
@@ -1137,18 +1101,13 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
     }
     {
       ScopedTimer t(DFN_PROF_RAY_BIAS, s);
-      CHECK_HIP(launch_ray_bias(fold ? h->rb_fold : h->rb, cv, ch, hist_rows, n, w.bias, s), "render: ray_bias");
+      CHECK_HIP(launch_ray_bias(rf.fold_table ? h->rb_fold : h->rb, cv, ch, hist_rows, n, w.bias, s), "render: ray_bias");
     }
     {
       MlpArgs a{nf.blob, nf.tab, nf.n_units, co, cd, w.z, w.bias, raw, fused ? w.partial : nullptr, (long long)n, Nf, 0.f, 0.f, g_timing_buf, nf.in_scale};
       a.status = range_flag_of(h);
       ScopedTimer t(1, s);
-      if (dyn_f) CHECK_HIP(launch_mlp_dyn(true, dyn_args(res_args(a, nf), h->tile_counter + 1), cus, s), "render: fine MLP (claimed tiles)");
-      else if (res_f) CHECK_HIP(launch_mlp_res(true, res_args(a, nf), cus, s), "render: fine MLP (resident layers)");
-      else if (half_f) CHECK_HIP(launch_mlp_half(true, want_maps, a, cus, s), "render: fine MLP (half-height heads)");
-      else if (fold) CHECK_HIP(launch_mlp_fold(fused && want_maps, a, cus, s), "render: fine MLP (folded)");
-      else if (fused && want_maps) CHECK_HIP(launch_mlp_maps(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP (maps)");
-      else CHECK_HIP(launch_mlp(true, prec, var, a, cus, s, h->desc.width), "render: fine MLP");
+      CHECK_HIP(launch_route(h, true, prec, rf, a, s), "render: fine MLP");
     }
     if (fused && want_maps) {
       ScopedTimer t(DFN_PROF_COMBINE, s);
@@ -1312,13 +1271,11 @@ extern "C" int dfn_mlp_coarse_points(dfn_nerfh_t h, int prec, const float* pts, 
   if (!n_rows) return DFN_OK;
   if (!pts || !sigma) return set_error(DFN_ERR_ARG, "dfn_mlp_coarse_points: bad argument");
   if (int rc = check_points(n_rows, N, "dfn_mlp_coarse_points")) return rc;
-  const bool w128 = h->desc.width == kWidth;
-  const bool half = w128 && half_heads(kDefaultVariant, prec);
-  const PackedNet& n = h->net[0][prec][half ? kHalfVariant : (w128 ? base_variant(kDefaultVariant) : 0)];
+  const Route r = coarse_route(kDefaultVariant, h->desc.width, prec, true);
+  const PackedNet& n = route_net(h, false, prec, r);
   MlpArgs a{n.blob, n.tab, n.n_units, pts, nullptr, nullptr, nullptr, sigma, nullptr, (long long)n_rows, N, 0.f, 0.f, nullptr, n.in_scale};
   a.status = range_flag_of(h);
-  if (half) CHECK_HIP(launch_mlp_pts_half(a, device_cu_count(), HS(stream)), "dfn_mlp_coarse_points");
-  else CHECK_HIP(launch_mlp_pts(false, prec, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_coarse_points");
+  CHECK_HIP(launch_route(h, false, prec, r, a, HS(stream)), "dfn_mlp_coarse_points");
   return DFN_OK;
 }
 
@@ -1330,14 +1287,12 @@ extern "C" int dfn_mlp_fine_points(dfn_nerfh_t h, int prec, const float* pts, co
     return set_error(DFN_ERR_ARG, "dfn_mlp_fine_points: bad argument (hist_rows must be 1 or n_rows)");
   if (int rc = check_points(n_rows, N, "dfn_mlp_fine_points")) return rc;
   float* table = static_cast<float*>(bias_ws);
-  const bool w128 = h->desc.width == kWidth;
-  const bool fold = w128 && fold_fine(kDefaultVariant, prec);
-  CHECK_HIP(launch_ray_bias(fold ? h->rb_fold : h->rb, viewdirs, hist, hist_rows, n_rows, table, HS(stream)), "dfn_mlp_fine_points(ray_bias)");
-  const PackedNet& n = h->net[1][prec][fold ? kFoldVariant : (w128 ? base_variant(kDefaultVariant) : 0)];
+  const Route r = fine_route(kDefaultVariant, h->desc.width, prec, false, false, true);
+  CHECK_HIP(launch_ray_bias(r.fold_table ? h->rb_fold : h->rb, viewdirs, hist, hist_rows, n_rows, table, HS(stream)), "dfn_mlp_fine_points(ray_bias)");
+  const PackedNet& n = route_net(h, true, prec, r);
   MlpArgs a{n.blob, n.tab, n.n_units, pts, nullptr, nullptr, table, raw, nullptr, (long long)n_rows, N, 0.f, 0.f, nullptr, n.in_scale};
   a.status = range_flag_of(h);
-  if (fold) CHECK_HIP(launch_mlp_pts_fold(a, device_cu_count(), HS(stream)), "dfn_mlp_fine_points");
-  else CHECK_HIP(launch_mlp_pts(true, prec, a, device_cu_count(), HS(stream), h->desc.width), "dfn_mlp_fine_points");
+  CHECK_HIP(launch_route(h, true, prec, r, a, HS(stream)), "dfn_mlp_fine_points");
   return DFN_OK;
 }
 
@@ -1457,7 +1412,7 @@ BwdWorkspace carve_bwd(char* base, size_t n_rays, int Nc, int Ni) {
 int render_backward_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const float* v, bool derive_v,
                          const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
                          const float* grad_rgb, float* go, float* gd, float* gv, const BwdWorkspace& w, hipStream_t s) {
-  const int Nf = Nc + Ni, var = base_variant(resolved_variant(h)), cus = device_cu_count();
+  const int Nf = Nc + Ni, var = route_facts(mlp_variant_128(), h->desc.width).base, cus = device_cu_count();
   const PackedNet& nc = h->net[0][prec][var];
   const PackedNet& nf = h->net[1][prec][var];
   const PackedNet& nb = h->bwd[prec];

@@ -23,7 +23,7 @@ struct MlpArgs {
   unsigned long long* timing;  // DFN_TIMING builds: per-wave cycle counters [total, dma wait, barrier, tile inputs]
   float in_scale;          // split-f16 only: weight scale x activation scale carried by the accumulators (else 1)
   int lindisp;             // coarse: depths linear in disparity instead of depth (rendering.py:272-273)
-  int dma_waves;           // waves of a workgroup that issue the weight DMA (0 = the kernel geometry's default, launch_one)
+  int dma_waves;           // waves of a workgroup that issue the weight DMA (0 = the kernel geometry's default, launch_tiles)
   int* status;             // range guard (device int, may be null): bit 0 = an f16 activation overflowed to inf, bit 1 = a
                            // split-f16 hi half saturated (DFN_RANGE_*: dfn_nerfh_range_status)
   uint32_t* masks;         // fine, split-f16, raw output: also record the ReLU signs of every hidden unit for the gradient kernel's

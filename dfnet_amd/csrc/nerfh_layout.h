@@ -132,35 +132,44 @@ constexpr float kX3ActScale = 16.f;
 // head value c of sample p lands on lane p of half 0 with one select.
 struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; static constexpr bool kSplit = true, kM16 = true; };
 
-// Kernel variants (nerfh_mlp.hip): workgroup width and staging granularity (M-blocks per unit).
+// Kernel variants (DFN_MLP_VARIANT, an A/B aid; nerfh_mlp.hip).  0 to 3 differ in workgroup width and staging granularity:
 //   variant 0: 8 waves per workgroup, 1 workgroup per CU, a unit = a whole layer (f16) / one M-block (f32)
 //   variant 1: 4 waves per workgroup, 2 workgroups per CU, a unit = 2 M-blocks (f16) / one M-block (f32)
-//   variant 3: variant 0's geometry without the pipelined epilogue (A/B reference)
 //   variant 2: 4 waves per workgroup x 3 point blocks, 1 workgroup per CU (1 wave per SIMD, 512 VGPRs), unit as variant 0
-//   variant 4: split-f16 as variant 0 on 16x16x32 MFMAs (PrecX3M16); f16 and exact fp32 run their variant-0 kernels
-//   variant 5: variant 4 with the split-f16 FINE RENDER kernel's tail folded (kFineFoldSeq, nerfh_mlp_fold.hip: 1 968 MFMAs
-//              per 32-point tile instead of 2 160); the coarse kernel and every other arithmetic mode, width and gradient path run
-//              variant 4's kernels on variant 4's weights
-//   variant 6: variant 5 with HALF-HEIGHT head M-blocks in the split-f16 render kernels (nerfh_mlp_half.hip): a PrecX3M16 head
-//              block keeps its values c = 0..3 on the 16-row half ms = 0 (head_row_m16), so static_sigma, static_rgb and -- where
-//              transient_beta reaches no output: compositing fused, no maps -- the transient head are packed and multiplied as their
-//              ms = 0 fragments only (1 920 / 1 932 MFMAs per fine tile plain / maps, 1 560 per coarse tile instead of 1 584); the
-//              raw route and everything else resolve as under variant 5
-//   variant 7: variant 6 with a fixed set of small layers RESIDENT in LDS in the two kernels the frame spends its time in, the coarse
-//              kernel and the plain fused fine kernel (nerfh_mlp_res.hip; kCoarseResident / kFineResident below): copied in once per
-//              workgroup behind the input slots and read there by every tile, they leave the streamed unit table (coarse 17 -> 14
-//              units, fine 26 -> 22 per 256-point tile) with their barriers and DMA round trips; the same fragments, MFMAs and
-//              conversion pieces in the same order: variant 6's outputs bit for bit.  The maps flavour, the raw route and everything
-//              else resolve as under variant 6
-//   variant 8: variant 7 with the tiles of its two kernels CLAIMED from a device counter instead of dealt blockIdx.x, + gridDim.x, ...
-//              (nerfh_mlp_dyn.hip: nerfh_coarse_dyn_kernel / nerfh_fine_dyn_kernel): scheduling only -- the same code computes every
-//              tile from the same inputs into the same place, on variant 7's packed networks (it packs none of its own, so it is no
-//              index of dfn_nerfh_s::net): variant 7's outputs bit for bit.  Everything else resolves as under variant 7
+//   variant 3: variant 0's geometry without the pipelined epilogue (A/B reference)
+// 4 to 8 exist in split-f16 at netwidth 128 only and each is the one before it with one thing more (kVariantFacts); every other
+// arithmetic mode, width and gradient path under them runs the `base` variant's kernels on its networks, and which kernel, network and
+// per-ray table a call runs is nerfh_route.h:
+//   variant 4: variant 0 on 16x16x32 MFMAs (PrecX3M16)
+//   variant 5: the FINE kernel's tail folded (kFineFoldSeq, nerfh_mlp_fold.hip: 1 968 MFMAs per 32-point tile instead of 2 160)
+//   variant 6: HALF-HEIGHT head M-blocks (nerfh_mlp_half.hip): a PrecX3M16 head block keeps its values c = 0..3 on the 16-row half
+//              ms = 0 (head_row_m16), so static_sigma, static_rgb and -- where transient_beta reaches no output: compositing fused, no
+//              maps -- the transient head are packed and multiplied as their ms = 0 fragments only (1 920 / 1 932 MFMAs per fine tile
+//              plain / maps, 1 560 per coarse tile instead of 1 584)
+//   variant 7: a fixed set of small layers RESIDENT in LDS in the coarse and the plain fused fine kernel (nerfh_mlp_res.hip;
+//              kCoarseResident / kFineResident below): copied in once per workgroup behind the input slots, they leave the streamed
+//              unit table (coarse 17 -> 14 units, fine 26 -> 22 per 256-point tile) with their barriers and DMA round trips; the same
+//              fragments, MFMAs and conversion pieces in the same order: variant 6's outputs bit for bit
+//   variant 8: the tiles of variant 7's two kernels CLAIMED from a device counter instead of dealt blockIdx.x, + gridDim.x, ...
+//              (nerfh_mlp_dyn.hip): scheduling only, on variant 7's packed networks (it packs none of its own, so it is no index of
+//              dfn_nerfh_s::net): variant 7's outputs bit for bit
 constexpr int kVariants = 8;   // packed networks per (coarse | fine, arithmetic): dfn_nerfh_s::net
 constexpr int kFoldVariant = 5;
 constexpr int kHalfVariant = 6;
 constexpr int kResidentVariant = 7;
 constexpr int kDynVariant = 8;
+struct VariantFacts { int base; bool fold, half, resident, claimed; };
+constexpr VariantFacts kVariantFacts[kDynVariant + 1] = {
+    {0, false, false, false, false}, {1, false, false, false, false}, {2, false, false, false, false}, {3, false, false, false, false},
+    {4, false, false, false, false},
+    {4, true, false, false, false},   // kFoldVariant
+    {4, true, true, false, false},    // kHalfVariant
+    {4, true, true, true, false},     // kResidentVariant
+    {4, true, true, true, true},      // kDynVariant
+};
+// What a process runs without DFN_MLP_VARIANT; the variant whose kernels the point queries run whatever it says
+constexpr int kSelectedByDefault = kDynVariant;
+constexpr int kDefaultVariant = kResidentVariant;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));
 }

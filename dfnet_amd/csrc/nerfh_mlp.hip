@@ -26,90 +26,75 @@
 
 namespace dfn {
 
-// The render-maps flavour of the fine kernel (MAPS below) is compiled in a translation unit of its own: nerfh_mlp_maps.hip includes
-// this file with DFN_MLP_MAPS_TU defined and gets launch_mlp_maps and the MAPS kernels only.  Every translation unit is a code
-// object of its own, so the code object of the kernels that run without maps is the one it was before the maps existed.
-#ifdef DFN_MLP_MAPS_TU
-constexpr bool kMapsTU = true;
-#define DFN_LAUNCH_MLP launch_mlp_maps
-#else
-constexpr bool kMapsTU = false;
-#define DFN_LAUNCH_MLP launch_mlp
-#endif
-// Kernel variant 5 (nerfh_layout.h: kFineFoldSeq) is a third translation unit, nerfh_mlp_fold.hip, for the same reason: it includes
-// this file with DFN_MLP_FOLD_TU defined and gets launch_mlp_fold and the fine kernel under the name nerfh_fine_fold_kernel (plain and
-// MAPS) with the folded tail below; what the other two units compile does not change by a token.
-// Kernel variant 6 (half-height head M-blocks: layer<..., HALF>) is a fourth one, nerfh_mlp_half.hip: DFN_MLP_HALF_TU on top of
-// DFN_MLP_FOLD_TU.  It gets launch_mlp_half, the folded fine kernel as nerfh_fine_half_kernel (fused compositing only, plain and MAPS)
-// and the coarse kernel as nerfh_coarse_half_kernel; in the other three units kHalfHeads is false and every layer<> below names the
-// instantiation it named before.
-// Kernel variant 7 (LDS-resident small layers: layer<..., RES>, nerfh_layout.h: kFineResident / kCoarseResident) is nerfh_mlp_res.hip:
-// DFN_MLP_RES_TU on top of DFN_MLP_HALF_TU.  It gets launch_mlp_res, the coarse kernel as nerfh_coarse_res_kernel and the plain fused
-// fine kernel as nerfh_fine_res_kernel, both taking MlpResArgs; in every other unit kResident is false, every res_base() is -1 and
-// every layer<> and trunk<> below names the instantiation it named before.
-// Kernel variant 8 (claimed tiles: Stager::claim / next, DFN_NEXT_TILE) is nerfh_mlp_dyn.hip: DFN_MLP_DYN_TU on top of DFN_MLP_RES_TU.
-// It gets launch_mlp_dyn and variant 7's two kernels as nerfh_coarse_dyn_kernel / nerfh_fine_dyn_kernel, both taking MlpDynArgs; in
-// every other unit DFN_NEXT_TILE is `tile + gridDim.x` and the tile loops are the tokens they were.
-// The points flavour (dfn_mlp_coarse_points, dfn_mlp_fine_points: DFN_MLP_PTS_TU, on top of none, DFN_MLP_FOLD_TU or DFN_MLP_HALF_TU) is
-// compiled in three more units, nerfh_mlp_pts.hip, nerfh_mlp_pts_fold.hip and nerfh_mlp_pts_half.hip: the three inputs of a point are
-// loaded from pts [n_rows, n_samples, 3] (MlpArgs::rays_o) instead of being formed as o + d z, and everything behind x[..][3] is the
-// code of the ray flavour.  The kernels carry names of their own (nerfh_*_pts_kernel) and only the raw route exists (no depths, so no
-// compositing); what the other four units compile does not change by a token.
-#if defined(DFN_MLP_PTS_TU)
-#if defined(DFN_MLP_HALF_TU)
-#define DFN_FINE_KERNEL nerfh_fine_half_pts_kernel
-#define DFN_COARSE_KERNEL nerfh_coarse_half_pts_kernel
-constexpr bool kHalfHeads = true;
-#elif defined(DFN_MLP_FOLD_TU)
-#define DFN_FINE_KERNEL nerfh_fine_fold_pts_kernel
-#define DFN_COARSE_KERNEL nerfh_coarse_fold_pts_kernel
-constexpr bool kHalfHeads = false;
-#else
-#define DFN_FINE_KERNEL nerfh_fine_pts_kernel
-#define DFN_COARSE_KERNEL nerfh_coarse_pts_kernel
-constexpr bool kHalfHeads = false;
-#endif
-#elif defined(DFN_MLP_DYN_TU)
-#define DFN_FINE_KERNEL nerfh_fine_dyn_kernel
-#define DFN_COARSE_KERNEL nerfh_coarse_dyn_kernel
-constexpr bool kHalfHeads = true;
-#elif defined(DFN_MLP_RES_TU)
-#define DFN_FINE_KERNEL nerfh_fine_res_kernel
-#define DFN_COARSE_KERNEL nerfh_coarse_res_kernel
-constexpr bool kHalfHeads = true;
-#elif defined(DFN_MLP_HALF_TU)
-#define DFN_FINE_KERNEL nerfh_fine_half_kernel
-#define DFN_COARSE_KERNEL nerfh_coarse_half_kernel
-constexpr bool kHalfHeads = true;
-#else
-#ifdef DFN_MLP_FOLD_TU
-#define DFN_FINE_KERNEL nerfh_fine_fold_kernel
-#else
-#define DFN_FINE_KERNEL nerfh_fine_kernel
-#endif
-#define DFN_COARSE_KERNEL nerfh_coarse_kernel
-constexpr bool kHalfHeads = false;
-#endif
-
-#if defined(DFN_MLP_RES_TU)
-#if !defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_PTS_TU)
+// One translation unit (= one code object) per flavour: a wrapper file (nerfh_mlp_{maps,fold,half,res,dyn,pts,pts_fold,pts_half}.hip)
+// sets DFN_MLP_*_TU flags and includes this file, and gets the kernels and the launcher named below and nothing else, so the code
+// objects of the other units do not change by a token when a unit is added.  The flags are cumulative (nerfh_layout.h "Kernel variants"):
+//   DFN_MLP_MAPS_TU   launch_mlp_maps: the MAPS instantiations of the plain fine kernels (the render-maps segment record)
+//   DFN_MLP_FOLD_TU   variant 5: the fine kernel with the folded tail (kFineFoldSeq)
+//   DFN_MLP_HALF_TU   variant 6, on FOLD: half-height head M-blocks (layer<..., HALF>), coarse and fine
+//   DFN_MLP_RES_TU    variant 7, on HALF: small layers resident in LDS (layer<..., RES>), MlpResArgs
+//   DFN_MLP_DYN_TU    variant 8, on RES: tiles claimed from a device counter (Stager::claim / next), MlpDynArgs
+//   DFN_MLP_PTS_TU    the points flavour, on none, FOLD or HALF: the inputs are loaded from pts [n_rows, n_samples, 3] (MlpArgs::rays_o)
+//                     instead of being formed as o + d z; the raw route only (no depths, so no compositing)
+// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn].
+#if defined(DFN_MLP_RES_TU) && (!defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_PTS_TU))
 #error "the resident layers exist in the half-height render kernels"
 #endif
-constexpr bool kResident = true;
-#if defined(DFN_MLP_DYN_TU)
-#define DFN_MLP_KARGS MlpDynArgs
-#else
-#define DFN_MLP_KARGS MlpResArgs
-#endif
-#else
-#if defined(DFN_MLP_DYN_TU)
+#if defined(DFN_MLP_DYN_TU) && !defined(DFN_MLP_RES_TU)
 #error "the claimed tiles exist in the kernels with resident layers"
 #endif
-constexpr bool kResident = false;
+#if defined(DFN_MLP_DYN_TU)
+#define DFN_TU_TAG _dyn
+#define DFN_MLP_KARGS MlpDynArgs
+#elif defined(DFN_MLP_RES_TU)
+#define DFN_TU_TAG _res
+#define DFN_MLP_KARGS MlpResArgs
+#elif defined(DFN_MLP_HALF_TU)
+#define DFN_TU_TAG _half
+#elif defined(DFN_MLP_FOLD_TU)
+#define DFN_TU_TAG _fold
+#else
+#define DFN_TU_TAG
+#endif
+#ifndef DFN_MLP_KARGS
 #define DFN_MLP_KARGS MlpArgs
 #endif
+#ifdef DFN_MLP_PTS_TU
+#define DFN_TU_PTS _pts
+#else
+#define DFN_TU_PTS
+#endif
+#ifdef DFN_MLP_MAPS_TU
+#define DFN_TU_MAPS _maps
+#else
+#define DFN_TU_MAPS
+#endif
+#define DFN_PASTE4_(a, b, c, d) a##b##c##d
+#define DFN_PASTE4(a, b, c, d) DFN_PASTE4_(a, b, c, d)
+#define DFN_FINE_KERNEL DFN_PASTE4(nerfh_fine, DFN_TU_TAG, DFN_TU_PTS, _kernel)
+#if defined(DFN_MLP_FOLD_TU) && !defined(DFN_MLP_HALF_TU) && !defined(DFN_MLP_PTS_TU)
+#define DFN_COARSE_KERNEL nerfh_coarse_kernel   // nerfh_mlp_fold.hip has no coarse kernel: the template keeps the plain name
+#else
+#define DFN_COARSE_KERNEL DFN_PASTE4(nerfh_coarse, DFN_TU_TAG, DFN_TU_PTS, _kernel)
+#endif
+#define DFN_LAUNCH_MLP DFN_PASTE4(launch_mlp, DFN_TU_MAPS, DFN_TU_PTS, DFN_TU_TAG)
+#ifdef DFN_MLP_MAPS_TU
+constexpr bool kMapsTU = true;
+#else
+constexpr bool kMapsTU = false;
+#endif
+#ifdef DFN_MLP_HALF_TU
+constexpr bool kHalfHeads = true;
+#else
+constexpr bool kHalfHeads = false;
+#endif
+#ifdef DFN_MLP_RES_TU
+constexpr bool kResident = true;
+#else
+constexpr bool kResident = false;
+#endif
 // the tile a workgroup computes after `tile` (inside the kernels' tile loops): dealt, or claimed (kernel variant 8: Stager::next)
-#if defined(DFN_MLP_DYN_TU)
+#ifdef DFN_MLP_DYN_TU
 #define DFN_NEXT_TILE (static_cast<long long>(st.next))
 #else
 #define DFN_NEXT_TILE (tile + gridDim.x)
@@ -208,7 +193,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #endif
     constexpr int LP = lane_pts<P>(NB);
     float x[LP][3];
-    uint32_t pt[NB];   // launch_one() bounds a launch to < 2^31 points: 32-bit indices (64-bit ones cost 2 registers each and spilled)
+    uint32_t pt[NB];   // launch_tiles() bounds a launch to < 2^31 points: 32-bit indices (64-bit ones cost 2 registers each and spilled)
     const uint32_t npts = uint32_t(n_pts);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) pt[nb] = uint32_t(tile) * uint32_t(PPT) + st.wave * (NB * 32) + nb * 32 + p;   // the lane's output
@@ -305,7 +290,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #else
   float zin[LP], znext[LP], oin[LP][3], din[LP][3];
 #endif
-  // launch_one() guarantees n_pts < 2^31: point / ray indices are 32-bit (as 64-bit values and as per-ray table POINTERS held
+  // launch_tiles() guarantees n_pts < 2^31: point / ray indices are 32-bit (as 64-bit values and as per-ray table POINTERS held
   // across the trunk they cost 16 registers at NB = 2 and the f16 kernel spilled them: any scratch use costs this kernel clock)
   uint32_t pt[LP], ray_of[LP];
   const uint32_t npts = uint32_t(n_pts);
@@ -621,50 +606,62 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 }
 
 // ------------------------------------------------------------------------------------------
-#if defined(DFN_MLP_PTS_TU)
-// The points flavour's launchers.  One geometry per (unit, arithmetic), the one the raw route of the ray entries runs at the default
-// kernel variant, so that a point equal to o + d z gives the bits the ray entry gives.
-template <class P, bool FAST, int WAVES, int UMB, int NB, bool PIPE, int W, bool FINE>
-static hipError_t launch_pts_one(const MlpArgs& a, int n_cu, hipStream_t stream) {
-  constexpr int PPT = WAVES * NB * 32;
+// The launch every launcher below ends in.  kern: the kernel the launcher picked, null where it refuses the arguments (an empty launch
+// succeeds before that is looked at); attr_done: the launcher's flag of this kernel, so that its LDS size is set once per kernel.
+static int dma_waves_env() {   // DFN_DMA_WAVES=n: A/B aid, read once
+  static int env = -1;
+  if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
+  return env;
+}
+template <class A, int PPT, int WG_PER_CU, int WAVES>
+static hipError_t launch_tiles(void (*kern)(A), bool& attr_done, uint32_t lds, const A& a, int n_cu, hipStream_t stream) {
   const long long n_pts = (long long)a.n_rays * a.n_samples;
   if (n_pts <= 0) return hipSuccess;
-  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
-  if (a.masks || a.partial || !a.rays_o || !a.out) return hipErrorInvalidValue;   // raw route only: points have no depths to composite along
+  if (n_pts >= (1LL << 31) || !kern) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
   const long long n_tiles = (n_pts + PPT - 1) / PPT;
-  const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
-  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB, W>();
-  void (*kern)(MlpArgs) = nullptr;
-  if constexpr (FINE) kern = DFN_FINE_KERNEL<P, FAST, WAVES, UMB, NB, PIPE, W>;
-  else kern = DFN_COARSE_KERNEL<P, FAST, WAVES, UMB, NB, PIPE, W>;
-  static bool attr_done = false;
+  const long long slots = (long long)n_cu * WG_PER_CU;  // resident workgroups
+  const int grid = int(n_tiles < slots ? n_tiles : slots);
   if (!attr_done) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
     if (e != hipSuccess) return e;
     attr_done = true;
   }
-  MlpArgs b = a;
-  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid, as launch_mlp
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
-    b.dma_waves = env > 0 ? env : (WAVES == 8 ? 4 : WAVES);
-  }
+  A b = a;
+  // 8-wave workgroups: the four older waves idle a third of their time at the unit barriers
+  if (b.dma_waves == 0) b.dma_waves = dma_waves_env() > 0 ? dma_waves_env() : (WAVES == 8 ? 4 : WAVES);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
   return hipGetLastError();
 }
+// the geometry of the PrecX3M16 kernels of variants 5 to 8: variant 4's (launch_one<PrecX3M16, false, 8, 2, 1, 1, true> below)
+using PM = PrecX3M16;
+constexpr int kMWaves = 8, kMUmb = unit_mb<PM>(0), kMNb = 1, kMPpt = kMWaves * kMNb * 32;
+
+#if defined(DFN_MLP_PTS_TU)
+// The points flavour's launchers.  One geometry per (unit, arithmetic), the one the raw route of the ray entries runs at the default
+// kernel variant, so that a point equal to o + d z gives the bits the ray entry gives.
+template <class P, bool FAST, int WAVES, int UMB, int NB, bool PIPE, int W, bool FINE>
+static hipError_t launch_pts_one(const MlpArgs& a, int n_cu, hipStream_t stream) {
+  void (*kern)(MlpArgs) = nullptr;
+  if constexpr (FINE) kern = DFN_FINE_KERNEL<P, FAST, WAVES, UMB, NB, PIPE, W>;
+  else kern = DFN_COARSE_KERNEL<P, FAST, WAVES, UMB, NB, PIPE, W>;
+  if (a.masks || a.partial || !a.rays_o || !a.out) kern = nullptr;   // raw route only: points have no depths to composite along
+  static bool attr_done = false;
+  return launch_tiles<MlpArgs, WAVES * NB * 32, 1, WAVES>(kern, attr_done, lds_bytes<P, UMB, WAVES, NB, W>(), a, n_cu, stream);
+}
 #if defined(DFN_MLP_HALF_TU)
-// split-f16, netwidth 128, coarse: variant 6's half-height kernel (launch_mlp_half's geometry) on net[0][F16X3][6]
-hipError_t launch_mlp_pts_half(const MlpArgs& a, int n_cu, hipStream_t stream) {
-  return launch_pts_one<PrecX3M16, false, 8, unit_mb<PrecX3M16>(0), 1, true, kWidth, false>(a, n_cu, stream);
+// launch_mlp_pts_half: split-f16, netwidth 128, coarse: variant 6's half-height kernel on net[0][F16X3][6]
+hipError_t DFN_LAUNCH_MLP(const MlpArgs& a, int n_cu, hipStream_t stream) {
+  return launch_pts_one<PM, false, kMWaves, kMUmb, kMNb, true, kWidth, false>(a, n_cu, stream);
 }
 #elif defined(DFN_MLP_FOLD_TU)
-// split-f16, netwidth 128, fine: variant 5's folded kernel (launch_mlp_fold's geometry) on net[1][F16X3][5], a.ray_bias from rb_fold
-hipError_t launch_mlp_pts_fold(const MlpArgs& a, int n_cu, hipStream_t stream) {
-  return launch_pts_one<PrecX3M16, false, 8, unit_mb<PrecX3M16>(0), 1, true, kWidth, true>(a, n_cu, stream);
+// launch_mlp_pts_fold: split-f16, netwidth 128, fine: variant 5's folded kernel on net[1][F16X3][5], a.ray_bias from rb_fold
+hipError_t DFN_LAUNCH_MLP(const MlpArgs& a, int n_cu, hipStream_t stream) {
+  return launch_pts_one<PM, false, kMWaves, kMUmb, kMNb, true, kWidth, true>(a, n_cu, stream);
 }
 #else
-// f16 and exact fp32 at netwidth 128 (their variant-0 kernels) and the three plain kernels of netwidth 256, as launch_mlp picks them
-hipError_t launch_mlp_pts(bool fine, int prec, const MlpArgs& a, int n_cu, hipStream_t stream, int width) {
+// launch_mlp_pts: f16 and exact fp32 at netwidth 128 (their variant-0 kernels) and the three plain kernels of netwidth 256, as
+// launch_mlp picks them
+hipError_t DFN_LAUNCH_MLP(bool fine, int prec, const MlpArgs& a, int n_cu, hipStream_t stream, int width) {
   if (width == 256) {
     if (prec == 0) {
       return fine ? launch_pts_one<PrecF16, true, 8, unit_mb_w256<PrecF16>(), 1, false, 256, true>(a, n_cu, stream)
@@ -687,169 +684,61 @@ hipError_t launch_mlp_pts(bool fine, int prec, const MlpArgs& a, int n_cu, hipSt
               : launch_pts_one<PrecF32, false, 8, 1, 1, false, kWidth, false>(a, n_cu, stream);
 }
 #endif
-#elif defined(DFN_MLP_DYN_TU)
-// variant 8's kernels: variant 7's (geometry, networks, resident region) with the claimed-tile word behind the region.  The grid is
-// variant 7's: min(tiles, CUs) workgroups, each starting on tile blockIdx.x; *a.tile_counter is 0 at the start (the caller's memset).
-hipError_t launch_mlp_dyn(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream) {
-  using P = PrecX3M16;
-  constexpr int WAVES = 8, UMB = unit_mb<P>(0), NB = 1, PPT = WAVES * NB * 32;
-  const long long n_pts = (long long)a.n_rays * a.n_samples;
-  if (n_pts <= 0) return hipSuccess;
-  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
-  if (a.masks || (fine && !a.partial) || !a.tile_counter) return hipErrorInvalidValue;
-  if (!a.res_blob || a.res_bytes != resident_bytes<P>(fine)) return hipErrorInvalidValue;   // the kernels copy exactly this many bytes
-  const long long n_tiles = (n_pts + PPT - 1) / PPT;
-  const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
-  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB>() + resident_bytes<P>(fine) + kClaimBytes;
-  void (*kern)(MlpDynArgs) = fine ? nerfh_fine_dyn_kernel<P, false, WAVES, UMB, NB, true> : nerfh_coarse_dyn_kernel<P, false, WAVES, UMB, NB, true>;
-  static bool attr_done[2] = {false, false};
-  if (!attr_done[fine]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-    if (e != hipSuccess) return e;
-    attr_done[fine] = true;
-  }
-  MlpDynArgs b = a;
-  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid, as launch_mlp
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
-    b.dma_waves = env > 0 ? env : 4;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
-  return hipGetLastError();
-}
 #elif defined(DFN_MLP_RES_TU)
-// variant 7's kernels: variant 6's geometry with the resident region behind the input slots.  coarse; fine with the compositing fused,
-// plain flavour -- the maps flavour stays with launch_mlp_half, the raw route with launch_mlp_fold.
-hipError_t launch_mlp_res(bool fine, const MlpResArgs& a, int n_cu, hipStream_t stream) {
-  using P = PrecX3M16;
-  constexpr int WAVES = 8, UMB = unit_mb<P>(0), NB = 1, PPT = WAVES * NB * 32;
-  const long long n_pts = (long long)a.n_rays * a.n_samples;
-  if (n_pts <= 0) return hipSuccess;
-  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
-  if (a.masks || (fine && !a.partial)) return hipErrorInvalidValue;
-  if (!a.res_blob || a.res_bytes != resident_bytes<P>(fine)) return hipErrorInvalidValue;   // the kernels copy exactly this many bytes
-  const long long n_tiles = (n_pts + PPT - 1) / PPT;
-  const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
-  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB>() + resident_bytes<P>(fine);
-  void (*kern)(MlpResArgs) = fine ? nerfh_fine_res_kernel<P, false, WAVES, UMB, NB, true> : nerfh_coarse_res_kernel<P, false, WAVES, UMB, NB, true>;
+// launch_mlp_res: variant 7's kernels, variant 6's geometry with the resident region behind the input slots.  coarse; fine with the
+// compositing fused, plain flavour -- the maps flavour stays with launch_mlp_half, the raw route with launch_mlp_fold.
+// launch_mlp_dyn: variant 8's, the same with the claimed-tile word behind the region.  The grid is variant 7's: min(tiles, CUs)
+// workgroups, each starting on tile blockIdx.x; *a.tile_counter is 0 at the start (the caller's memset).
+hipError_t DFN_LAUNCH_MLP(bool fine, const DFN_MLP_KARGS& a, int n_cu, hipStream_t stream) {
+  void (*kern)(DFN_MLP_KARGS) = fine ? DFN_FINE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true> : DFN_COARSE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true>;
+  uint32_t lds = lds_bytes<PM, kMUmb, kMWaves, kMNb>() + resident_bytes<PM>(fine);
+  if (a.masks || (fine && !a.partial)) kern = nullptr;
+  if (!a.res_blob || a.res_bytes != resident_bytes<PM>(fine)) kern = nullptr;   // the kernels copy exactly this many bytes
+#ifdef DFN_MLP_DYN_TU
+  if (!a.tile_counter) kern = nullptr;
+  lds += kClaimBytes;
+#endif
   static bool attr_done[2] = {false, false};
-  if (!attr_done[fine]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-    if (e != hipSuccess) return e;
-    attr_done[fine] = true;
-  }
-  MlpResArgs b = a;
-  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid, as launch_mlp
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
-    b.dma_waves = env > 0 ? env : 4;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
-  return hipGetLastError();
+  return launch_tiles<DFN_MLP_KARGS, kMPpt, 1, kMWaves>(kern, attr_done[fine], lds, a, n_cu, stream);
 }
 #elif defined(DFN_MLP_HALF_TU)
-// variant 6's kernels: variant 4's geometry (launch_one<PrecX3M16, false, 8, 2, 1, 1, true> below).  coarse; fine with the compositing
-// fused, plain or render-maps flavour -- the raw route (a.partial == nullptr) stays with launch_mlp_fold.
-hipError_t launch_mlp_half(bool fine, bool maps, const MlpArgs& a, int n_cu, hipStream_t stream) {
-  using P = PrecX3M16;
-  constexpr int WAVES = 8, UMB = unit_mb<P>(0), NB = 1, PPT = WAVES * NB * 32;
-  const long long n_pts = (long long)a.n_rays * a.n_samples;
-  if (n_pts <= 0) return hipSuccess;
-  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
-  if (a.masks || (fine && !a.partial) || (maps && !fine)) return hipErrorInvalidValue;
-  const long long n_tiles = (n_pts + PPT - 1) / PPT;
-  const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
-  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB>();
-  const int slot = fine ? (maps ? 2 : 1) : 0;
-  void (*kern)(MlpArgs) = !fine ? nerfh_coarse_half_kernel<P, false, WAVES, UMB, NB, true>
-                          : maps ? nerfh_fine_half_kernel<P, false, WAVES, UMB, NB, true, kWidth, false, true>
-                                 : nerfh_fine_half_kernel<P, false, WAVES, UMB, NB, true>;
+// launch_mlp_half: variant 6's kernels.  coarse; fine with the compositing fused, plain or render-maps flavour -- the raw route
+// (a.partial == nullptr) stays with launch_mlp_fold.
+hipError_t DFN_LAUNCH_MLP(bool fine, bool maps, const MlpArgs& a, int n_cu, hipStream_t stream) {
+  void (*kern)(MlpArgs) = !fine ? nerfh_coarse_half_kernel<PM, false, kMWaves, kMUmb, kMNb, true>
+                          : maps ? nerfh_fine_half_kernel<PM, false, kMWaves, kMUmb, kMNb, true, kWidth, false, true>
+                                 : nerfh_fine_half_kernel<PM, false, kMWaves, kMUmb, kMNb, true>;
+  if (a.masks || (fine && !a.partial) || (maps && !fine)) kern = nullptr;
   static bool attr_done[3] = {false, false, false};
-  if (!attr_done[slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-    if (e != hipSuccess) return e;
-    attr_done[slot] = true;
-  }
-  MlpArgs b = a;
-  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid, as launch_mlp
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
-    b.dma_waves = env > 0 ? env : 4;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
-  return hipGetLastError();
+  return launch_tiles<MlpArgs, kMPpt, 1, kMWaves>(kern, attr_done[fine ? (maps ? 2 : 1) : 0], lds_bytes<PM, kMUmb, kMWaves, kMNb>(), a, n_cu, stream);
 }
 #elif defined(DFN_MLP_FOLD_TU)
-// variant 5's fine kernel: variant 4's geometry (launch_one<PrecX3M16, false, 8, 2, 1, 1, true> below), plain or render-maps flavour
-hipError_t launch_mlp_fold(bool maps, const MlpArgs& a, int n_cu, hipStream_t stream) {
-  using P = PrecX3M16;
-  constexpr int WAVES = 8, UMB = unit_mb<P>(0), NB = 1, PPT = WAVES * NB * 32;
-  const long long n_pts = (long long)a.n_rays * a.n_samples;
-  if (n_pts <= 0) return hipSuccess;
-  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
-  if (a.masks || (maps && !a.partial)) return hipErrorInvalidValue;
-  const long long n_tiles = (n_pts + PPT - 1) / PPT;
-  const int grid = int(n_tiles < n_cu ? n_tiles : n_cu);
-  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB>();
-  void (*kern)(MlpArgs) = maps ? nerfh_fine_fold_kernel<P, false, WAVES, UMB, NB, true, kWidth, false, true>
-                               : nerfh_fine_fold_kernel<P, false, WAVES, UMB, NB, true>;
+// launch_mlp_fold: variant 5's fine kernel, plain or render-maps flavour
+hipError_t DFN_LAUNCH_MLP(bool maps, const MlpArgs& a, int n_cu, hipStream_t stream) {
+  void (*kern)(MlpArgs) = maps ? nerfh_fine_fold_kernel<PM, false, kMWaves, kMUmb, kMNb, true, kWidth, false, true>
+                               : nerfh_fine_fold_kernel<PM, false, kMWaves, kMUmb, kMNb, true>;
+  if (a.masks || (maps && !a.partial)) kern = nullptr;
   static bool attr_done[2] = {false, false};
-  if (!attr_done[maps]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-    if (e != hipSuccess) return e;
-    attr_done[maps] = true;
-  }
-  MlpArgs b = a;
-  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid, as launch_mlp
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
-    b.dma_waves = env > 0 ? env : 4;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
-  return hipGetLastError();
+  return launch_tiles<MlpArgs, kMPpt, 1, kMWaves>(kern, attr_done[maps], lds_bytes<PM, kMUmb, kMWaves, kMNb>(), a, n_cu, stream);
 }
 #else
 template <class P, bool FAST, int WAVES, int UMB, int NB, int WG_PER_CU, bool PIPE, int W = kWidth>
 static hipError_t launch_one(bool fine, const MlpArgs& a, int n_cu, hipStream_t stream) {
-  constexpr int PPT = WAVES * NB * 32;
-  const long long n_pts = (long long)a.n_rays * a.n_samples;
-  if (n_pts <= 0) return hipSuccess;
-  if (n_pts >= (1LL << 31)) return hipErrorInvalidValue;  // kernels index points with 32 bits; callers chunk
-  const long long n_tiles = (n_pts + PPT - 1) / PPT;
-  const long long slots = (long long)n_cu * WG_PER_CU;  // resident workgroups
-  const int grid = int(n_tiles < slots ? n_tiles : slots);
-  const uint32_t lds = lds_bytes<P, UMB, WAVES, NB, W>();
   void (*kern)(MlpArgs) = nullptr;
   int slot = fine ? 1 : 0;
   if constexpr (kMapsTU) {
     // render maps: the fused fine kernel with the kMapsRecFloats-float segment record, where the fused compositing exists at all
     if constexpr (W == kWidth && NB <= 2) {
-      if (!fine || !a.partial || a.masks) return hipErrorInvalidValue;
-      kern = nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W, false, true>;
-    } else {
-      return hipErrorInvalidValue;
+      if (fine && a.partial && !a.masks) kern = nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W, false, true>;
     }
   } else {
     kern = fine ? nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W> : nerfh_coarse_kernel<P, FAST, WAVES, UMB, NB, PIPE, W>;
     if constexpr (P::kSplit && !P::kM16 && NB == 1 && WAVES == 8 && W == kWidth && PIPE) {
       if (fine && a.masks) { kern = nerfh_fine_kernel<P, FAST, WAVES, UMB, NB, PIPE, W, true>; slot = 2; }
-    } else if (a.masks) return hipErrorInvalidValue;
+    } else if (a.masks) kern = nullptr;
   }
   static bool attr_done[3] = {false, false, false};
-  if (!attr_done[slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-    if (e != hipSuccess) return e;
-    attr_done[slot] = true;
-  }
-  MlpArgs b = a;
-  if (b.dma_waves == 0) {  // DFN_DMA_WAVES=n: A/B aid
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("DFN_DMA_WAVES"); env = e ? atoi(e) : 0; }
-    b.dma_waves = env > 0 ? env : (WAVES == 8 ? 4 : WAVES);  // 8-wave workgroups: the four older waves idle a third of their time at the unit barriers
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
-  return hipGetLastError();
+  return launch_tiles<MlpArgs, WAVES * NB * 32, WG_PER_CU, WAVES>(kern, attr_done[slot], lds_bytes<P, UMB, WAVES, NB, W>(), a, n_cu, stream);
 }
 
 // variant 0: 8 waves x NB 2, 1 WG/CU, unit = layer, epilogue pipelined into the next M-block's MFMAs
