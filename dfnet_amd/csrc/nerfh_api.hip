@@ -839,14 +839,14 @@ static int check_grad_prec(int prec, const char* fn) {
 // every kernel launch that carries the guard runs on a committed handle.
 static int* range_flag_of(dfn_nerfh_t h) { return h->range_flag; }
 
-// Kernel variant: DFN_MLP_VARIANT=0..8 (A/B aid; nerfh_layout.h: kVariantFacts, kSelectedByDefault), read once.  What it means for a call
+// Kernel variant: DFN_MLP_VARIANT=0..9 (A/B aid; nerfh_layout.h: kVariantFacts, kSelectedByDefault), read once.  What it means for a call
 // is nerfh_route.h; the gradient paths (render backward, dfn_mlp_fine_saving) run the base variant's / variant 0's plain kernels on
 // the plain table, which their backward kernels read.
 static int mlp_variant_128() {
   static int v = -1;
   if (v < 0) {
     const char* e = getenv("DFN_MLP_VARIANT");
-    v = (e && e[0] >= '0' && e[0] <= '0' + kDynVariant) ? e[0] - '0' : kSelectedByDefault;
+    v = (e && e[0] >= '0' && e[0] <= '0' + kLastVariant) ? e[0] - '0' : kSelectedByDefault;
   }
   return v;
 }
@@ -870,6 +870,7 @@ static hipError_t launch_route(dfn_nerfh_t h, bool fine, int prec, const Route& 
     case kLaunchHalf: return launch_mlp_half(fine, r.maps, a, cus, s);
     case kLaunchResident: return launch_mlp_res(fine, d, cus, s);
     case kLaunchClaimed: return launch_mlp_dyn(fine, d, cus, s);
+    case kLaunchKept: return launch_mlp_pe(fine, d, cus, s);
     case kLaunchPoints: return launch_mlp_pts(fine, prec, a, cus, s, width);
     case kLaunchPointsFold: return launch_mlp_pts_fold(a, cus, s);
     case kLaunchPointsHalf: return launch_mlp_pts_half(a, cus, s);
@@ -905,7 +906,7 @@ extern "C" int dfn_mlp_coarse(dfn_nerfh_t h, int prec, const float* rays_o, cons
   MlpArgs a{n.blob, n.tab, n.n_units, rays_o, rays_d, nullptr, nullptr, sigma, nullptr, (long long)n_rays, Nc, near, far, nullptr, n.in_scale,
             h->render_flags & DFN_RENDER_LINDISP};
   a.status = range_flag_of(h);
-  if (r.launcher == kLaunchClaimed) CHECK_HIP(zero_tile_counters(h, HS(stream)), "dfn_mlp_coarse(tile counters)");
+  if (claims_tiles(r.launcher)) CHECK_HIP(zero_tile_counters(h, HS(stream)), "dfn_mlp_coarse(tile counters)");
   ScopedTimer t(0, HS(stream));
   CHECK_HIP(launch_route(h, false, prec, r, a, HS(stream)), "dfn_mlp_coarse");
   return DFN_OK;
@@ -1090,7 +1091,7 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
       MlpArgs a{nc.blob, nc.tab, nc.n_units, co, cd, nullptr, nullptr, w.sigma, nullptr, (long long)n, Nc, near, far, nullptr, nc.in_scale,
                  h->render_flags & DFN_RENDER_LINDISP};
       a.status = range_flag_of(h);
-      if (rc.launcher == kLaunchClaimed || rf.launcher == kLaunchClaimed) CHECK_HIP(zero_tile_counters(h, s), "render: tile counters");
+      if (claims_tiles(rc.launcher) || claims_tiles(rf.launcher)) CHECK_HIP(zero_tile_counters(h, s), "render: tile counters");
       ScopedTimer t(0, s);
       CHECK_HIP(launch_route(h, false, cprec, rc, a, s), "render: coarse MLP");
     }

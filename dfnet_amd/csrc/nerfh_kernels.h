@@ -57,6 +57,9 @@ struct MlpDynArgs : MlpResArgs {
   uint32_t* tile_counter;
 };
 hipError_t launch_mlp_dyn(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
+// Kernel variant 9 (nerfh_mlp_pe.hip): variant 8's two kernels with the positional encoding kept for the skip concat instead of
+// formed twice per tile.  Variant 8's arguments, networks, resident blob and counter.
+hipError_t launch_mlp_pe(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
 
 // The points flavour (nerfh_mlp_pts*.hip): a.rays_o is pts [n_rays, n_samples, 3] (n_rays = query rows), a.rays_d, a.z and a.partial
 // are unused (a.partial must be null: the raw route only), a.ray_bias has one row per query row.  launch_mlp_pts: f16 / exact fp32 at

@@ -137,7 +137,7 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //   variant 1: 4 waves per workgroup, 2 workgroups per CU, a unit = 2 M-blocks (f16) / one M-block (f32)
 //   variant 2: 4 waves per workgroup x 3 point blocks, 1 workgroup per CU (1 wave per SIMD, 512 VGPRs), unit as variant 0
 //   variant 3: variant 0's geometry without the pipelined epilogue (A/B reference)
-// 4 to 8 exist in split-f16 at netwidth 128 only and each is the one before it with one thing more (kVariantFacts); every other
+// 4 to 9 exist in split-f16 at netwidth 128 only and each is the one before it with one thing more (kVariantFacts); every other
 // arithmetic mode, width and gradient path under them runs the `base` variant's kernels on its networks, and which kernel, network and
 // per-ray table a call runs is nerfh_route.h:
 //   variant 4: variant 0 on 16x16x32 MFMAs (PrecX3M16)
@@ -153,22 +153,30 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //   variant 8: the tiles of variant 7's two kernels CLAIMED from a device counter instead of dealt blockIdx.x, + gridDim.x, ...
 //              (nerfh_mlp_dyn.hip): scheduling only, on variant 7's packed networks (it packs none of its own, so it is no index of
 //              dfn_nerfh_s::net): variant 7's outputs bit for bit
+//   variant 9: the positional encoding of variant 8's two kernels formed ONCE per tile and KEPT for the skip concat in front of layer 5
+//              instead of formed a second time there (nerfh_mlp_pe.hip; trunk() in nerfh_mlp_core.h): 32 registers live across layers
+//              2 to 4, which the 16x16x32 kernels have free, against 231 vector instructions per tile and wave, 32 of them quarter-rate
+//              v_sin / v_cos.  The kept operand is the value the second evaluation gives: variant 8's outputs bit for bit, on variant
+//              7's packed networks, variant 8's per-ray table and tile counters
 constexpr int kVariants = 8;   // packed networks per (coarse | fine, arithmetic): dfn_nerfh_s::net
 constexpr int kFoldVariant = 5;
 constexpr int kHalfVariant = 6;
 constexpr int kResidentVariant = 7;
 constexpr int kDynVariant = 8;
-struct VariantFacts { int base; bool fold, half, resident, claimed; };
-constexpr VariantFacts kVariantFacts[kDynVariant + 1] = {
+constexpr int kKeptVariant = 9;
+constexpr int kLastVariant = kKeptVariant;   // DFN_MLP_VARIANT = 0 .. kLastVariant
+struct VariantFacts { int base; bool fold, half, resident, claimed, kept; };   // kept: the encoding, for the skip concat
+constexpr VariantFacts kVariantFacts[kLastVariant + 1] = {
     {0, false, false, false, false}, {1, false, false, false, false}, {2, false, false, false, false}, {3, false, false, false, false},
     {4, false, false, false, false},
     {4, true, false, false, false},   // kFoldVariant
     {4, true, true, false, false},    // kHalfVariant
     {4, true, true, true, false},     // kResidentVariant
     {4, true, true, true, true},      // kDynVariant
+    {4, true, true, true, true, true},   // kKeptVariant
 };
 // What a process runs without DFN_MLP_VARIANT; the variant whose kernels the point queries run whatever it says
-constexpr int kSelectedByDefault = kDynVariant;
+constexpr int kSelectedByDefault = kKeptVariant;
 constexpr int kDefaultVariant = kResidentVariant;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));

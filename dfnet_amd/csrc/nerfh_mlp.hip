@@ -26,7 +26,7 @@
 
 namespace dfn {
 
-// One translation unit (= one code object) per flavour: a wrapper file (nerfh_mlp_{maps,fold,half,res,dyn,pts,pts_fold,pts_half}.hip)
+// One translation unit (= one code object) per flavour: a wrapper file (nerfh_mlp_{maps,fold,half,res,dyn,pe,pts,pts_fold,pts_half}.hip)
 // sets DFN_MLP_*_TU flags and includes this file, and gets the kernels and the launcher named below and nothing else, so the code
 // objects of the other units do not change by a token when a unit is added.  The flags are cumulative (nerfh_layout.h "Kernel variants"):
 //   DFN_MLP_MAPS_TU   launch_mlp_maps: the MAPS instantiations of the plain fine kernels (the render-maps segment record)
@@ -34,16 +34,23 @@ namespace dfn {
 //   DFN_MLP_HALF_TU   variant 6, on FOLD: half-height head M-blocks (layer<..., HALF>), coarse and fine
 //   DFN_MLP_RES_TU    variant 7, on HALF: small layers resident in LDS (layer<..., RES>), MlpResArgs
 //   DFN_MLP_DYN_TU    variant 8, on RES: tiles claimed from a device counter (Stager::claim / next), MlpDynArgs
+//   DFN_MLP_PE_TU     variant 9, on DYN: the positional encoding kept for the skip concat (trunk(): kEncodingKept), MlpDynArgs
 //   DFN_MLP_PTS_TU    the points flavour, on none, FOLD or HALF: the inputs are loaded from pts [n_rows, n_samples, 3] (MlpArgs::rays_o)
 //                     instead of being formed as o + d z; the raw route only (no depths, so no compositing)
-// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn].
+// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn|_pe][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn|_pe].
 #if defined(DFN_MLP_RES_TU) && (!defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_PTS_TU))
 #error "the resident layers exist in the half-height render kernels"
 #endif
 #if defined(DFN_MLP_DYN_TU) && !defined(DFN_MLP_RES_TU)
 #error "the claimed tiles exist in the kernels with resident layers"
 #endif
-#if defined(DFN_MLP_DYN_TU)
+#if defined(DFN_MLP_PE_TU) && !defined(DFN_MLP_DYN_TU)
+#error "the kept encoding exists in the kernels with claimed tiles"
+#endif
+#if defined(DFN_MLP_PE_TU)
+#define DFN_TU_TAG _pe
+#define DFN_MLP_KARGS MlpDynArgs
+#elif defined(DFN_MLP_DYN_TU)
 #define DFN_TU_TAG _dyn
 #define DFN_MLP_KARGS MlpDynArgs
 #elif defined(DFN_MLP_RES_TU)
@@ -689,6 +696,7 @@ hipError_t DFN_LAUNCH_MLP(bool fine, int prec, const MlpArgs& a, int n_cu, hipSt
 // compositing fused, plain flavour -- the maps flavour stays with launch_mlp_half, the raw route with launch_mlp_fold.
 // launch_mlp_dyn: variant 8's, the same with the claimed-tile word behind the region.  The grid is variant 7's: min(tiles, CUs)
 // workgroups, each starting on tile blockIdx.x; *a.tile_counter is 0 at the start (the caller's memset).
+// launch_mlp_pe: variant 9's, variant 8's arguments, LDS map and grid (this body under DFN_MLP_PE_TU: nerfh_mlp_pe.hip).
 hipError_t DFN_LAUNCH_MLP(bool fine, const DFN_MLP_KARGS& a, int n_cu, hipStream_t stream) {
   void (*kern)(DFN_MLP_KARGS) = fine ? DFN_FINE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true> : DFN_COARSE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true>;
   uint32_t lds = lds_bytes<PM, kMUmb, kMWaves, kMNb>() + resident_bytes<PM>(fine);

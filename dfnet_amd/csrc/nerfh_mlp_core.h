@@ -873,6 +873,12 @@ struct NoTrunkHook {
   template <class A> DFN_DEV void operator()(int, A&) const {}
 };
 // RES_L1 >= 0: layer 1 is LDS-resident at that offset (kernel variant 7's coarse kernel: layer<..., RES>).
+// kEncodingKept: kernel variant 9's translation unit (DFN_MLP_PE_TU), see the skip concat below.
+#ifdef DFN_MLP_PE_TU
+constexpr bool kEncodingKept = true;
+#else
+constexpr bool kEncodingKept = false;
+#endif
 template <class P, int UMB, bool PIPE, bool FAST, int NB, int W = kWidth, class Hook = NoTrunkHook, int RES_L1 = -1>
 DFN_DEV void trunk(Stager& st, char* smem, const float (&x)[lane_pts<P>(NB)][3],
                    typename FragOf<P>::type (&out)[NB][chunks_of<P>(W / 2)], f32x16 (&carry)[NB], Hook hook = Hook()) {
@@ -900,7 +906,12 @@ DFN_DEV void trunk(Stager& st, char* smem, const float (&x)[lane_pts<P>(NB)][3],
   hook(2, a[0]);
   {
     F cat[NB][PC + HC];
-    if constexpr (P::kSlotsPerChunk == 8 && (!PIPE || P::kSplit)) {  // recompute: cheaper than 32 VGPRs live across 4 layers
+    // The skip concat's encoding.  The f16 / split-f16 kernels form it a SECOND time here, from an opaque copy of the coordinates:
+    // in the 32x32 kernels (and the f16 one without the pipelined epilogue) 32 more VGPRs live across layers 2 to 4 cost more than
+    // the evaluation.  Kernel variant 9 (kEncodingKept, the 16x16x32 kernels of nerfh_mlp_pe.hip) keeps layer 1's operand instead:
+    // those kernels have the registers free across layers 2 to 4 and their peak is inside layer 5, where the encoding is an operand
+    // in either form.  The pipelined f16 kernel and exact fp32 have always kept it.
+    if constexpr (P::kSlotsPerChunk == 8 && (!PIPE || P::kSplit) && !(kEncodingKept && P::kM16)) {
       float x2[lane_pts<P>(NB)][3];
 #pragma unroll
       for (int nb = 0; nb < lane_pts<P>(NB); ++nb)

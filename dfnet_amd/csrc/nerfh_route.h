@@ -16,6 +16,7 @@ enum Launcher {       // nerfh_kernels.h:
   kLaunchHalf,        // launch_mlp_half(fine, maps)
   kLaunchResident,    // launch_mlp_res
   kLaunchClaimed,     // launch_mlp_dyn: both tile counters are zeroed in front of a pass in which either kernel takes this route
+  kLaunchKept,        // launch_mlp_pe: claimed tiles as kLaunchClaimed (claims_tiles below)
   kLaunchPoints,      // launch_mlp_pts
   kLaunchPointsFold,  // launch_mlp_pts_fold
   kLaunchPointsHalf,  // launch_mlp_pts_half
@@ -29,13 +30,17 @@ struct Route {
   bool maps;         // fine: the render-maps flavour of the kernel (kMapsRecFloats floats per segment record)
 };
 
-// Netwidth 256 has one kernel per arithmetic: variant 0.  Variants 5 to 8 differ from their base in split-f16 only.
+// the launchers whose kernels claim their tiles: both tile counters are zeroed in front of a pass in which either kernel is one of them
+constexpr bool claims_tiles(Launcher l) { return l == kLaunchClaimed || l == kLaunchKept; }
+
+// Netwidth 256 has one kernel per arithmetic: variant 0.  Variants 5 to 9 differ from their base in split-f16 only.
 constexpr VariantFacts route_facts(int variant, int width) { return kVariantFacts[width == kWidth ? variant : 0]; }
 
 // points: the point queries (dfn_mlp_*_points, called with kDefaultVariant); they have no resident / claimed flavour and run variant 6's
 constexpr Route coarse_route(int variant, int width, int prec, bool points = false) {
   const VariantFacts f = route_facts(variant, width);
   const bool x3 = prec == kPrecF16X3;
+  if (x3 && f.kept && !points) return {kLaunchKept, kResidentVariant, f.base, false, false};
   if (x3 && f.resident && !points) return {f.claimed ? kLaunchClaimed : kLaunchResident, kResidentVariant, f.base, false, false};
   if (x3 && f.half) return {points ? kLaunchPointsHalf : kLaunchHalf, kHalfVariant, f.base, false, false};
   return {points ? kLaunchPoints : kLaunchPlain, f.base, f.base, false, false};
@@ -44,6 +49,7 @@ constexpr Route coarse_route(int variant, int width, int prec, bool points = fal
 constexpr Route fine_route(int variant, int width, int prec, bool fused, bool want_maps, bool points = false) {
   const VariantFacts f = route_facts(variant, width);
   const bool x3 = prec == kPrecF16X3, maps = fused && want_maps;
+  if (x3 && f.kept && fused && !want_maps) return {kLaunchKept, kResidentVariant, f.base, true, false};
   if (x3 && f.resident && fused && !want_maps) return {f.claimed ? kLaunchClaimed : kLaunchResident, kResidentVariant, f.base, true, false};
   if (x3 && f.half && fused) return {kLaunchHalf, want_maps ? kNetHalfMaps : kHalfVariant, f.base, true, want_maps};
   if (x3 && f.fold) return {points ? kLaunchPointsFold : kLaunchFold, kFoldVariant, f.base, true, maps};
@@ -72,7 +78,7 @@ constexpr bool plain_as(int v, int w, int p, int b) {
          is(fine_route(v, w, p, true, true), kLaunchMaps, b, b, false, true);
 }
 constexpr bool plain_all(int v, int w, int b) { return plain_as(v, w, H, b) && plain_as(v, w, F, b) && plain_as(v, w, X, b); }
-// the raw route of variants 5 to 8 in split-f16: variant 5's fine kernel on net[1][F16X3][5], with or without maps wanted
+// the raw route of variants 5 to 9 in split-f16: variant 5's fine kernel on net[1][F16X3][5], with or without maps wanted
 constexpr bool raw_is_fold(int v) {
   return is(fine_route(v, W, X, false, false), kLaunchFold, 5, 4, true) && is(fine_route(v, W, X, false, true), kLaunchFold, 5, 4, true);
 }
@@ -103,6 +109,14 @@ static_assert(plain_as(8, W, H, 4) && plain_as(8, W, F, 4) && plain_all(8, W2, 0
 static_assert(is(coarse_route(8, W, X), kLaunchClaimed, 7, 4), "variant 8 coarse");
 static_assert(raw_is_fold(8) && is(fine_route(8, W, X, true, false), kLaunchClaimed, 7, 4, true) &&
               is(fine_route(8, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 8 fine");
+// variant 9: variant 8 with launch_mlp_pe where variant 8 has launch_mlp_dyn, on variant 7's networks; everything else variant 8's
+static_assert(plain_as(9, W, H, 4) && plain_as(9, W, F, 4) && plain_all(9, W2, 0), "variant 9 outside split-f16");
+static_assert(is(coarse_route(9, W, X), kLaunchKept, 7, 4), "variant 9 coarse");
+static_assert(raw_is_fold(9) && is(fine_route(9, W, X, true, false), kLaunchKept, 7, 4, true) &&
+              is(fine_route(9, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 9 fine");
+static_assert(is(coarse_route(9, W, X, true), kLaunchPointsHalf, 6, 4) && is(fine_route(9, W, X, false, false, true), kLaunchPointsFold, 5, 4, true),
+              "variant 9 points");
+static_assert(claims_tiles(kLaunchClaimed) && claims_tiles(kLaunchKept) && !claims_tiles(kLaunchResident), "who claims tiles");
 // the coarse pass of a split-f16 render under DFN_RENDER_COARSE_F16 is the f16 route: variant 0's kernel on net[0][F16][4]
 static_assert(is(coarse_route(kSelectedByDefault, W, H), kLaunchPlain, 4, 4), "f16 coarse pass");
 // point queries: the default variant's kernels -- split-f16 at netwidth 128 variant 6's coarse and variant 5's fine (raw) kernel
@@ -112,7 +126,8 @@ static_assert(is(coarse_route(7, W, H, true), kLaunchPoints, 4, 4) && is(fine_ro
               is(coarse_route(7, W2, X, true), kLaunchPoints, 0, 0) && is(fine_route(7, W2, X, false, false, true), kLaunchPoints, 0, 0),
               "points outside split-f16 at netwidth 128");
 // fused compositing: whole segments, no raw, netwidth 128, and not the 3-block f16 kernel (base variant 2)
-static_assert(fused_compositing(8, W, X, 128, false) && fused_compositing(0, W, H, 128, false) && fused_compositing(2, W, X, 96, false), "fused");
+static_assert(fused_compositing(9, W, X, 128, false) && fused_compositing(8, W, X, 128, false) && fused_compositing(0, W, H, 128, false) &&
+              fused_compositing(2, W, X, 96, false), "fused");
 static_assert(!fused_compositing(8, W, X, 128, true) && !fused_compositing(8, W, X, 40, false) && !fused_compositing(0, W, H, 96, false) &&
               !fused_compositing(2, W, H, 128, false) && !fused_compositing(0, W2, X, 128, false), "not fused");
 }  // namespace route_spec
