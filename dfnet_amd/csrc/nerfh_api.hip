@@ -839,14 +839,16 @@ static int check_grad_prec(int prec, const char* fn) {
 // every kernel launch that carries the guard runs on a committed handle.
 static int* range_flag_of(dfn_nerfh_t h) { return h->range_flag; }
 
-// Kernel variant: DFN_MLP_VARIANT=0..9 (A/B aid; nerfh_layout.h: kVariantFacts, kSelectedByDefault), read once.  What it means for a call
+// Kernel variant: DFN_MLP_VARIANT=0..10 (A/B aid; nerfh_layout.h: kVariantFacts, kSelectedByDefault), read once.  What it means for a call
 // is nerfh_route.h; the gradient paths (render backward, dfn_mlp_fine_saving) run the base variant's / variant 0's plain kernels on
 // the plain table, which their backward kernels read.
 static int mlp_variant_128() {
   static int v = -1;
   if (v < 0) {
     const char* e = getenv("DFN_MLP_VARIANT");
-    v = (e && e[0] >= '0' && e[0] <= '0' + kLastVariant) ? e[0] - '0' : kSelectedByDefault;
+    char* end = nullptr;
+    const long n = e ? strtol(e, &end, 10) : -1;   // whole decimal numbers only; anything else selects the default
+    v = (e && end != e && *end == '\0' && n >= 0 && n <= kLastVariant) ? int(n) : kSelectedByDefault;
   }
   return v;
 }
@@ -871,6 +873,7 @@ static hipError_t launch_route(dfn_nerfh_t h, bool fine, int prec, const Route& 
     case kLaunchResident: return launch_mlp_res(fine, d, cus, s);
     case kLaunchClaimed: return launch_mlp_dyn(fine, d, cus, s);
     case kLaunchKept: return launch_mlp_pe(fine, d, cus, s);
+    case kLaunchHoisted: return launch_mlp_hoist(fine, d, cus, s);
     case kLaunchPoints: return launch_mlp_pts(fine, prec, a, cus, s, width);
     case kLaunchPointsFold: return launch_mlp_pts_fold(a, cus, s);
     case kLaunchPointsHalf: return launch_mlp_pts_half(a, cus, s);
@@ -1102,7 +1105,9 @@ int render_core(dfn_nerfh_t h, int prec, const float* o, const float* d, const f
     }
     {
       ScopedTimer t(DFN_PROF_RAY_BIAS, s);
-      CHECK_HIP(launch_ray_bias(rf.fold_table ? h->rb_fold : h->rb, cv, ch, hist_rows, n, w.bias, s), "render: ray_bias");
+      // w.bias is written for this pass's fine launch and read by nothing else: on a seed_scaled route it holds in_scale x the seeds
+      CHECK_HIP(launch_ray_bias(rf.fold_table ? h->rb_fold : h->rb, cv, ch, hist_rows, n, w.bias, s, rf.seed_scaled ? nf.in_scale : 1.f),
+                "render: ray_bias");
     }
     {
       MlpArgs a{nf.blob, nf.tab, nf.n_units, co, cd, w.z, w.bias, raw, fused ? w.partial : nullptr, (long long)n, Nf, 0.f, 0.f, g_timing_buf, nf.in_scale};

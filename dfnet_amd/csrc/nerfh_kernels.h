@@ -60,6 +60,11 @@ hipError_t launch_mlp_dyn(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t 
 // Kernel variant 9 (nerfh_mlp_pe.hip): variant 8's two kernels with the positional encoding kept for the skip concat instead of
 // formed twice per tile.  Variant 8's arguments, networks, resident blob and counter.
 hipError_t launch_mlp_pe(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
+// Kernel variant 10 (nerfh_mlp_hoist.hip): variant 9's plain fused fine kernel on a per-ray table that already holds in_scale x the
+// seeds (launch_ray_bias with scale = a.in_scale): its RAYBIAS layers take the loaded seeds as they are, and its uniform state is
+// formed at the use instead of parked in VGPR lanes.  Variant 9's arguments otherwise.
+// fine = false is refused: the coarse kernel has no per-ray seeds and stays launch_mlp_pe's.
+hipError_t launch_mlp_hoist(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
 
 // The points flavour (nerfh_mlp_pts*.hip): a.rays_o is pts [n_rays, n_samples, 3] (n_rays = query rows), a.rays_d, a.z and a.partial
 // are unused (a.partial must be null: the raw route only), a.ray_bias has one row per query row.  launch_mlp_pts: f16 / exact fp32 at
@@ -88,8 +93,10 @@ struct RayBiasWeights {       // device pointers, fp32
   int hist_bin, dim_a, dim_t, n_vocab;
   int nout;                   // outputs per table = netwidth / 2 (w_dir, w_tr are [*][nout]; the table row is 2 * nout floats)
 };
+// scale: every table entry is stored multiplied by it (1 = the seeds themselves, the kernel every route but variant 10's fused fine
+// one has always run; otherwise the fine network's in_scale, a power of two: launch_mlp_hoist)
 hipError_t launch_ray_bias(const RayBiasWeights& w, const float* viewdirs, const float* hist,
-                           size_t hist_rows, size_t n_rays, float* table, hipStream_t stream);
+                           size_t hist_rows, size_t n_rays, float* table, hipStream_t stream, float scale = 1.f);
 
 hipError_t launch_coarse_weights(const float* sigma, const float* z, size_t n, int N, float* weights,
                                  hipStream_t stream);

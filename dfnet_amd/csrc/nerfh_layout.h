@@ -137,7 +137,7 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //   variant 1: 4 waves per workgroup, 2 workgroups per CU, a unit = 2 M-blocks (f16) / one M-block (f32)
 //   variant 2: 4 waves per workgroup x 3 point blocks, 1 workgroup per CU (1 wave per SIMD, 512 VGPRs), unit as variant 0
 //   variant 3: variant 0's geometry without the pipelined epilogue (A/B reference)
-// 4 to 9 exist in split-f16 at netwidth 128 only and each is the one before it with one thing more (kVariantFacts); every other
+// 4 to 10 exist in split-f16 at netwidth 128 only and each is the one before it with one thing more (kVariantFacts); every other
 // arithmetic mode, width and gradient path under them runs the `base` variant's kernels on its networks, and which kernel, network and
 // per-ray table a call runs is nerfh_route.h:
 //   variant 4: variant 0 on 16x16x32 MFMAs (PrecX3M16)
@@ -158,14 +158,23 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //              2 to 4, which the 16x16x32 kernels have free, against 231 vector instructions per tile and wave, 32 of them quarter-rate
 //              v_sin / v_cos.  The kept operand is the value the second evaluation gives: variant 8's outputs bit for bit, on variant
 //              7's packed networks, variant 8's per-ray table and tile counters
+//   variant 10: variant 9 with per-tile work the result does not need HOISTED out of the fused fine kernel's tile loop
+//              (nerfh_mlp_hoist.hip): ray_bias_kernel writes the table of that route multiplied by the fine network's in_scale, once
+//              per pass, instead of layer() multiplying the loaded seeds of the two RAYBIAS layers on every tile; and uniform values
+//              (the weight DMA's per-wave piece, prefetch slot addresses, argument pointers) are formed where they are used instead of
+//              parked in VGPR lanes and read back by v_readlane_b32 (79 -> 39 parked SGPRs, 231 -> 62 lane reads per tile).  The same
+//              values by the same arithmetic: variant 9's outputs bit for bit, on its networks, resident blob and counters.  The
+//              coarse kernel has no RAYBIAS layer and parks nothing: variant 9's runs
 constexpr int kVariants = 8;   // packed networks per (coarse | fine, arithmetic): dfn_nerfh_s::net
 constexpr int kFoldVariant = 5;
 constexpr int kHalfVariant = 6;
 constexpr int kResidentVariant = 7;
 constexpr int kDynVariant = 8;
 constexpr int kKeptVariant = 9;
-constexpr int kLastVariant = kKeptVariant;   // DFN_MLP_VARIANT = 0 .. kLastVariant
-struct VariantFacts { int base; bool fold, half, resident, claimed, kept; };   // kept: the encoding, for the skip concat
+constexpr int kHoistVariant = 10;
+constexpr int kLastVariant = kHoistVariant;   // DFN_MLP_VARIANT = 0 .. kLastVariant
+// kept: the encoding, for the skip concat; hoisted: the fused fine kernel is nerfh_mlp_hoist.hip's and its per-ray table holds in_scale x the seeds
+struct VariantFacts { int base; bool fold, half, resident, claimed, kept, hoisted; };
 constexpr VariantFacts kVariantFacts[kLastVariant + 1] = {
     {0, false, false, false, false}, {1, false, false, false, false}, {2, false, false, false, false}, {3, false, false, false, false},
     {4, false, false, false, false},
@@ -174,9 +183,10 @@ constexpr VariantFacts kVariantFacts[kLastVariant + 1] = {
     {4, true, true, true, false},     // kResidentVariant
     {4, true, true, true, true},      // kDynVariant
     {4, true, true, true, true, true},   // kKeptVariant
+    {4, true, true, true, true, true, true},   // kHoistVariant: variant 9's row (its plain kernels are variant 4's too) and the new fact
 };
 // What a process runs without DFN_MLP_VARIANT; the variant whose kernels the point queries run whatever it says
-constexpr int kSelectedByDefault = kKeptVariant;
+constexpr int kSelectedByDefault = kHoistVariant;
 constexpr int kDefaultVariant = kResidentVariant;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));

@@ -37,7 +37,10 @@ namespace dfn {
 //   DFN_MLP_PE_TU     variant 9, on DYN: the positional encoding kept for the skip concat (trunk(): kEncodingKept), MlpDynArgs
 //   DFN_MLP_PTS_TU    the points flavour, on none, FOLD or HALF: the inputs are loaded from pts [n_rows, n_samples, 3] (MlpArgs::rays_o)
 //                     instead of being formed as o + d z; the raw route only (no depths, so no compositing)
-// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn|_pe][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn|_pe].
+//   DFN_MLP_HOIST_TU  variant 10, on PE: the fine kernel's per-ray seeds are stored at the accumulators' scale (layer(): RAYBIAS takes
+//                     them as loaded) and uniform values are formed at their use (wave_here / args_here below, stage_issue_at),
+//                     MlpDynArgs; the unit has no coarse kernel (variant 9's runs)
+// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn|_pe|_hoist][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn|_pe|_hoist].
 #if defined(DFN_MLP_RES_TU) && (!defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_PTS_TU))
 #error "the resident layers exist in the half-height render kernels"
 #endif
@@ -47,7 +50,13 @@ namespace dfn {
 #if defined(DFN_MLP_PE_TU) && !defined(DFN_MLP_DYN_TU)
 #error "the kept encoding exists in the kernels with claimed tiles"
 #endif
-#if defined(DFN_MLP_PE_TU)
+#if defined(DFN_MLP_HOIST_TU) && !defined(DFN_MLP_PE_TU)
+#error "the hoisted per-tile work is taken out of the kernels with the kept encoding"
+#endif
+#if defined(DFN_MLP_HOIST_TU)
+#define DFN_TU_TAG _hoist
+#define DFN_MLP_KARGS MlpDynArgs
+#elif defined(DFN_MLP_PE_TU)
 #define DFN_TU_TAG _pe
 #define DFN_MLP_KARGS MlpDynArgs
 #elif defined(DFN_MLP_DYN_TU)
@@ -105,6 +114,29 @@ constexpr bool kResident = false;
 #define DFN_NEXT_TILE (static_cast<long long>(st.next))
 #else
 #define DFN_NEXT_TILE (tile + gridDim.x)
+#endif
+
+// Kernel variant 10 (DFN_MLP_HOIST_TU): uniform values the tile loop needs once per tile are formed where they are used.  As loop
+// invariants LLVM hoists them to the prologue, where the scalar file cannot hold them all: they are parked in VGPR lanes and every use
+// costs a v_readlane_b32 on the vector pipe (79 parked SGPRs and 231 lane reads per tile in variant 9's fine kernel).  wave_here: the
+// wave index behind an opaque copy, so that what is derived from it (LDS slot addresses) is scalar arithmetic at the use.  args_here:
+// the kernel arguments read from the kernarg segment at the use (one s_load) instead of held, or parked, for the whole kernel.
+#ifdef DFN_MLP_HOIST_TU
+DFN_DEV int wave_here(const Stager& st) {
+  int w = st.wave;
+  asm volatile("" : "+s"(w));
+  return w;
+}
+typedef const DFN_MLP_KARGS __attribute__((address_space(4))) const_kargs;
+DFN_DEV const_kargs* args_here() {
+  uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr());   // the argument struct is the kernel's only parameter: offset 0
+  asm volatile("" : "+s"(p));
+  return reinterpret_cast<const_kargs*>(p);
+}
+#define DFN_ARGS_HERE(a) (*args_here())
+#else
+DFN_DEV int wave_here(const Stager& st) { return st.wave; }
+#define DFN_ARGS_HERE(a) (a)
 #endif
 
 // Head activations per arithmetic mode: f16 = hardware transcendentals (1e-6), split-f16 = the fp32-grade hardware forms
@@ -331,7 +363,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   st.claim = 0; st.grid = gridDim.x; st.next = 0; st.n_tiles = uint32_t(n_tiles); st.more = false;
   st.claim_lds = lds_bytes<P, UMB, WAVES, NB, W>() + resident_bytes<P>(true);
   for (; tile < n_tiles; tile = st.next) {
-    if (st.wave == 0 && st.lane == 0) st.claim = claim_tile(a.tile_counter);
+    if (st.wave == 0 && st.lane == 0) st.claim = claim_tile(DFN_ARGS_HERE(a).tile_counter);
     st.claiming = true;
 #else
   for (; tile < n_tiles; tile += gridDim.x) {
@@ -356,7 +388,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       for (int nb = 0; nb < LP; ++nb) {
         uint32_t r = ray_cur[nb];
         asm volatile("" : "+v"(r));
-        rb[nb] = a.ray_bias + (size_t)r * ray_bias_floats(W) + half_table * (ray_bias_floats(W) / 2);
+        rb[nb] = DFN_ARGS_HERE(a).ray_bias + (size_t)r * ray_bias_floats(W) + half_table * (ray_bias_floats(W) / 2);
       }
     };
     const float* const norb[LP] = {};
@@ -437,8 +469,10 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
         // Prefetch the next tile's inputs by LDS-DMA (no destination registers).  Issued AFTER this unit's mid_sync so
         // that nothing younger than a weight DMA is ever waited for before the tile's end:
         // lane l of round r fetches z, o, d and the next sample's z of the wave's point 64 r + l into this wave's LDS slot.
-        const uint32_t base = uint32_t(DFN_NEXT_TILE) * uint32_t(PPT) + st.wave * (NB * 32);
-        char* slot = smem + ring_slots<P, W>() * USTRIDE + st.wave * (PF_ROUNDS * 8 * 256);
+        const int wv = wave_here(st);
+        const auto& pa = DFN_ARGS_HERE(a);   // rays_o, rays_d, z
+        const uint32_t base = uint32_t(DFN_NEXT_TILE) * uint32_t(PPT) + wv * (NB * 32);
+        char* slot = smem + ring_slots<P, W>() * USTRIDE + wv * (PF_ROUNDS * 8 * 256);
 #pragma unroll
         for (int r = 0; r < PF_ROUNDS; ++r) {
           const uint32_t ptn = base + r * 64 + st.lane;
@@ -446,15 +480,15 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #ifdef DFN_MLP_PTS_TU
           // points flavour: the three coordinates of the wave's point 64 r + l (dwords 0..2 of the round's eight)
 #pragma unroll
-          for (int c = 0; c < 3; ++c) lds_dma_b32(a.rays_o + size_t(q) * 3 + c, slot + (r * 8 + c) * 256);
+          for (int c = 0; c < 3; ++c) lds_dma_b32(pa.rays_o + size_t(q) * 3 + c, slot + (r * 8 + c) * 256);
 #else
           const uint32_t ray = q / uint32_t(a.n_samples);
-          lds_dma_b32(a.z + q, slot + (r * 8) * 256);
-          lds_dma_b32(a.z + (q + 1 < npts ? q + 1 : q), slot + (r * 8 + 7) * 256);
+          lds_dma_b32(pa.z + q, slot + (r * 8) * 256);
+          lds_dma_b32(pa.z + (q + 1 < npts ? q + 1 : q), slot + (r * 8 + 7) * 256);
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
-            lds_dma_b32(a.rays_o + ray * 3 + c, slot + (r * 8 + 1 + c) * 256);
-            lds_dma_b32(a.rays_d + ray * 3 + c, slot + (r * 8 + 4 + c) * 256);
+            lds_dma_b32(pa.rays_o + ray * 3 + c, slot + (r * 8 + 1 + c) * 256);
+            lds_dma_b32(pa.rays_d + ray * 3 + c, slot + (r * 8 + 4 + c) * 256);
           }
 #endif
         }
@@ -501,7 +535,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
         pt_own[nb] = pt_cur[nb]; ray_own[nb] = ray_cur[nb]; z_own[nb] = zin[nb]; zn_own[nb] = znext[nb];
       }
     }
-    if (a.partial) {
+    if (DFN_ARGS_HERE(a).partial) {
       // Fused compositing (n_samples % (32 NB) == 0): this wave holds 32 NB consecutive samples of ONE ray, sample
       // 32 nb + p on lane p of half 0.  Transmittance factorises over segments, so the wave composites its
       // segment locally (products P and sums relative to the segment start) and a tiny combine pass chains
@@ -557,7 +591,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       }
       if (st.lane == 0 && pt_own[0] < npts) {
         constexpr int REC = MAPS ? kMapsRecFloats : 12;
-        f32x4* dst = reinterpret_cast<f32x4*>(a.partial + (size_t)(pt_own[0] / uint32_t(NB * 32)) * REC);   // one segment per wave
+        f32x4* dst = reinterpret_cast<f32x4*>(DFN_ARGS_HERE(a).partial + (size_t)(pt_own[0] / uint32_t(NB * 32)) * REC);   // one segment per wave
         dst[0] = f32x4{s_rgb[0], s_rgb[1], s_rgb[2], s_acc};
         dst[1] = f32x4{s_dso, s_dj, s_beta, Pj};
         if constexpr (MAPS) {
@@ -697,8 +731,14 @@ hipError_t DFN_LAUNCH_MLP(bool fine, int prec, const MlpArgs& a, int n_cu, hipSt
 // launch_mlp_dyn: variant 8's, the same with the claimed-tile word behind the region.  The grid is variant 7's: min(tiles, CUs)
 // workgroups, each starting on tile blockIdx.x; *a.tile_counter is 0 at the start (the caller's memset).
 // launch_mlp_pe: variant 9's, variant 8's arguments, LDS map and grid (this body under DFN_MLP_PE_TU: nerfh_mlp_pe.hip).
+// launch_mlp_hoist: variant 10's fine kernel, variant 9's arguments, LDS map and grid; a.ray_bias holds in_scale x the seeds
+// (nerfh_mlp_hoist.hip); no coarse kernel.
 hipError_t DFN_LAUNCH_MLP(bool fine, const DFN_MLP_KARGS& a, int n_cu, hipStream_t stream) {
+#ifdef DFN_MLP_HOIST_TU
+  void (*kern)(DFN_MLP_KARGS) = fine ? DFN_FINE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true> : nullptr;
+#else
   void (*kern)(DFN_MLP_KARGS) = fine ? DFN_FINE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true> : DFN_COARSE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true>;
+#endif
   uint32_t lds = lds_bytes<PM, kMUmb, kMWaves, kMNb>() + resident_bytes<PM>(fine);
   if (a.masks || (fine && !a.partial)) kern = nullptr;
   if (!a.res_blob || a.res_bytes != resident_bytes<PM>(fine)) kern = nullptr;   // the kernels copy exactly this many bytes

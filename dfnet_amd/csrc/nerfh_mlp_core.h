@@ -126,8 +126,19 @@ DFN_DEV uint32_t claim_tile(uint32_t* counter) {
 
 DFN_DEV void stage_issue_at(const Stager& st, char* smem, uint32_t off, uint32_t size, uint32_t lds_off) {
   const char* src = st.blob + off + st.lane * 16;
+#ifdef DFN_MLP_HOIST_TU
+  // kernel variant 10: whether this wave issues DMA and where its first piece lies are formed HERE from the wave index.  As loop
+  // invariants of the tile loop the condition (a 64-bit lane mask) and the 64-bit offset (wave * kPiece, 0) were hoisted to the
+  // prologue, parked in VGPR lanes and read back by v_readlane_b32 pairs in front of every unit's DMA: 88 of the 223 reads of parked
+  // SGPRs per tile in variant 9's fine kernel.  Behind the opaque copy they are one scalar compare and one scalar shift per unit.
+  uint32_t w = st.wave;
+  asm volatile("" : "+s"(w));
+  if (int(w) >= st.dma_waves) return;
+  for (uint32_t p = w * kPiece; p < size; p += st.dma_waves * kPiece) lds_dma_b128(src + p, smem + lds_off + p);
+#else
   if (st.wave >= st.dma_waves) return;
   for (uint32_t p = st.wave * kPiece; p < size; p += st.dma_waves * kPiece) lds_dma_b128(src + p, smem + lds_off + p);
+#endif
 }
 // The unit table is read through the CONSTANT address space so that the loads are scalar (s_load, lgkmcnt): as
 // vector loads they would sit in the vmcnt queue behind the DMA and every wait for them would wait for the DMA too.
@@ -539,7 +550,9 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
       for (int nb = 0; nb < NB; ++nb) {
         if constexpr (P::kM16) rb[mb][nb] = load_raybias_m16(raybias, mb, g16);
         else rb[mb][nb] = load16(raybias[nb] + (mb * 2 + h) * 16);
+#ifndef DFN_MLP_HOIST_TU   // kernel variant 10: the table holds in_scale x the seeds (ray_bias_kernel<true>)
         if constexpr (P::kSplit) rb[mb][nb] *= st.in_scale;   // accumulators carry in_scale x the true value
+#endif
       }
   }
   f32x16 pend[PIPE ? NB : 1];  // accumulators of M-block mb-1 while M-block mb runs
@@ -581,7 +594,9 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
           for (int nb = 0; nb < NB; ++nb) {
             if constexpr (P::kM16) acc[nb] = RB_ALL ? rb[RB_ALL ? mb : 0][nb] : load_raybias_m16(raybias, mb, g16);
             else acc[nb] = RB_ALL ? rb[RB_ALL ? mb : 0][nb] : load16(raybias[nb] + (mb * 2 + h) * 16);
+#ifndef DFN_MLP_HOIST_TU
             if constexpr (P::kSplit && !RB_ALL) acc[nb] *= st.in_scale;
+#endif
           }
         }
 #pragma unroll

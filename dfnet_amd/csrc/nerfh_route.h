@@ -17,6 +17,7 @@ enum Launcher {       // nerfh_kernels.h:
   kLaunchResident,    // launch_mlp_res
   kLaunchClaimed,     // launch_mlp_dyn: both tile counters are zeroed in front of a pass in which either kernel takes this route
   kLaunchKept,        // launch_mlp_pe: claimed tiles as kLaunchClaimed (claims_tiles below)
+  kLaunchHoisted,      // launch_mlp_hoist: kLaunchKept's fine kernel on the per-ray table written at the accumulators' scale (Route::seed_scaled)
   kLaunchPoints,      // launch_mlp_pts
   kLaunchPointsFold,  // launch_mlp_pts_fold
   kLaunchPointsHalf,  // launch_mlp_pts_half
@@ -28,12 +29,13 @@ struct Route {
   int variant;       // what launch_mlp / launch_mlp_maps take as `variant` (the other launchers have one geometry)
   bool fold_table;   // fine: the per-ray table is written from rb_fold (the seeds carry W[:, :128] . b_final) instead of rb
   bool maps;         // fine: the render-maps flavour of the kernel (kMapsRecFloats floats per segment record)
+  bool seed_scaled;  // fine: the per-ray table of this launch holds in_scale x the seeds (launch_ray_bias's scale); no other kernel reads it
 };
 
 // the launchers whose kernels claim their tiles: both tile counters are zeroed in front of a pass in which either kernel is one of them
-constexpr bool claims_tiles(Launcher l) { return l == kLaunchClaimed || l == kLaunchKept; }
+constexpr bool claims_tiles(Launcher l) { return l == kLaunchClaimed || l == kLaunchKept || l == kLaunchHoisted; }
 
-// Netwidth 256 has one kernel per arithmetic: variant 0.  Variants 5 to 9 differ from their base in split-f16 only.
+// Netwidth 256 has one kernel per arithmetic: variant 0.  Variants 5 to 10 differ from their base in split-f16 only.
 constexpr VariantFacts route_facts(int variant, int width) { return kVariantFacts[width == kWidth ? variant : 0]; }
 
 // points: the point queries (dfn_mlp_*_points, called with kDefaultVariant); they have no resident / claimed flavour and run variant 6's
@@ -49,6 +51,7 @@ constexpr Route coarse_route(int variant, int width, int prec, bool points = fal
 constexpr Route fine_route(int variant, int width, int prec, bool fused, bool want_maps, bool points = false) {
   const VariantFacts f = route_facts(variant, width);
   const bool x3 = prec == kPrecF16X3, maps = fused && want_maps;
+  if (x3 && f.hoisted && fused && !want_maps) return {kLaunchHoisted, kResidentVariant, f.base, true, false, true};
   if (x3 && f.kept && fused && !want_maps) return {kLaunchKept, kResidentVariant, f.base, true, false};
   if (x3 && f.resident && fused && !want_maps) return {f.claimed ? kLaunchClaimed : kLaunchResident, kResidentVariant, f.base, true, false};
   if (x3 && f.half && fused) return {kLaunchHalf, want_maps ? kNetHalfMaps : kHalfVariant, f.base, true, want_maps};
@@ -67,8 +70,9 @@ constexpr bool fused_compositing(int variant, int width, int prec, int Nf, bool 
 // ---- the routes, written out -------------------------------------------------------------------------------------------------
 namespace route_spec {
 constexpr int W = kWidth, W2 = kMaxWidth, H = kPrecF16, F = kPrecF32, X = kPrecF16X3, HM = kNetHalfMaps;
-constexpr bool is(const Route& r, Launcher l, int net, int variant, bool fold_table = false, bool maps = false) {
-  return r.launcher == l && r.net == net && r.variant == variant && r.fold_table == fold_table && r.maps == maps;
+constexpr bool is(const Route& r, Launcher l, int net, int variant, bool fold_table = false, bool maps = false, bool seed_scaled = false) {
+  return r.launcher == l && r.net == net && r.variant == variant && r.fold_table == fold_table && r.maps == maps &&
+         r.seed_scaled == seed_scaled;
 }
 // (v, w, p) runs variant b's plain kernels on net[*][p][b] and the plain table everywhere: coarse; fine raw (maps then come from the
 // separate compositor) and fused, where the maps flavour is launch_mlp_maps
@@ -78,7 +82,7 @@ constexpr bool plain_as(int v, int w, int p, int b) {
          is(fine_route(v, w, p, true, true), kLaunchMaps, b, b, false, true);
 }
 constexpr bool plain_all(int v, int w, int b) { return plain_as(v, w, H, b) && plain_as(v, w, F, b) && plain_as(v, w, X, b); }
-// the raw route of variants 5 to 9 in split-f16: variant 5's fine kernel on net[1][F16X3][5], with or without maps wanted
+// the raw route of variants 5 to 10 in split-f16: variant 5's fine kernel on net[1][F16X3][5], with or without maps wanted
 constexpr bool raw_is_fold(int v) {
   return is(fine_route(v, W, X, false, false), kLaunchFold, 5, 4, true) && is(fine_route(v, W, X, false, true), kLaunchFold, 5, 4, true);
 }
@@ -116,7 +120,16 @@ static_assert(raw_is_fold(9) && is(fine_route(9, W, X, true, false), kLaunchKept
               is(fine_route(9, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 9 fine");
 static_assert(is(coarse_route(9, W, X, true), kLaunchPointsHalf, 6, 4) && is(fine_route(9, W, X, false, false, true), kLaunchPointsFold, 5, 4, true),
               "variant 9 points");
-static_assert(claims_tiles(kLaunchClaimed) && claims_tiles(kLaunchKept) && !claims_tiles(kLaunchResident), "who claims tiles");
+// variant 10: variant 9 with launch_mlp_hoist and the scaled table in the plain fused fine kernel, and there alone: the coarse kernel is
+// variant 9's, and the maps flavour, the raw route and the point queries read the unscaled table as under variant 9
+static_assert(plain_as(10, W, H, 4) && plain_as(10, W, F, 4) && plain_all(10, W2, 0), "variant 10 outside split-f16");
+static_assert(is(coarse_route(10, W, X), kLaunchKept, 7, 4), "variant 10 coarse");
+static_assert(raw_is_fold(10) && is(fine_route(10, W, X, true, false), kLaunchHoisted, 7, 4, true, false, true) &&
+              is(fine_route(10, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 10 fine");
+static_assert(is(coarse_route(10, W, X, true), kLaunchPointsHalf, 6, 4) && is(fine_route(10, W, X, false, false, true), kLaunchPointsFold, 5, 4, true),
+              "variant 10 points");
+static_assert(claims_tiles(kLaunchClaimed) && claims_tiles(kLaunchKept) && claims_tiles(kLaunchHoisted) && !claims_tiles(kLaunchResident),
+              "who claims tiles");
 // the coarse pass of a split-f16 render under DFN_RENDER_COARSE_F16 is the f16 route: variant 0's kernel on net[0][F16][4]
 static_assert(is(coarse_route(kSelectedByDefault, W, H), kLaunchPlain, 4, 4), "f16 coarse pass");
 // point queries: the default variant's kernels -- split-f16 at netwidth 128 variant 6's coarse and variant 5's fine (raw) kernel
@@ -126,7 +139,7 @@ static_assert(is(coarse_route(7, W, H, true), kLaunchPoints, 4, 4) && is(fine_ro
               is(coarse_route(7, W2, X, true), kLaunchPoints, 0, 0) && is(fine_route(7, W2, X, false, false, true), kLaunchPoints, 0, 0),
               "points outside split-f16 at netwidth 128");
 // fused compositing: whole segments, no raw, netwidth 128, and not the 3-block f16 kernel (base variant 2)
-static_assert(fused_compositing(9, W, X, 128, false) && fused_compositing(8, W, X, 128, false) && fused_compositing(0, W, H, 128, false) &&
+static_assert(fused_compositing(10, W, X, 128, false) && fused_compositing(9, W, X, 128, false) && fused_compositing(8, W, X, 128, false) && fused_compositing(0, W, H, 128, false) &&
               fused_compositing(2, W, X, 96, false), "fused");
 static_assert(!fused_compositing(8, W, X, 128, true) && !fused_compositing(8, W, X, 40, false) && !fused_compositing(0, W, H, 96, false) &&
               !fused_compositing(2, W, H, 128, false) && !fused_compositing(0, W2, X, 128, false), "not fused");

@@ -147,9 +147,13 @@ hipError_t launch_posenc(const float* x, size_t n, int L, int mode, float* out, 
 // table[ray][0] = b_dir + W_dir[:, W:] . [pe_dir(viewdir) (27), a (hist_bin*dim_a)]     (nout = netwidth / 2 outputs)
 // table[ray][1] = b_tr  + W_tr [:, W:] . t (hist_bin*dim_t)
 // stored in C-fragment order [tbl][mb][h][r] so the fine kernel's accumulators load it directly.
+// SCALED: every entry is stored multiplied by `scale` (kernel variant 10: the split-f16 accumulators carry in_scale x the value, and
+// the product by that power of two is formed here once per ray instead of on every tile that loads the entry).  An instantiation of
+// its own: without it `scale` is not read and the code is the kernel's of before.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void ray_bias_kernel(RayBiasWeights w, const float* __restrict__ viewdirs,
                                                        const float* __restrict__ hist, size_t hist_rows,
-                                                       size_t n_rays, float* __restrict__ table) {
+                                                       size_t n_rays, float* __restrict__ table, float scale) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int na = w.hist_bin * w.dim_a, nt = w.hist_bin * w.dim_t;
   const int kd = kChDir + na;  // rows of w_dir
@@ -215,7 +219,7 @@ __global__ __launch_bounds__(256) void ray_bias_kernel(RayBiasWeights w, const f
       auto put = [&](int tbl, int f, float v) {
         const int mb = f >> 5, row = f & 31;
         const int h = (row >> 2) & 1, r = (row & 3) + 4 * (row >> 3);
-        table[ray * size_t(2 * NO) + ((tbl * nmb + mb) * 2 + h) * 16 + r] = v;
+        table[ray * size_t(2 * NO) + ((tbl * nmb + mb) * 2 + h) * 16 + r] = SCALED ? v * scale : v;
       };
       if (shared) {
         for (int f = o; f < NO; f += 64) {
@@ -243,19 +247,21 @@ __global__ __launch_bounds__(256) void ray_bias_kernel(RayBiasWeights w, const f
 }
 
 hipError_t launch_ray_bias(const RayBiasWeights& w, const float* viewdirs, const float* hist,
-                           size_t hist_rows, size_t n_rays, float* table, hipStream_t stream) {
+                           size_t hist_rows, size_t n_rays, float* table, hipStream_t stream, float scale) {
   if (!n_rays) return hipSuccess;
+  const bool scaled = scale != 1.f;
+  void (*kern)(RayBiasWeights, const float*, const float*, size_t, size_t, float*, float) = scaled ? ray_bias_kernel<true> : ray_bias_kernel<false>;
   const int na = w.hist_bin * w.dim_a, nt = w.hist_bin * w.dim_t;
   const size_t lds = size_t((kChDir + na) * w.nout + nt * w.nout + 4 * (kChDir + na + nt) + 2 * w.nout) * 4;
   const size_t rpb = hist_rows == 1 ? 4 : 2;
-  static bool attr_done = false;
-  if (lds > 64 * 1024 && !attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ray_bias_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+  static bool attr_done[2] = {false, false};
+  if (lds > 64 * 1024 && !attr_done[scaled]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
     if (e != hipSuccess) return e;
-    attr_done = true;
+    attr_done[scaled] = true;
   }
-  hipLaunchKernelGGL(ray_bias_kernel, dim3(grid_for((n_rays + rpb - 1) / rpb, 1)), dim3(256), lds, stream, w, viewdirs,
-                     hist, hist_rows, n_rays, table);
+  hipLaunchKernelGGL(kern, dim3(grid_for((n_rays + rpb - 1) / rpb, 1)), dim3(256), lds, stream, w, viewdirs,
+                     hist, hist_rows, n_rays, table, scale);
   return hipGetLastError();
 }
 
