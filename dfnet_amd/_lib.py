@@ -15,6 +15,7 @@ DFN_PREC_F16X3 = 2  # DFNet only: split-f16 (fp32-grade results at f16 MFMA rate
 PRECISIONS = {"f16": DFN_PREC_F16, "fp16": DFN_PREC_F16, "f32": DFN_PREC_F32, "fp32": DFN_PREC_F32, "f16x3": DFN_PREC_F16X3}
 
 COMP_TEST_TIME, COMP_STATIC_ONLY, COMP_WHITE_BKGD = 1, 2, 4
+COMP_COARSE = 16   # typ == "coarse" (dfn_raw2outputs)
 RENDER_LINDISP, RENDER_COARSE_F16 = 1, 2
 
 
@@ -43,6 +44,11 @@ class MapGrads(Structure):
     """dfn_map_grads (include/dfnet_hip.h): upstream gradients of the compositor's outputs, NULL = zero"""
     _fields_ = [("rgb", c_void_p), ("acc", c_void_p), ("depth", c_void_p), ("depth_static", c_void_p), ("disp", c_void_p),
                 ("beta", c_void_p), ("rgb_static", c_void_p), ("rgb_transient", c_void_p)]
+
+
+class Raw2OutputsGrads(Structure):
+    """dfn_raw2outputs_grads (include/dfnet_hip.h): upstream gradients of what raw2outputs_NeRFW returns, NULL = zero"""
+    _fields_ = [("rgb", c_void_p), ("disp", c_void_p), ("acc", c_void_p), ("weights", c_void_p), ("depth", c_void_p), ("beta", c_void_p)]
 
 
 class TrainMapGrads(Structure):
@@ -103,6 +109,10 @@ SIGNATURES = {
     "dfn_composite_fine_maps": (c_int, [_P, _P, c_size_t, c_int, c_float, POINTER(RenderMaps), _P]),
     "dfn_composite_fine_backward": (c_int, [_P, _P, _P, c_size_t, c_int, _P, _P]),
     "dfn_composite_fine_backward_maps": (c_int, [_P, _P, c_size_t, c_int, c_float, POINTER(MapGrads), _P, _P, _P]),
+    # models/rendering.py:132-243 raw2outputs_NeRFW as a stage, forward and backward w.r.t. raw and z_vals
+    "dfn_raw2outputs": (c_int, [_P, c_int, _P, _P, c_float, c_size_t, c_int, c_float, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "dfn_raw2outputs_backward": (c_int, [_P, c_int, _P, _P, c_float, c_size_t, c_int, c_float, c_int, POINTER(Raw2OutputsGrads), _P, _P,
+                                         _P]),
     "dfn_mlp_fine_backward": (c_int, [_P, c_int, _P, _P, _P, _P, c_size_t, c_size_t, _P, c_int, _P, _P, _P, _P]),
     "dfn_mlp_fine_mask_bytes": (c_size_t, [c_size_t]),
     "dfn_mlp_fine_saving": (c_int, [_P, c_int, _P, _P, _P, _P, c_size_t, c_size_t, _P, c_int, _P, _P, _P, _P]),

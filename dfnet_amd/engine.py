@@ -968,6 +968,66 @@ def composite_fine(raw, z, beta_min=0.1, test_time=True, static_only=True, white
     return out
 
 
+R2O_GRAD_NAMES = tuple(n for n, _ in _lib.Raw2OutputsGrads._fields_)   # rgb, disp, acc, weights, depth, beta
+
+
+def _r2o_args(raw, z, noise, noise_std, test_time, static_only, white_bkgd, coarse):
+    """(raw, ch, z, noise, noise_std, n, N, flags) of dfn_raw2outputs / _backward: raw [n,N] or [n,N,1] (the coarse test-time mode), [n,N,4]
+    or [n,N,9]; the channel count selects the arithmetic mode."""
+    raw, z = _f32c(raw), _f32c(z)
+    n, N = z.shape
+    ch = 1 if raw.dim() == 2 else raw.shape[-1]
+    if raw.numel() != n * N * ch:
+        raise ValueError(f"raw {tuple(raw.shape)} does not go with z {tuple(z.shape)}")
+    if noise is not None:
+        noise = _f32c(noise).reshape(n, N)
+    flags = (_lib.COMP_TEST_TIME if test_time else 0) | (_lib.COMP_STATIC_ONLY if static_only else 0) | \
+            (_lib.COMP_WHITE_BKGD if white_bkgd else 0) | (_lib.COMP_COARSE if coarse else 0)
+    return raw, ch, z, noise, (0. if noise is None else float(noise_std)), n, N, flags
+
+
+def raw2outputs(raw, z, noise=None, noise_std=0., beta_min=0.1, test_time=False, static_only=True, white_bkgd=False, coarse=False):
+    """raw2outputs_NeRFW (models/rendering.py:132-243) on the device (dfn_raw2outputs); the channel count of raw selects the mode:
+    [n,N] / [n,N,1] the coarse test-time mode (needs coarse and test_time) -> dict(acc, weights); [n,N,4] -> dict(rgb, disp, acc,
+    weights, depth); [n,N,9] -> the same and beta (composite_fine's bits).  noise [n,N] x noise_std is added to sigma before the relu
+    (not with 9 channels)."""
+    lib = _lib.load()
+    raw, ch, z, noise, noise_std, n, N, flags = _r2o_args(raw, z, noise, noise_std, test_time, static_only, white_bkgd, coarse)
+    dev = raw.device
+    out = dict(acc=torch.empty(n, device=dev), weights=torch.empty(n, N, device=dev))
+    if ch != 1:
+        out.update(rgb=torch.empty(n, 3, device=dev), disp=torch.empty(n, device=dev), depth=torch.empty(n, device=dev))
+    if ch == 9:
+        out.update(beta=torch.empty(n, device=dev))
+    check(lib.dfn_raw2outputs(ptr(raw), ch, ptr(z), ptr(noise), noise_std, n, N, float(beta_min), flags, ptr(out.get("rgb")),
+                              ptr(out.get("disp")), ptr(out["acc"]), ptr(out["weights"]), ptr(out.get("depth")), ptr(out.get("beta")),
+                              current_stream()), "dfn_raw2outputs")
+    return out
+
+
+def raw2outputs_backward(raw, z, grads, noise=None, noise_std=0., beta_min=0.1, test_time=False, static_only=True, white_bkgd=False,
+                         coarse=False, want=("raw", "z")):
+    """(d L/d raw, d L/d z) through raw2outputs (dfn_raw2outputs_backward) from grads = {name: tensor} over rgb [n,3], disp, acc, depth,
+    beta [n] and a dense weights [n,N]; a missing name or None is a zero gradient.  d L/d raw has the shape of raw and is the gradient of
+    the post-activation raw given (exactly 0 on sigma behind a closed relu gate); d L/d z [n,N].  want: which of the two is computed, the
+    other is returned as None."""
+    unknown = [k for k in grads if k not in R2O_GRAD_NAMES]
+    if unknown:
+        raise ValueError(f"unknown upstream gradient(s) {unknown}: raw2outputs returns {list(R2O_GRAD_NAMES)}")
+    unknown = [k for k in want if k not in ("raw", "z")]
+    if unknown:
+        raise ValueError(f"want holds {unknown}: the inputs are 'raw' and 'z'")
+    shape = raw.shape
+    raw, ch, z, noise, noise_std, n, N, flags = _r2o_args(raw, z, noise, noise_std, test_time, static_only, white_bkgd, coarse)
+    held = {k: _f32c(t).reshape({"rgb": (n, 3), "weights": (n, N)}.get(k, (n,))) for k, t in grads.items() if t is not None}
+    st = _lib.Raw2OutputsGrads(**{k: t.data_ptr() for k, t in held.items()})
+    graw = torch.empty(shape, device=raw.device) if "raw" in want else None
+    gz = torch.empty(n, N, device=raw.device) if "z" in want else None
+    check(_lib.load().dfn_raw2outputs_backward(ptr(raw), ch, ptr(z), ptr(noise), noise_std, n, N, float(beta_min), flags, ctypes.byref(st),
+                                               ptr(graw), ptr(gz), current_stream()), "dfn_raw2outputs_backward")
+    return graw, gz
+
+
 def composite_fine_maps(raw, z, beta_min=0.1, maps=MAP_NAMES):
     """{name: map} of the requested render maps (models/rendering.py:196-241) from raw [n,Nf,9] and z [n,Nf]: depth, depth_static,
     beta [n]; rgb_static, rgb_transient [n,3] (dfn_composite_fine_maps)."""

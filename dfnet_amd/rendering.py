@@ -1,5 +1,6 @@
 """Host-side mirror of /root/reference/script/models/rendering.py: same function names, arguments
-and return shapes (`render`, `render_path`, `render_test`), evaluated by the HIP library.
+and return shapes (`render`, `render_path`, `render_test`, and the two stages a caller composes a renderer of their own from:
+`raw2outputs_NeRFW`, differentiable in raw and z_vals, and `sample_pdf`), evaluated by the HIP library.
 
 What the reference does per ray chunk in Python (`batchify_rays` -> `render_rays` -> `netchunk`
 loops, rendering.py:245-351) is one call into libdfnet_hip.so here; `chunk`/`netchunk` are accepted
@@ -395,6 +396,112 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     if retraw:
         extras['raw'] = out[-1]
     return _shaped(lead, *out[:3], extras)
+
+
+# ------------------------------------------------------------------------------------------ the compositor and the sampler as public stages
+_R2O_OUTPUTS = {1: ("acc", "weights"), 4: ("rgb", "disp", "acc", "weights", "depth"), 9: ("rgb", "disp", "acc", "weights", "depth", "beta")}
+
+
+class _Raw2OutputsFn(torch.autograd.Function):
+    """engine.raw2outputs attached to autograd with respect to raw and z_vals (dfn_raw2outputs_backward).  The outputs are those of the
+    mode (_R2O_OUTPUTS by channel count); one the loss does not use arrives as None = a NULL upstream pointer, and needs_input_grad
+    decides which of d L/d raw and d L/d z_vals the kernel computes."""
+
+    @staticmethod
+    def forward(ctx, raw, z, noise, noise_std, beta_min, opts):
+        from . import engine as _e
+        raw, z = raw.detach().contiguous(), z.detach().contiguous()
+        out = _e.raw2outputs(raw, z, noise, noise_std, beta_min, **opts)
+        ctx.save_for_backward(raw, z, noise)
+        ctx.noise_std, ctx.beta_min, ctx.opts = noise_std, beta_min, opts
+        ctx.names = _R2O_OUTPUTS[1 if raw.dim() == 2 else raw.shape[-1]]
+        ctx.set_materialize_grads(False)
+        return tuple(out[k] for k in ctx.names)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        from . import engine as _e
+        raw, z, noise = ctx.saved_tensors
+        want = tuple(k for k, need in zip(("raw", "z"), ctx.needs_input_grad[:2]) if need)
+        grads = {k: g for k, g in zip(ctx.names, gs) if g is not None}
+        if not grads or not want:
+            return (None,) * 6
+        graw, gz = _e.raw2outputs_backward(raw, z, grads, noise, ctx.noise_std, ctx.beta_min, want=want, **ctx.opts)
+        return (graw, gz) + (None,) * 4
+
+
+def raw2outputs_NeRFW(raw, z_vals, rays_d, raw_noise_std=0, output_transient=False, beta_min=0.1, white_bkgd=False, test_time=False,
+                      static_only=True, typ="coarse", noise=None):
+    """Drop-in for models/rendering.py:132-243 on the device: the reference's signature and argument order plus `noise`, and its 7-tuple
+    (rgb_map, disp_map, acc_map, weights, depth_map, transient_sigmas, beta).
+
+    Modes and what they return, as in the reference:
+      typ == "coarse" and test_time: raw [n,N,C>=1], channel 0 = sigma -> (None, None, acc, weights, None, None, None); with
+        output_transient=True a TypeError, as there (`deltas * None`);
+      output_transient=False otherwise: raw [n,N,4] = (rgb, sigma) -> beta is zeros [n], transient_sigmas None;
+      output_transient=True: raw [n,N,9] -> everything, transient_sigmas = raw[..., 7]; with test_time and static_only the depth (and
+        with it disp) comes from the static field's own transmittance.
+    Another channel count raises NotImplementedError: feature heads are not part of the NeRF-H path.  rays_d is accepted and unused, as
+    in the reference.  Inputs are fp32 device tensors; there is no CPU fallback.
+
+    noise [n,N]: the draws the reference takes from torch.randn_like at :173 (multiplied by raw_noise_std, added to sigma before the
+    relu).  Without it, raw_noise_std != 0 draws torch.randn on the device; at raw_noise_std == 0 NOTHING is drawn - the reference draws
+    even then (and multiplies by 0), so a caller who relies on the generator's state after the call sees a difference.  The transient
+    mode has no noise in the reference; an explicit `noise` there is refused.
+
+    Autograd: under grad mode with raw or z_vals requiring grad every returned tensor is attached, and backward runs ONE kernel for
+    d L/d raw and d L/d z_vals from whichever outputs the loss used (dfn_raw2outputs_backward; transient_sigmas is a slice of raw and
+    needs none).  Otherwise this is the plain forward."""
+    from . import engine as _e
+    coarse_test = typ == "coarse" and bool(test_time)
+    if coarse_test and output_transient:
+        raise TypeError("raw2outputs_NeRFW: typ='coarse' with test_time and output_transient=True: transient_sigmas is None there "
+                        "(unsupported operand type(s) for *: 'Tensor' and 'NoneType', models/rendering.py:170)")
+    if raw.dim() != 3 or z_vals.dim() != 2 or raw.shape[:2] != z_vals.shape:
+        raise ValueError(f"raw2outputs_NeRFW: raw [n,N,C] and z_vals [n,N] expected, got {tuple(raw.shape)} and {tuple(z_vals.shape)}")
+    ch = raw.shape[-1]
+    if not coarse_test and ch != (9 if output_transient else 4):
+        raise NotImplementedError(f"raw2outputs_NeRFW: {ch} channels with output_transient={bool(output_transient)}: the NeRF-H path has "
+                                  "(rgb, sigma) = 4 or static + transient = 9 (feature heads are not part of it)")
+    std = 0. if output_transient else float(raw_noise_std)
+    if output_transient and noise is not None:
+        raise ValueError("raw2outputs_NeRFW: noise together with output_transient=True (the transient mode draws none)")
+    if std != 0. and noise is None:
+        noise = torch.randn(z_vals.shape, device=raw.device)
+    if std == 0.:
+        noise = None
+    elif noise is not None:
+        noise = noise.detach().float().contiguous()
+    opts = dict(test_time=bool(test_time), static_only=bool(static_only), white_bkgd=bool(white_bkgd), coarse=typ == "coarse")
+    arg = raw[..., 0] if coarse_test else raw   # a torch slice: its gradient needs no kernel
+    if torch.is_grad_enabled() and (raw.requires_grad or z_vals.requires_grad):
+        out = dict(zip(_R2O_OUTPUTS[1 if coarse_test else ch], _Raw2OutputsFn.apply(arg, z_vals, noise, std, float(beta_min), opts)))
+    else:
+        out = _e.raw2outputs(arg, z_vals, noise, std, float(beta_min), **opts)
+        raw = raw.detach()   # (a slice of a leaf taken under no_grad would still say requires_grad)
+    if coarse_test:
+        return None, None, out["acc"], out["weights"], None, None, None
+    if not output_transient:
+        return out["rgb"], out["disp"], out["acc"], out["weights"], out["depth"], None, torch.zeros_like(out["acc"])
+    return out["rgb"], out["disp"], out["acc"], out["weights"], out["depth"], raw[..., 7], out["beta"]
+
+
+def sample_pdf(bins, weights, N_samples, det=False, pytest=False, u=None):
+    """Drop-in for models/rendering.py:24-65 on the device (dfn_sample_pdf): bins [n,nb], weights [n,nb-1] -> samples [n,N_samples].
+    det: u = linspace(0, 1, N_samples); otherwise torch.rand on the device; pytest=True: the reference's np.random.seed(0) draws
+    formed on the host (:39-47); u [n,N_samples]: explicit draws (this port's addition; it overrides the other three).
+    The result is returned DETACHED whatever the inputs require: the reference's only caller detaches it (:302), and the sampler has no
+    backward here."""
+    from . import engine as _e
+    bins, weights = bins.detach(), weights.detach()
+    n = bins.shape[0]
+    if u is None and pytest:
+        np.random.seed(0)
+        host = np.broadcast_to(np.linspace(0., 1., N_samples), (n, N_samples)) if det else np.random.rand(n, N_samples)
+        u = torch.Tensor(np.ascontiguousarray(host)).to(bins.device)
+    elif u is None and not det:
+        u = torch.rand(n, N_samples, device=bins.device)
+    return _e.sample_pdf(bins, weights, int(N_samples), u=None if u is None else u.detach())
 
 
 def _png_bytes(arr):

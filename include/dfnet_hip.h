@@ -255,6 +255,44 @@ typedef struct {
  * too; n_rays == 0 is DFN_OK.  dfn_composite_fine_backward and its kernel are not involved. */
 int dfn_composite_fine_backward_maps(const float* raw, const float* z, size_t n_rays, int Nf, float beta_min,
                                      const dfn_map_grads* grads, const float* grad_raw_ext, float* grad_raw, void* stream);
+
+/* raw2outputs_NeRFW as a stage of its own (rendering.py:132-243), in the three arithmetic modes the function has; `ch`, the channel
+ * count of raw [n_rays, N, ch], selects the mode:
+ *   ch = 1  typ == "coarse" and test_time (:140-142, :188-193): raw is the sigma channel alone; alpha = 1 - exp(-delta relu(sigma +
+ *           noise_std noise)); writes acc and weights only.  Requires DFN_COMP_COARSE | DFN_COMP_TEST_TIME in flags, and those two
+ *           bits together require ch = 1 (the reference reads raw[..., 0] there: pass that channel).
+ *   ch = 4  output_transient = False otherwise (:144-152, :173-174, :232-243): raw = (rgb, sigma); the same alpha; rgb = sum w c
+ *           (+ 1 - acc with DFN_COMP_WHITE_BKGD), depth = sum w z, disp = 1 / max(1e-10, depth / sum w).  beta is not written
+ *           (the reference returns zeros there).
+ *   ch = 9  output_transient = True (:153-156, :168-171, :195-230): dfn_composite_fine, all of its flags; rgb, disp, acc non-NULL.
+ * In every mode delta_i = z_{i+1} - z_i, the last delta is 1e2, no |d| factor (:161-166), 1 <= N <= 512.  noise [n_rays, N]
+ * (optional) are the draws of :173, multiplied by noise_std; NULL = none; not with ch = 9 (the transient branch draws none).  For
+ * ch = 1, 4 every output pointer is optional.  rgb [n,3]; disp, acc, depth, beta [n]; weights [n,N].
+ * DFN_ERR_ARG: N outside 1..512, another ch, ch and the coarse / test-time bits at odds, noise with ch = 9.  n_rays == 0 is DFN_OK.
+ * Caller-allocated buffers, enqueued on `stream`, no allocation and no synchronisation. */
+enum { DFN_COMP_COARSE = 16 };   /* typ == "coarse", beside the DFN_COMP_* bits above (8 is taken inside the library) */
+int dfn_raw2outputs(const float* raw, int ch, const float* z_vals, const float* noise, float noise_std, size_t n_rays, int N,
+                    float beta_min, int flags, float* rgb, float* disp, float* acc, float* weights, float* depth, float* beta,
+                    void* stream);
+/* Upstream gradients of what raw2outputs_NeRFW returns: rgb [n,3]; disp, acc, depth, beta [n]; weights DENSE [n,N].  Every member is
+ * optional: NULL = a zero gradient.  (transient_sigmas is raw[..., 7] itself and needs no kernel.) */
+typedef struct {
+  const float *rgb, *disp, *acc, *weights, *depth, *beta;
+} dfn_raw2outputs_grads;
+/* Backward of dfn_raw2outputs with respect to BOTH of its inputs, as the reference's function is differentiable under autograd
+ * (rendering.py:161-243; raw, ch, z_vals, noise, noise_std, flags as in the forward call):
+ *   grad_raw [n_rays, N, ch] = d L / d raw, the POST-activation raw the function was given; exactly 0 on sigma where the relu gate
+ *            of ch = 1, 4 is closed;
+ *   grad_z   [n_rays, N]     = d L / d z_vals: through the intervals (d z_i = d delta_{i-1} - d delta_i, the constant last interval
+ *            carries none) plus the direct factor of depth (the joint weights; the static-only ones under test_time and static_only).
+ * Either output may be NULL and is then not computed.  Members of `grads` that the mode does not return are ignored (ch = 1: all but
+ * acc and weights; ch = 4: beta).  disp contributes nothing where its clamp is active.  Nothing is divided by 1 - alpha: opaque
+ * samples, duplicate depths and N = 1 give finite gradients.  Deterministic.
+ * DFN_ERR_ARG: as dfn_raw2outputs; no upstream gradient of the mode given; grad_raw and grad_z both NULL.  n_rays == 0 is DFN_OK. */
+int dfn_raw2outputs_backward(const float* raw, int ch, const float* z_vals, const float* noise, float noise_std, size_t n_rays, int N,
+                             float beta_min, int flags, const dfn_raw2outputs_grads* grads, float* grad_raw, float* grad_z,
+                             void* stream);
+
 /* Fine-network input gradient: from grad_raw [n_rays, Nf, 9] to grad_pts [n_rays, Nf, 6] =
  * [d L / d sample point (3), d L / d viewdir through this sample (3)].  Other arguments as dfn_mlp_fine. */
 int dfn_mlp_fine_backward(dfn_nerfh_t h, int prec, const float* rays_o, const float* rays_d,
