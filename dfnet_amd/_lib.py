@@ -92,6 +92,7 @@ SIGNATURES = {
     "dfn_mlp_coarse": (c_int, [_P, c_int, _P, _P, c_size_t, c_int, c_float, c_float, _P, _P]),
     "dfn_coarse_weights": (c_int, [_P, _P, c_size_t, c_int, _P, _P]),
     "dfn_sample_pdf": (c_int, [_P, _P, c_size_t, c_int, c_int, _P, _P, _P]),
+    "dfn_sample_pdf_backward": (c_int, [_P, _P, c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "dfn_sample_fine": (c_int, [_P, c_size_t, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
     "dfn_fine_bias_bytes": (c_size_t, [c_size_t]),
     "dfn_mlp_fine": (c_int, [_P, c_int, _P, _P, _P, _P, c_size_t, c_size_t, _P, c_int, _P, _P, _P]),

@@ -929,6 +929,22 @@ extern "C" int dfn_sample_pdf(const float* bins, const float* weights, size_t n,
   return DFN_OK;
 }
 
+extern "C" int dfn_sample_pdf_backward(const float* bins, const float* weights, size_t n, int nb, int Ni, const float* u,
+                                       const float* grad_out, float* grad_bins, float* grad_weights, float* grad_u, void* stream) {
+  if (!bins || !weights || !grad_out) return set_error(DFN_ERR_ARG, "dfn_sample_pdf_backward: bad argument (bins, weights or grad_out NULL)");
+  if (nb < 2 || Ni < 1) return set_error(DFN_ERR_ARG, "dfn_sample_pdf_backward: bad argument (need nb >= 2 and Ni >= 1, got %d and %d)", nb, Ni);
+  if (!grad_bins && !grad_weights && !grad_u)
+    return set_error(DFN_ERR_ARG, "dfn_sample_pdf_backward: bad argument (grad_bins, grad_weights and grad_u all NULL)");
+  if (grad_u && !u) return set_error(DFN_ERR_ARG, "dfn_sample_pdf_backward: bad argument (grad_u without u: the linspace draws are constants)");
+  if (sample_pdf_backward_lds_bytes(nb, Ni) > kSamplePdfBackwardMaxLds)
+    return set_error(DFN_ERR_UNSUPPORTED, "dfn_sample_pdf_backward: nb = %d, Ni = %d need %zu bytes of LDS per block, the kernel has %zu", nb, Ni,
+                     sample_pdf_backward_lds_bytes(nb, Ni), kSamplePdfBackwardMaxLds);
+  if (!n) return DFN_OK;
+  CHECK_HIP(launch_sample_pdf_backward(bins, weights, n, nb, Ni, u, grad_out, grad_bins, grad_weights, grad_u, HS(stream)),
+            "dfn_sample_pdf_backward");
+  return DFN_OK;
+}
+
 extern "C" int dfn_sample_fine_opt(const float* sigma, size_t n_rays, int Nc, int Ni, float near, float far, int render_flags,
                                    float* z_fine, float* weights_coarse, float* z_samples, void* stream) {
   if (!sigma || !z_fine || Nc < 3 || Ni < 1 || 6 * Nc + 2 * Ni > 8192)

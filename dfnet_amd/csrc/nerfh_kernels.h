@@ -102,6 +102,13 @@ hipError_t launch_coarse_weights(const float* sigma, const float* z, size_t n, i
                                  hipStream_t stream);
 hipError_t launch_sample_pdf(const float* bins, const float* weights, size_t n, int nb, int Ni,
                              const float* u, float* out, hipStream_t stream);
+// Backward of launch_sample_pdf (grad_out [n, Ni] -> grad_bins [n, nb], grad_weights [n, nb-1], grad_u [n, Ni]; a NULL output is
+// skipped).  Its LDS need is sample_pdf_backward_lds_bytes(nb, Ni) per block; a shape above kSamplePdfBackwardMaxLds (what a kernel may
+// ask for without an attribute) is hipErrorInvalidValue, never a launch.
+constexpr size_t kSamplePdfBackwardMaxLds = 64 * 1024;
+size_t sample_pdf_backward_lds_bytes(int nb, int Ni);
+hipError_t launch_sample_pdf_backward(const float* bins, const float* weights, size_t n, int nb, int Ni, const float* u,
+                                      const float* grad_out, float* grad_bins, float* grad_weights, float* grad_u, hipStream_t stream);
 hipError_t launch_sample_fine(const float* sigma, size_t n_rays, int Nc, int Ni, float near, float far,
                               float* z_fine, float* weights_coarse, float* z_samples, hipStream_t stream, int lindisp = 0);
 hipError_t launch_composite_fine(const float* raw, const float* z, size_t n_rays, int Nf, float beta_min,

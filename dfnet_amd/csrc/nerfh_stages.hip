@@ -287,8 +287,10 @@ DFN_DEV void ray_coarse_weights(const float* sig, const float* z, int N, float* 
 
 // Inverse-CDF sampling of one ray (rendering.py:24-65).  bins[0..nb), wts[0..nb-1) in LDS;
 // cdf[0..nb) scratch in LDS; writes out[0..Ni).  u == nullptr -> linspace(0,1,Ni).
-DFN_DEV void ray_sample_pdf(const float* bins, const float* wts, int nb, float* cdf, const float* u, int Ni,
-                            float* out, int lane) {
+// The two halves below are shared with the sampler's backward (ray_sample_pdf_backward), which has to rebuild the forward's cdf and
+// find the forward's bin for every sample: one piece of device code, one operation order.
+// cdf[0..nb) of pdf = (w + 1e-5) / S from wts[0..nb-1); returns S.  Leaves the cdf visible to the whole wave.
+DFN_DEV float ray_build_cdf(const float* wts, int nb, float* cdf, int lane) {
   const int nw = nb - 1;
   float part = 0.f;
   for (int i = lane; i < nw; i += 64) part += add_rn(wts[i], 1e-5f);
@@ -303,21 +305,107 @@ DFN_DEV void ray_sample_pdf(const float* bins, const float* wts, int nb, float* 
     carry = add_rn(carry, __shfl(incl, 63, 64));
   }
   wave_sync();  // cdf visible to the whole wave
+  return total;
+}
+// The bin of one draw: below / above = the clamped neighbours of the first index with cdf > u (searchsorted right=True), and
+// t = (u - cdf[below]) / den with den = cdf[above] - cdf[below], replaced by 1 below 1e-5 (live = not replaced).
+struct PdfBin { int below, above; float t, den; bool live; };
+DFN_DEV PdfBin ray_cdf_bin(const float* cdf, int nb, float uj) {
+  int lo = 0, hi = nb;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cdf[mid] <= uj) lo = mid + 1; else hi = mid;
+  }
+  PdfBin b;
+  b.below = lo - 1 > 0 ? lo - 1 : 0;
+  b.above = lo < nb - 1 ? lo : nb - 1;
+  const float c0 = cdf[b.below], c1 = cdf[b.above];
+  b.den = sub_rn(c1, c0);
+  b.live = !(b.den < 1e-5f);
+  if (!b.live) b.den = 1.f;
+  b.t = sub_rn(uj, c0) / b.den;
+  return b;
+}
+DFN_DEV void ray_sample_pdf(const float* bins, const float* wts, int nb, float* cdf, const float* u, int Ni,
+                            float* out, int lane) {
+  ray_build_cdf(wts, nb, cdf, lane);
+  for (int j = lane; j < Ni; j += 64) {
+    const PdfBin b = ray_cdf_bin(cdf, nb, u ? u[j] : unit_linspace(j, Ni));
+    out[j] = add_rn(bins[b.below], mul_rn(b.t, sub_rn(bins[b.above], bins[b.below])));
+  }
+}
+
+// Backward of ray_sample_pdf for one row (rendering.py:24-65 under autograd): g[0..Ni) = d L/d samples -> d L/d bins [nb], d L/d
+// weights [nb-1], d L/d u [Ni], each written to global memory when its pointer is non-NULL.  Conventions, all autograd's: the search
+// carries no gradient; where den was replaced by 1 (torch.where) only the numerator's cdf[below] receives one; at the clamped ends
+// (below == above) both halves of the bin gradient land on the one edge, as gather's backward adds them.
+//   per sample: g_t = g (b1 - b0); d bins[below] += g (1 - t), d bins[above] += g t; d u = g_t / den (den of a live bin: see below);
+//               d cdf[below] += g_t ((live ? t : 0) - 1) / den, d cdf[above] += live ? -g_t t / den : 0;
+//   cdf[k] = sum_{m<k} pdf[m]  =>  d pdf[m] = sum_{k>m} d cdf[k] (a suffix scan; cdf[0] is a constant);
+//   pdf = (w + 1e-5) / S       =>  d w[m] = (d pdf[m] - sum_k d pdf[k] pdf[k]) / S.
+// Several samples share a bin.  Pass 1 leaves every sample's four contributions (contrib[j] = to bins[below], bins[above], cdf[below],
+// cdf[above]) and its bin (idx[j] = below | above << 16) in LDS; in pass 2 lane l OWNS bins l, l + 64, ... and walks the samples in
+// index order, so every per-bin sum has one order of summation, the code's: no atomics, the same bits on every call.  All lanes read
+// the same LDS address in that walk (a broadcast: no bank conflict), ceil(nb / 64) Ni steps per lane.
+// LDS: cdf[nb] is overwritten with d cdf in pass 2, bins[nb] with d pdf in pass 3; wts stays (pdf is formed from it again).
+DFN_DEV void ray_sample_pdf_backward(float* bins, const float* wts, int nb, float* cdf, const float* u, const float* g, int Ni,
+                                     f32x4_t* contrib, int* idx, float* grad_bins, float* grad_w, float* grad_u, int lane) {
+  const int nw = nb - 1;
+  const float total = ray_build_cdf(wts, nb, cdf, lane);
+  const bool scatter = grad_bins || grad_w;
   for (int j = lane; j < Ni; j += 64) {
     const float uj = u ? u[j] : unit_linspace(j, Ni);
-    int lo = 0, hi = nb;  // first index with cdf > u  (searchsorted right=True)
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (cdf[mid] <= uj) lo = mid + 1; else hi = mid;
+    const PdfBin b = ray_cdf_bin(cdf, nb, uj);
+    // The bin and its live / replaced branch are the forward's.  The cdf step a live bin's derivative divides by is pdf[below], the
+    // very number the forward's scan summed, not the difference of two scanned knots: each knot carries the scan's roundings (~1e-7
+    // at cdf ~ 1), which is 1e-4 of a step of 1e-3 and goes straight into d u and d cdf (LABBOOK R21.2).
+    float den = b.den, t = b.t;
+    if (b.live) {
+      den = add_rn(wts[b.below], 1e-5f) / total;
+      t = sub_rn(uj, cdf[b.below]) / den;
     }
-    const int below = lo - 1 > 0 ? lo - 1 : 0;
-    const int above = lo < nb - 1 ? lo : nb - 1;
-    const float c0 = cdf[below], c1 = cdf[above];
-    float den = sub_rn(c1, c0);
-    if (den < 1e-5f) den = 1.f;
-    const float t = sub_rn(uj, c0) / den;
-    out[j] = add_rn(bins[below], mul_rn(t, sub_rn(bins[above], bins[below])));
+    const float gj = g[j];
+    const float gt = gj * sub_rn(bins[b.above], bins[b.below]);
+    const float gtd = gt / den;
+    if (grad_u) grad_u[j] = gtd;
+    if (scatter) {
+      f32x4_t c;
+      c[0] = gj * (1.f - t);
+      c[1] = gj * t;
+      c[2] = b.live ? gtd * (t - 1.f) : -gtd;
+      c[3] = b.live ? -gtd * t : 0.f;
+      contrib[j] = c;
+      idx[j] = b.below | (b.above << 16);
+    }
   }
+  if (!scatter) return;
+  wave_sync();  // contributions visible; every lane is done with cdf and bins
+  for (int k = lane; k < nb; k += 64) {
+    float gb = 0.f, gc = 0.f;
+    for (int j = 0; j < Ni; ++j) {
+      const int ix = idx[j];
+      const f32x4_t c = contrib[j];
+      if ((ix & 0xffff) == k) { gb += c[0]; gc += c[2]; }
+      if ((ix >> 16) == k) { gb += c[1]; gc += c[3]; }
+    }
+    if (grad_bins) grad_bins[k] = gb;
+    cdf[k] = gc;
+  }
+  if (!grad_w) return;
+  wave_sync();  // d cdf visible
+  float carry = 0.f, part = 0.f;   // suffix scan in chunks of 64 from the far end, the mirror of the forward's prefix scan
+  for (int c0 = ((nw - 1) / 64) * 64; c0 >= 0; c0 -= 64) {
+    const int i = c0 + lane;
+    const float incl = wave_incl_suffix_sum(i < nw ? cdf[i + 1] : 0.f, lane);
+    if (i < nw) {
+      const float gp = carry + incl;
+      bins[i] = gp;   // read back below by the lane that wrote it
+      part += gp * (add_rn(wts[i], 1e-5f) / total);
+    }
+    carry += __shfl(incl, 0, 64);
+  }
+  const float dot = wave_sum(part);
+  for (int i = lane; i < nw; i += 64) grad_w[i] = (bins[i] - dot) / total;
 }
 
 // ------------------------------------------------------------------------------------------ standalone stage kernels
@@ -372,6 +460,49 @@ hipError_t launch_sample_pdf(const float* bins, const float* weights, size_t n, 
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(sample_pdf_kernel, dim3(grid_for((n + 3) / 4, 1)), dim3(256), size_t(4) * (3 * nb + 2 * Ni) * 4,
                      stream, bins, weights, n, nb, Ni, u, out);
+  return hipGetLastError();
+}
+
+// Backward of sample_pdf_kernel, the same geometry: one wave per row, four rows per block, the row staged in LDS.  Per wave, in floats:
+// contrib [4 Ni] first (16-byte aligned: it is read as b128), idx [Ni], u [Ni], g [Ni], bins, wts, cdf [nb each], rounded up to 4.
+__host__ __device__ static inline size_t sample_pdf_backward_row_floats(int nb, int Ni) { return (size_t(7) * Ni + size_t(3) * nb + 3) & ~size_t(3); }
+size_t sample_pdf_backward_lds_bytes(int nb, int Ni) { return 4 * sample_pdf_backward_row_floats(nb, Ni) * sizeof(float); }
+
+__global__ __launch_bounds__(256) void sample_pdf_backward_kernel(const float* __restrict__ bins, const float* __restrict__ wts, size_t n,
+                                                                  int nb, int Ni, const float* __restrict__ u,
+                                                                  const float* __restrict__ grad_out, float* __restrict__ grad_bins,
+                                                                  float* __restrict__ grad_w, float* __restrict__ grad_u) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* base = sm + size_t(wave) * sample_pdf_backward_row_floats(nb, Ni);
+  f32x4_t* s_contrib = reinterpret_cast<f32x4_t*>(base);
+  int* s_idx = reinterpret_cast<int*>(base + size_t(4) * Ni);
+  float* s_u = base + size_t(5) * Ni;
+  float* s_g = s_u + Ni;
+  float* s_bins = s_g + Ni;
+  float* s_w = s_bins + nb;
+  float* s_cdf = s_w + nb;
+  for (size_t row = size_t(blockIdx.x) * 4 + wave; row < n; row += size_t(gridDim.x) * 4) {
+    for (int i = lane; i < nb; i += 64) s_bins[i] = bins[row * nb + i];
+    for (int i = lane; i < nb - 1; i += 64) s_w[i] = wts[row * (nb - 1) + i];
+    for (int i = lane; i < Ni; i += 64) {
+      if (u) s_u[i] = u[row * Ni + i];
+      s_g[i] = grad_out[row * Ni + i];
+    }
+    wave_sync();
+    ray_sample_pdf_backward(s_bins, s_w, nb, s_cdf, u ? s_u : nullptr, s_g, Ni, s_contrib, s_idx,
+                            grad_bins ? grad_bins + row * nb : nullptr, grad_w ? grad_w + row * (nb - 1) : nullptr,
+                            grad_u ? grad_u + row * Ni : nullptr, lane);
+    wave_sync();  // the next row's staging overwrites what this row still read
+  }
+}
+hipError_t launch_sample_pdf_backward(const float* bins, const float* weights, size_t n, int nb, int Ni, const float* u,
+                                      const float* grad_out, float* grad_bins, float* grad_weights, float* grad_u, hipStream_t stream) {
+  if (!n) return hipSuccess;
+  const size_t lds = sample_pdf_backward_lds_bytes(nb, Ni);
+  if (lds > kSamplePdfBackwardMaxLds) return hipErrorInvalidValue;   // (the entry refuses such a shape before it gets here)
+  hipLaunchKernelGGL(sample_pdf_backward_kernel, dim3(grid_for((n + 3) / 4, 1)), dim3(256), lds, stream, bins, weights, n, nb, Ni,
+                     u, grad_out, grad_bins, grad_weights, grad_u);
   return hipGetLastError();
 }
 

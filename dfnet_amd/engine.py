@@ -927,6 +927,34 @@ def sample_pdf(bins, weights, Ni, u=None):
     return out
 
 
+def sample_pdf_backward(bins, weights, Ni, grad_out, u=None, want=("bins", "weights", "u")):
+    """(d L/d bins [n,nb], d L/d weights [n,nb-1], d L/d u [n,Ni]) through sample_pdf (dfn_sample_pdf_backward) from grad_out [n,Ni] =
+    d L/d samples; bins, weights, Ni, u as in the forward call.  want: which of the three are computed, the others are returned as None;
+    'u' needs an explicit u (the linspace draws of u=None are constants).  The chosen bins are the forward's: the kernel rebuilds its cdf
+    with the forward's code."""
+    unknown = [k for k in want if k not in ("bins", "weights", "u")]
+    if unknown:
+        raise ValueError(f"want holds {unknown}: the inputs are 'bins', 'weights' and 'u'")
+    if "u" in want and u is None:
+        raise ValueError("want holds 'u' without an explicit u: the linspace draws are constants")
+    bins, weights, grad_out = _f32c(bins), _f32c(weights), _f32c(grad_out)
+    n, nb = bins.shape
+    Ni = int(Ni)
+    if weights.shape != (n, nb - 1) or grad_out.shape != (n, Ni) or (u is not None and u.shape != (n, Ni)):
+        raise ValueError(f"bins {tuple(bins.shape)}, weights {tuple(weights.shape)}, grad_out {tuple(grad_out.shape)}"
+                         f"{'' if u is None else f', u {tuple(u.shape)}'} do not go together with Ni = {Ni}")
+    if u is not None:
+        u = _f32c(u)
+    gb = torch.empty(n, nb, device=bins.device) if "bins" in want else None
+    gw = torch.empty(n, nb - 1, device=bins.device) if "weights" in want else None
+    gu = torch.empty(n, Ni, device=bins.device) if "u" in want else None
+    if n == 0:   # (an empty tensor has no pointer to pass)
+        return gb, gw, gu
+    check(_lib.load().dfn_sample_pdf_backward(ptr(bins), ptr(weights), n, nb, Ni, ptr(u), ptr(grad_out), ptr(gb), ptr(gw), ptr(gu),
+                                              current_stream()), "dfn_sample_pdf_backward")
+    return gb, gw, gu
+
+
 def ndc_rays(H, W, focal, near, rays_o, rays_d):
     """ray_utils.ndc_rays (models/ray_utils.py:27-46) on the device: (rays_o, rays_d) in normalised device coordinates."""
     lib = _lib.load()

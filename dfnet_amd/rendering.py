@@ -486,22 +486,52 @@ def raw2outputs_NeRFW(raw, z_vals, rays_d, raw_noise_std=0, output_transient=Fal
     return out["rgb"], out["disp"], out["acc"], out["weights"], out["depth"], raw[..., 7], out["beta"]
 
 
-def sample_pdf(bins, weights, N_samples, det=False, pytest=False, u=None):
+class _SamplePdfFn(torch.autograd.Function):
+    """engine.sample_pdf attached to autograd with respect to bins, weights and an explicit u (dfn_sample_pdf_backward).  u None = the
+    linspace draws, a constant; needs_input_grad decides which of the three gradients the kernel computes."""
+
+    @staticmethod
+    def forward(ctx, bins, weights, u, Ni):
+        from . import engine as _e
+        bins, weights = bins.detach().contiguous(), weights.detach().contiguous()
+        u = None if u is None else u.detach().contiguous()
+        ctx.save_for_backward(bins, weights, u)
+        ctx.Ni = Ni
+        return _e.sample_pdf(bins, weights, Ni, u=u)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import engine as _e
+        bins, weights, u = ctx.saved_tensors
+        want = tuple(k for k, need in zip(("bins", "weights", "u"), ctx.needs_input_grad[:3]) if need)
+        if not want:
+            return (None,) * 4
+        return _e.sample_pdf_backward(bins, weights, ctx.Ni, g, u=u, want=want) + (None,)
+
+
+def sample_pdf(bins, weights, N_samples, det=False, pytest=False, u=None, diff=False):
     """Drop-in for models/rendering.py:24-65 on the device (dfn_sample_pdf): bins [n,nb], weights [n,nb-1] -> samples [n,N_samples].
     det: u = linspace(0, 1, N_samples); otherwise torch.rand on the device; pytest=True: the reference's np.random.seed(0) draws
     formed on the host (:39-47); u [n,N_samples]: explicit draws (this port's addition; it overrides the other three).
-    The result is returned DETACHED whatever the inputs require: the reference's only caller detaches it (:302), and the sampler has no
-    backward here."""
+
+    diff=False (the default): the result is returned DETACHED whatever the inputs require, as the reference's only caller takes it
+    (:302).  diff=True: the reference's function itself, which is differentiable in bins, weights and u - under grad mode with bins,
+    weights or an explicit u requiring grad the samples are attached, and backward runs ONE kernel (dfn_sample_pdf_backward) for
+    whichever of the three need a gradient.  The draws of det, pytest and torch.rand are constants and receive none; the search has no
+    gradient, and where the cdf step of a bin is below 1e-5 its replaced denominator has none (torch.where).  With nothing requiring
+    grad, or under no_grad, diff=True is the plain forward; the values are the same bits either way."""
     from . import engine as _e
-    bins, weights = bins.detach(), weights.detach()
     n = bins.shape[0]
+    own_u = u is not None
     if u is None and pytest:
         np.random.seed(0)
         host = np.broadcast_to(np.linspace(0., 1., N_samples), (n, N_samples)) if det else np.random.rand(n, N_samples)
         u = torch.Tensor(np.ascontiguousarray(host)).to(bins.device)
     elif u is None and not det:
         u = torch.rand(n, N_samples, device=bins.device)
-    return _e.sample_pdf(bins, weights, int(N_samples), u=None if u is None else u.detach())
+    if diff and torch.is_grad_enabled() and (bins.requires_grad or weights.requires_grad or (own_u and u.requires_grad)):
+        return _SamplePdfFn.apply(bins, weights, u, int(N_samples))
+    return _e.sample_pdf(bins.detach(), weights.detach(), int(N_samples), u=None if u is None else u.detach())
 
 
 def _png_bytes(arr):

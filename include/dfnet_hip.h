@@ -133,6 +133,26 @@ int dfn_coarse_weights(const float* sigma, const float* z, size_t n, int N, floa
 int dfn_sample_pdf(const float* bins, const float* weights, size_t n, int nb, int Ni,
                    const float* u, float* out, void* stream);
 
+/* Backward of dfn_sample_pdf with respect to bins, weights and u, as the reference's sample_pdf (models/rendering.py:24-65) is
+ * differentiable under autograd; bins, weights, n, nb, Ni, u as in the forward call (u NULL = the linspace draws, which are
+ * constants), grad_out [n, Ni] = d L / d samples:
+ *   grad_bins    [n, nb]   = d L / d bins;
+ *   grad_weights [n, nb-1] = d L / d weights, through the cdf and the normalisation of pdf = (w + 1e-5) / sum;
+ *   grad_u       [n, Ni]   = d L / d u (needs u).
+ * Any output may be NULL and is then not computed.  The conventions are autograd's on the reference's code:
+ *   - the den branch: where cdf[above] - cdf[below] < 1e-5 the denominator was replaced by 1 (torch.where, :61) and carries no
+ *     gradient: only the numerator's cdf[below] receives one there;
+ *   - the clamped ends: where below == above (u outside the cdf's range, :52-53) both halves of the bin gradient land on that one
+ *     edge and sum to grad_out, as gather's backward adds them;
+ *   - no gradient through the search: searchsorted (:51) is piecewise constant, the chosen bin is the forward's.
+ * The forward's cdf and bins are rebuilt by the forward's device code; the cdf step a live bin's derivative divides by is pdf[below]
+ * itself (what the forward's scan summed), which is more accurate than the difference of two scanned knots.  One launch, no atomics, no workspace; every per-bin sum is
+ * taken in sample order: deterministic.
+ * DFN_ERR_ARG: bins, weights or grad_out NULL; nb < 2; Ni < 1; all three outputs NULL; grad_u without u.  DFN_ERR_UNSUPPORTED: a row
+ * of 3 nb + 7 Ni floats, four to a block, above 64 KiB of LDS (nothing is launched).  n == 0 is DFN_OK. */
+int dfn_sample_pdf_backward(const float* bins, const float* weights, size_t n, int nb, int Ni, const float* u,
+                            const float* grad_out, float* grad_bins, float* grad_weights, float* grad_u, void* stream);
+
 /* Fused production sampler: rendering.py:295-304 — coarse weights of sigma over the
  * linspace z, z_mid, sample_pdf(det) on the interior weights, merge/sort with the coarse z.
  * z_fine [n_rays, Nc+Ni]; weights_coarse / z_samples optional (may be NULL). */
