@@ -115,7 +115,7 @@ static void free_packed(dfn_nerfh_s* h) {
         if (n.res_blob) (void)hipFree(n.res_blob);
         n = PackedNet();
       }
-  for (PackedNet* n : {&h->bwd[0], &h->bwd[1], &h->bwd[2], &h->half_maps}) {
+  for (PackedNet* n : {&h->bwd[0], &h->bwd[1], &h->bwd[2], &h->half_maps, &h->bwd_coarse[0], &h->bwd_coarse[1], &h->bwd_coarse[2]}) {
     if (n->blob) (void)hipFree(n->blob);
     if (n->tab) (void)hipFree(n->tab);
     *n = PackedNet();
@@ -352,6 +352,7 @@ struct Packer {
         if (mb < 4) return W(mat("xyz_encoding_5.0"), j, kChXyz + k);
         return W(mat("xyz_encoding_5.0"), j, pe_col(mb - 4));
       case BW_L1: return W(mat("xyz_encoding_1.0"), j, pe_col(mb));
+      case BW_SIG: return (s == 0 && hh == 0) ? W(mat("static_sigma.0"), 0, k) : 0.f;   // the coarse chain's seed layer
       default: {  // BW_L8..BW_L6, BW_L4..BW_L2: 128 -> 128
         const int n = 8 - (layer - BW_L8);
         return W(mat("xyz_encoding_" + std::to_string(n) + ".0"), j, k);
@@ -380,13 +381,14 @@ struct Packer {
           }
   }
   // Blob of the gradient kernel: the fine net's forward layers, one unit per layer (f16) / per M-block (f32),
-  // then the backward layers the same way.
+  // then the backward layers the same way.  coarse: the coarse net's forward layers (kCoarseSeq), then the layers of kBwdCoarseSeq.
   template <class PF, class P>
-  void pack_bwd(std::vector<uint8_t>& blob, std::vector<uint32_t>& tab) const {
-    pack<PF>(true, bwd_fwd_unit_mb<PF>(), false, blob, tab);
+  void pack_bwd(std::vector<uint8_t>& blob, std::vector<uint32_t>& tab, bool coarse = false) const {
+    pack<PF>(!coarse, bwd_fwd_unit_mb<PF>(), false, blob, tab);
     fwd_units = int(tab.size() / 2);
     const int umb = bwd_unit_mb<P>();
-    for (int layer = 0; layer < BW_COUNT; ++layer) {
+    for (int li = 0; li < (coarse ? kBwdCoarseLayers : int(BW_COUNT)); ++li) {
+      const int layer = coarse ? kBwdCoarseSeq[li] : li;
       const LayerShape sh = bwd_layer_shape(layer);
       for (int u0 = 0; u0 < sh.mb; u0 += umb) {
         // units of one or two M-blocks: BW_L5's two d pe M-blocks (4, 5) are staged BEFORE its four d h4 M-blocks — the kernel
@@ -699,6 +701,27 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
       n.in_scale = h->net[1][2][0].in_scale * 1024.f;
       pk.wscale = n.in_scale / kX3ActScale;
       pk.pack_bwd<PrecX3, PrecX3>(blob, tab);
+    }
+    int rc = upload(blob.data(), blob.size(), reinterpret_cast<void**>(&n.blob));
+    if (rc) return rc;
+    rc = upload(tab.data(), tab.size() * 4, reinterpret_cast<void**>(&n.tab));
+    if (rc) return rc;
+    n.n_units = int(tab.size() / 2);
+    n.n_fwd_units = pk.fwd_units;
+  }
+  // the coarse network's gradient blob (dfn_mlp_coarse_points_backward): exact fp32 and split-f16, the latter at the fine gradient
+  // blob's weight scale rule.  Two buffers per precision (blob, unit table): 1 152 000 B + 552 B (fp32: 33 + 36 units) and 1 117 184 B +
+  // 280 B (split-f16: 17 + 18 units), 2.27 MB per handle in all.
+  for (int prec : {int(DFN_PREC_F32), int(DFN_PREC_F16X3)}) {
+    Packer pk{h, "coarse."};
+    std::vector<uint8_t> blob;
+    std::vector<uint32_t> tab;
+    PackedNet& n = h->bwd_coarse[prec];
+    if (prec == DFN_PREC_F32) pk.pack_bwd<PrecF32, PrecF32>(blob, tab, true);
+    else {
+      n.in_scale = h->net[0][2][0].in_scale * 1024.f;
+      pk.wscale = n.in_scale / kX3ActScale;
+      pk.pack_bwd<PrecX3, PrecX3>(blob, tab, true);
     }
     int rc = upload(blob.data(), blob.size(), reinterpret_cast<void**>(&n.blob));
     if (rc) return rc;
@@ -1333,6 +1356,21 @@ extern "C" int dfn_mlp_fine_points_backward(dfn_nerfh_t h, int prec, const float
   const PackedNet& n = h->bwd[prec];
   BwdArgs a{n.blob, n.tab, n.n_units, pts, nullptr, viewdirs, nullptr, table, grad_raw, grad_pts, (long long)n_rows, N, n.in_scale};
   CHECK_HIP(launch_mlp_fine_backward_pts(prec, a, device_cu_count(), HS(stream)), "dfn_mlp_fine_points_backward");
+  return DFN_OK;
+}
+
+// nerfw.py:37-46, 315-334 under autograd: d L / d sigma of the test-time coarse query -> d L / d point.
+extern "C" int dfn_mlp_coarse_points_backward(dfn_nerfh_t h, int prec, const float* pts, size_t n_rows, int N, const float* grad_sigma,
+                                              float* grad_pts, void* stream) {
+  if (int rc = check_net(h, prec, "dfn_mlp_coarse_points_backward", true)) return rc;
+  if (int rc = check_grad_prec(prec, "dfn_mlp_coarse_points_backward")) return rc;
+  if (int rc = check_grad_width(h, "dfn_mlp_coarse_points_backward")) return rc;
+  if (!n_rows) return DFN_OK;
+  if (!pts || !grad_sigma || !grad_pts) return set_error(DFN_ERR_ARG, "dfn_mlp_coarse_points_backward: bad argument (null pointer)");
+  if (int rc = check_points(n_rows, N, "dfn_mlp_coarse_points_backward")) return rc;
+  const PackedNet& n = h->bwd_coarse[prec];
+  BwdArgs a{n.blob, n.tab, n.n_units, pts, nullptr, nullptr, nullptr, nullptr, grad_sigma, grad_pts, (long long)n_rows, N, n.in_scale};
+  CHECK_HIP(launch_mlp_coarse_backward_pts(prec, a, device_cu_count(), HS(stream)), "dfn_mlp_coarse_points_backward");
   return DFN_OK;
 }
 

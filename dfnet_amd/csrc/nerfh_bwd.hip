@@ -26,7 +26,15 @@ namespace dfn {
 // with DFN_BWD_PTS_TU defined and gets the one-pass kernel under the name nerfh_fine_backward_pts_kernel, its inputs loaded from
 // pts [n_rows, n_samples, 3] (BwdArgs::rays_o) instead of being formed as o + d z, and the launcher launch_mlp_fine_backward_pts.
 // What this unit compiles does not change by a token.
-#ifdef DFN_BWD_PTS_TU
+// The COARSE network's input gradient (dfn_mlp_coarse_points_backward) is a third unit: nerfh_bwd_coarse_pts.hip defines DFN_BWD_PTS_TU and
+// DFN_BWD_COARSE_TU and gets nerfh_coarse_backward_pts_kernel / launch_mlp_coarse_backward_pts — the points flavour reduced to what
+// sigma = softplus(static_sigma(h8)) needs: the trunk's forward recompute, static_sigma as a head block of its own (LY_SIG), the seed
+// d sigma_pre = g sigmoid(pre) spread over d h8 by BW_SIG, then BW_L8 .. BW_L1 as below.  BwdArgs::graw is then d L / d sigma, ONE float
+// per point, and BwdArgs::gpts three floats per point.  Every #ifdef DFN_BWD_COARSE_TU below is that unit's alone.
+#if defined(DFN_BWD_COARSE_TU)
+#define DFN_BWD_KERNEL nerfh_coarse_backward_pts_kernel
+#define DFN_LAUNCH_BWD launch_mlp_coarse_backward_pts
+#elif defined(DFN_BWD_PTS_TU)
 #define DFN_BWD_KERNEL nerfh_fine_backward_pts_kernel
 #define DFN_LAUNCH_BWD launch_mlp_fine_backward_pts
 #else
@@ -115,10 +123,17 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) x[nb][c] = add_rn(a.rays_o[ray_of[nb] * 3 + c], mul_rn(a.rays_d[ray_of[nb] * 3 + c], z));
 #endif
+#ifdef DFN_BWD_COARSE_TU
+#pragma unroll
+      for (int c = 0; c < 9; ++c) g[nb][c] = 0.f;
+      g[nb][3] = (h == 0 && pt[nb] < n_pts) ? a.graw[q] : 0.f;   // d L / d sigma, one float per point; no per-ray bias table
+      rb_dir[nb] = rb_tr[nb] = nullptr;
+#else
 #pragma unroll
       for (int c = 0; c < 9; ++c) g[nb][c] = (MODE != 1 && h == 0 && pt[nb] < n_pts) ? a.graw[size_t(q) * 9 + c] : 0.f;
       rb_dir[nb] = a.ray_bias + size_t(ray_of[nb]) * kRayBiasFloats;
       rb_tr[nb] = rb_dir[nb] + kRayBiasFloats / 2;
+#endif
     }
     const float* const norb[NB] = {};
     f32x16 head[NB], carry[NB];
@@ -218,6 +233,15 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
       for (int nb = 0; nb < NB; ++nb) relu_mask<PF, FHC>(hid[nb], mk[7][nb]);
       if constexpr (MODE == 1) { mwords[14 * 64] = mk[7][0][0]; mwords[15 * 64] = mk[7][0][1]; }
     }
+#ifdef DFN_BWD_COARSE_TU
+    // the one head: static_sigma read off h8 (LY_SIG, as the coarse render kernel); its pre-activation gradient seeds the backward pass
+    {
+      FF dummy[NB][FSC];
+      DFN_FLAYER(FHC, 0, true, false, hid, dummy, norb);
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) dsig_true[nb] = h == 0 ? g[nb][3] * bwd_sigmoid<PF, FAST>(head[nb][0]) : 0.f;  // softplus' = sigmoid
+    }
+#else
     // heads; their pre-activation gradients seed the backward pass
     {
       FF fin[NB][FHC], dummy[NB][FSC];
@@ -279,6 +303,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
         }
       }
     }
+#endif
 
     }   // MODE != 2
     if constexpr (MODE == 1) {
@@ -292,6 +317,34 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
     // ------------------------------------------------------------------ backward
     float gx[NB][3], gv[NB][3];
     F gh[NB][HC];
+#ifdef DFN_BWD_COARSE_TU
+    {
+      // d h8 = d sigma_pre . w_sigma as a backward layer of its own: BW_SIG {16 slots, 4 M-blocks}, static_sigma's row the column of
+      // slot 0 of half 0 (Packer::bwd_elem); the lanes of half 1 hold 0 there.
+      // split-f16: d sigma_pre is the chain's ONLY seed, so the per-point scale is taken from it and not from g (sigmoid(pre) may lie
+      // far below 1: the seed's hi / lo halves would leave f16's normal range).  |d sigma_pre| sp in [0.5, 1): the operand sits where
+      // renorm_factor() would put it, and the fine kernel's guard on the density slot (|d sigma| sp 16 < 2^11) holds by
+      // construction, |d sigma_pre| sp 16 < 2^4.  From BW_L8 on the scale is re-centred every other layer as in the fine chain.
+      F dsg[NB][SC];
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        if constexpr (P::kSplit) {
+          sp[nb] = 1.f;
+          float mx = fabsf(dsig_true[nb]);
+          mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+          if (mx > 0.f) {
+            int e;
+            (void)frexpf(mx, &e);
+            sp[nb] = ldexpf(1.f, e < -64 ? 64 : -e);   // scale capped at 2^64, as above
+          }
+        }
+        clear<P>(dsg[nb]);
+        set_slot<P>(dsg[nb], 0, dsig_true[nb] * sp[nb]);
+      }
+      fetch_mk(7);
+      DFN_BLAYER_NT(SC, 4, false, false, dsg, gh, norb);   // BW_SIG
+    }
+#else
     {
       F cat[NB][HC];
       {
@@ -371,6 +424,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
       DFN_BLAYER_NT(HC + SC, 4, false, false, cat2, gh, norb);  // BW_FIN
       if constexpr (P::kSplit) { sp[0] *= st.lane_mul; st.lane_mul = 1.f; }
     }
+#endif
     F gh2[NB][HC];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) apply_mask<P, HC>(gh[nb], mk[7][nb]);
@@ -484,6 +538,16 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
     }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
+#ifdef DFN_BWD_COARSE_TU
+      float o3[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o3[c] = gx[nb][c] + __shfl_xor(gx[nb][c], 32, 64);
+      if (h == 0 && pt[nb] < n_pts) {
+        float* dst = a.gpts + size_t(pt[nb]) * 3;   // d L / d point alone: sigma does not see the view direction
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dst[c] = o3[c];
+      }
+#else
       float o6[6];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
@@ -495,6 +559,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
 #pragma unroll
         for (int c = 0; c < 6; ++c) dst[c] = o6[c];
       }
+#endif
     }
   }
 }

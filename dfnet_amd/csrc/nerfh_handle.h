@@ -27,6 +27,8 @@ struct dfn_nerfh_s {
   PackedNet half_maps;             // kernel variant 6: the split-f16 fine network of the maps flavour (transient head at full height)
   PackedNet bwd[3];                // [prec] fine forward units + backward (W^T) units of the gradient kernel
                                    // (prec 2: split-f16 forward and backward units)
+  PackedNet bwd_coarse[3];         // [prec] coarse forward units + the backward units of kBwdCoarseSeq (dfn_mlp_coarse_points_backward);
+                                   // DFN_PREC_F32 and DFN_PREC_F16X3 only (plain f16 differentiates nothing: stays empty)
   float* extra = nullptr;  // w_dir^T | b_dir | w_tr^T | b_tr | emb_a | emb_t | b_dir + W_dir[:, :W] b_final | b_tr + W_tr[:, :W] b_final
   dfn::RayBiasWeights rb{};
   dfn::RayBiasWeights rb_fold{};   // rb with the two folded bias vectors: the table of kernel variant 5's fine kernel, and of it alone

@@ -161,6 +161,11 @@ constexpr int kBwdTilePoints = 256;  // points per workgroup tile of the split-f
 hipError_t launch_mlp_fine_backward(int prec, const BwdArgs& a, int n_cu, hipStream_t stream, int mode = 0);
 // Its points flavour (nerfh_bwd_pts.hip): a.rays_o is pts [n_rays, n_samples, 3], a.rays_d and a.z are unused; the one-pass form only.
 hipError_t launch_mlp_fine_backward_pts(int prec, const BwdArgs& a, int n_cu, hipStream_t stream, int mode = 0);
+// The coarse network's input gradient, points flavour (nerfh_bwd_coarse_pts.hip: nerfh_coarse_backward_pts_kernel): a.blob = the coarse
+// forward units followed by the backward units of kBwdCoarseSeq, a.rays_o = pts [n_rays, n_samples, 3], a.graw = d L / d sigma
+// [n_rays, n_samples] (ONE float per point), a.gpts = d L / d point [n_rays, n_samples, 3]; a.rays_d, a.viewdirs, a.z and a.ray_bias are
+// unused (sigma depends on the point alone).  The one-pass form only.
+hipError_t launch_mlp_coarse_backward_pts(int prec, const BwdArgs& a, int n_cu, hipStream_t stream, int mode = 0);
 // d L / d raw from d L / d rgb through the fine compositing (test-time, rgb only).  grad_raw_ext [n_rays, Nf, 9] (optional): a
 // gradient that reaches raw directly, added in the same kernel (graw = d raw(compositor) + grad_raw_ext); with grad_rgb == nullptr
 // graw = grad_raw_ext and the scan is skipped.  Without it: the rgb-only kernel, unchanged.

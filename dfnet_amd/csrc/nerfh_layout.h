@@ -269,10 +269,17 @@ enum BwdLayerId {
   BW_L5,         // d h5_pre -> d h4 (128) + M-blocks 4,5: d pe_xyz in positional-encoding slot order
   BW_L4, BW_L3, BW_L2,
   BW_L1,         // d h1_pre -> d pe_xyz (M-blocks 0,1)
-  BW_COUNT
+  BW_COUNT,
+  // the coarse network's gradient kernel only (kBwdCoarseSeq; no part of the fine blob, which packs BW_THEAD .. BW_L1):
+  BW_SIG = BW_COUNT   // d sigma_pre (slot 0 of half 0) -> d h8 (128): static_sigma's row as a column
 };
+// The coarse network's input gradient (nerfh_bwd_coarse_pts.hip): sigma = softplus(static_sigma(h8)), so d h8 is seeded by BW_SIG
+// and the chain is the trunk's.
+constexpr int kBwdCoarseSeq[] = {BW_SIG, BW_L8, BW_L7, BW_L6, BW_L5, BW_L4, BW_L3, BW_L2, BW_L1};
+constexpr int kBwdCoarseLayers = sizeof(kBwdCoarseSeq) / sizeof(int);
 DFN_HD constexpr LayerShape bwd_layer_shape(int id) {
-  return id == BW_THEAD || id == BW_RGB ? LayerShape{16, 2}
+  return id == BW_SIG ? LayerShape{16, 4}
+       : id == BW_THEAD || id == BW_RGB ? LayerShape{16, 2}
        : id <= BW_TE1 ? LayerShape{32, 2}
        : id == BW_FINCAT ? LayerShape{64, 5}
        : id == BW_FIN ? LayerShape{80, 4}

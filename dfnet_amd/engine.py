@@ -275,6 +275,19 @@ class NerfHEngine:
                                                  current_stream()), "dfn_mlp_coarse_points")
         return sigma
 
+    def mlp_coarse_points_backward(self, pts, grad_sigma, precision=None):
+        """d L/d sigma [n, N] of mlp_coarse_points -> d L/d point [n, N, 3] (autograd through nerfw.py:37-46, 315-334; the forward
+        is recomputed inside the gradient kernel).  Netwidth 128, f16x3 or f32."""
+        pts, _, _ = self._point_rows(pts)
+        n, N = pts.shape[:2]
+        grad_sigma = _f32c(grad_sigma).reshape(n, N)
+        gpts = torch.empty(n, N, 3, device=pts.device)
+        for r0, r1 in self._point_chunks(n, N, False) or [(0, 0)]:
+            check(self.lib.dfn_mlp_coarse_points_backward(self.handle, self._prec(precision), ptr(pts[r0:r1]), r1 - r0, N,
+                                                          ptr(grad_sigma[r0:r1]), ptr(gpts[r0:r1]), current_stream()),
+                  "dfn_mlp_coarse_points_backward")
+        return gpts
+
     def mlp_fine_points(self, pts, viewdirs, hist, precision=None):
         """The fine network at the caller's own points: pts [n, N, 3], one view direction [n, 3] and one histogram (hist [1 | n,
         hist_bin]) per row -> raw [n, N, 9] (nerfw.py:62-95)."""

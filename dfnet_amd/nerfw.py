@@ -86,6 +86,23 @@ class _FinePointsFn(torch.autograd.Function):
         return g_pts, g_v, None, None, None
 
 
+class _CoarsePointsFn(torch.autograd.Function):
+    """sigma [R,N] = the coarse network's density at pts [R,N,3]; backward: d L/d pts from d L/d sigma (NerfHEngine.mlp_coarse_points
+    / mlp_coarse_points_backward: the forward is recomputed inside the gradient kernel).  sigma does not see the view direction."""
+
+    @staticmethod
+    def forward(ctx, pts, eng, prec):
+        pts = pts.detach().contiguous().float()
+        ctx.eng, ctx.prec = eng, prec
+        ctx.save_for_backward(pts)
+        return eng.mlp_coarse_points(pts, precision=prec)
+
+    @staticmethod
+    def backward(ctx, g_sigma):
+        pts, = ctx.saved_tensors
+        return ctx.eng.mlp_coarse_points_backward(pts, g_sigma, precision=ctx.prec), None, None
+
+
 class HipQuery:
     """Stands in for the reference's `network_query_fn` lambda (nerfw.py:425-434): carries the engine that evaluates both networks,
     and is callable as the reference's is.
@@ -101,8 +118,12 @@ class HipQuery:
     it raises ValueError (None is accepted).  With grad enabled and `inputs` or `viewdirs` requiring it, typ='fine' is differentiable
     with respect to both (the weights receive no gradient here: that is the training step's job), in fp32-grade arithmetic as
     `render` under autograd: an engine whose precision is plain f16 differentiates in split-f16.
+    typ='coarse' is differentiable on request, as sample_pdf(diff=True) is: with `diff=True`, test_time=True, grad enabled and
+    `inputs` requiring grad, sigma is attached to `inputs` (the coarse network's input-gradient kernel, netwidth 128, the precision
+    rule above; `viewdirs` receives nothing: sigma does not depend on it).  With nothing to track, or under no_grad, diff=True is the
+    plain query; typ='fine' accepts and ignores the keyword.
     Refused with NotImplementedError: typ='coarse' with test_time=False (the 4-channel training query, nerfw.py:47-60), typ='coarse'
-    under autograd, and a netwidth other than 128 or 256 (no register-resident kernels)."""
+    under autograd without diff=True, and a netwidth other than 128 or 256 (no register-resident kernels)."""
 
     def __init__(self, engine, netchunk=65536, trainer=None, modules=None):
         self.engine = engine
@@ -137,7 +158,7 @@ class HipQuery:
                              "engine's own weights (pass None, or the module create_nerf returned)")
 
     def __call__(self, inputs, viewdirs, ts, network_fn=None, typ='fine', embedding_a=None, embedding_t=None, output_transient=True,
-                 test_time=True):
+                 test_time=True, diff=False):
         self.refresh()
         if typ not in ('coarse', 'fine'):
             raise ValueError(f"network_query_fn: typ must be 'coarse' or 'fine', got {typ!r}")
@@ -157,9 +178,12 @@ class HipQuery:
             if not test_time:
                 raise NotImplementedError("network_query_fn: typ='coarse' with test_time=False (the 4-channel training query, "
                                           "nerfw.py:47-60) is not implemented; the training render evaluates it (rendering.render)")
-            if tracked:
-                raise NotImplementedError("network_query_fn: typ='coarse' under autograd is not implemented (the input-gradient "
-                                          "kernel is the fine network's)")
+            if diff and torch.is_grad_enabled() and inputs.requires_grad:
+                sigma = _CoarsePointsFn.apply(pts, eng, "f16x3" if eng.precision in ("f16", "fp16") else eng.precision)
+                return sigma.reshape(lead + (1,))
+            if tracked and not diff:
+                raise NotImplementedError("network_query_fn: typ='coarse' under autograd is opt-in: pass diff=True for sigma attached "
+                                          "to `inputs` (netwidth 128); without it the coarse query builds no graph")
             return eng.mlp_coarse_points(pts.detach()).reshape(lead + (1,))
         if viewdirs is None or ts is None:
             raise ValueError("network_query_fn: typ='fine' needs viewdirs [R, 3] and ts [R | 1, hist_bin]")

@@ -351,6 +351,13 @@ int dfn_mlp_fine_points(dfn_nerfh_t h, int prec, const float* pts, const float* 
 int dfn_mlp_fine_points_backward(dfn_nerfh_t h, int prec, const float* pts, const float* viewdirs, const float* hist,
                                  size_t hist_rows, size_t n_rows, int N, const float* grad_raw, float* grad_pts, void* bias_ws,
                                  void* stream);
+/* cites nerfw.py:37-46, 315-334: autograd through the test-time coarse query into its points.  sigma = softplus(static_sigma(
+ * xyz_encoding_1..8(pe(x)))) depends on the point alone: from pts [n_rows, N, 3] and grad_sigma [n_rows, N] = d L / d sigma to
+ * grad_pts [n_rows, N, 3] = d L / d point, exactly n_rows * N * 3 floats.  One pass (forward recompute recording the ReLU signs, then the
+ * transposed chain), deterministic, no workspace.  Netwidth 128, DFN_PREC_F16X3 or DFN_PREC_F32 (plain f16 and other widths:
+ * DFN_ERR_UNSUPPORTED); n_rows == 0 is DFN_OK, a null pointer DFN_ERR_ARG, n_rows * N below 2^31 as above. */
+int dfn_mlp_coarse_points_backward(dfn_nerfh_t h, int prec, const float* pts, size_t n_rows, int N, const float* grad_sigma,
+                                   float* grad_pts, void* stream);
 
 /* Per-ray reduction of grad_pts [n_rays, Nf, 6] (pts = o + d z, rendering.py:292,305): grad_rays_o = sum g,
  * grad_rays_d = sum z g; with derive_viewdirs != 0 the view-direction part is folded into grad_rays_d through
