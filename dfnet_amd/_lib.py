@@ -122,6 +122,8 @@ SIGNATURES = {
     "dfn_mlp_fine_points": (c_int, [_P, c_int, _P, _P, _P, c_size_t, c_size_t, c_int, _P, _P, _P]),
     "dfn_mlp_fine_points_backward": (c_int, [_P, c_int, _P, _P, _P, c_size_t, c_size_t, c_int, _P, _P, _P, _P]),
     "dfn_mlp_coarse_points_backward": (c_int, [_P, c_int, _P, c_size_t, c_int, _P, _P, _P]),
+    "dfn_mlp_coarse_static_points": (c_int, [_P, c_int, _P, _P, c_size_t, c_int, _P, _P, _P]),
+    "dfn_mlp_coarse_static_points_backward": (c_int, [_P, c_int, _P, _P, c_size_t, c_int, _P, _P, _P, _P]),
     "dfn_ray_grad_reduce": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, _P, _P, _P, _P]),
     "dfn_raygen_backward": (c_int, [c_int, c_int, c_float, _P, _P, _P, _P]),
     "dfn_raygen_frames_backward": (c_int, [c_int, c_int, c_int, c_float, _P, _P, _P, _P]),

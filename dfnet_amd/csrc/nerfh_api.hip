@@ -115,7 +115,8 @@ static void free_packed(dfn_nerfh_s* h) {
         if (n.res_blob) (void)hipFree(n.res_blob);
         n = PackedNet();
       }
-  for (PackedNet* n : {&h->bwd[0], &h->bwd[1], &h->bwd[2], &h->half_maps, &h->bwd_coarse[0], &h->bwd_coarse[1], &h->bwd_coarse[2]}) {
+  for (PackedNet* n : {&h->bwd[0], &h->bwd[1], &h->bwd[2], &h->half_maps, &h->bwd_coarse[0], &h->bwd_coarse[1], &h->bwd_coarse[2],
+                       &h->cstatic[0], &h->cstatic[1], &h->cstatic[2], &h->bwd_cstatic[0], &h->bwd_cstatic[1], &h->bwd_cstatic[2]}) {
     if (n->blob) (void)hipFree(n->blob);
     if (n->tab) (void)hipFree(n->tab);
     *n = PackedNet();
@@ -353,6 +354,11 @@ struct Packer {
         return W(mat("xyz_encoding_5.0"), j, pe_col(mb - 4));
       case BW_L1: return W(mat("xyz_encoding_1.0"), j, pe_col(mb));
       case BW_SIG: return (s == 0 && hh == 0) ? W(mat("static_sigma.0"), 0, k) : 0.f;   // the coarse chain's seed layer
+      case BW_DIRCAT: {   // BW_FINCAT's dir_encoding.0 half: M-blocks 0..3 d final, the 5th d pe_dir (the columns behind the W of `final`)
+        if (mb < 4) return W(mat("dir_encoding.0"), j, k);
+        const int c = pe_dir_feature(mblock_half_of_row(i), mblock_reg_of_row(i));
+        return c >= 0 ? W(mat("dir_encoding.0"), j, kWidth + c) : 0.f;
+      }
       default: {  // BW_L8..BW_L6, BW_L4..BW_L2: 128 -> 128
         const int n = 8 - (layer - BW_L8);
         return W(mat("xyz_encoding_" + std::to_string(n) + ".0"), j, k);
@@ -382,13 +388,14 @@ struct Packer {
   }
   // Blob of the gradient kernel: the fine net's forward layers, one unit per layer (f16) / per M-block (f32),
   // then the backward layers the same way.  coarse: the coarse net's forward layers (kCoarseSeq), then the layers of kBwdCoarseSeq.
+  // stat (with coarse): the coarse net's training query, kCoarseStaticSeq then kBwdCoarseStaticSeq.
   template <class PF, class P>
-  void pack_bwd(std::vector<uint8_t>& blob, std::vector<uint32_t>& tab, bool coarse = false) const {
-    pack<PF>(!coarse, bwd_fwd_unit_mb<PF>(), false, blob, tab);
+  void pack_bwd(std::vector<uint8_t>& blob, std::vector<uint32_t>& tab, bool coarse = false, bool stat = false) const {
+    pack<PF>(!coarse, bwd_fwd_unit_mb<PF>(), false, blob, tab, -1, false, nullptr, stat);
     fwd_units = int(tab.size() / 2);
     const int umb = bwd_unit_mb<P>();
-    for (int li = 0; li < (coarse ? kBwdCoarseLayers : int(BW_COUNT)); ++li) {
-      const int layer = coarse ? kBwdCoarseSeq[li] : li;
+    for (int li = 0; li < (stat ? kBwdCoarseStaticLayers : (coarse ? kBwdCoarseLayers : int(BW_COUNT))); ++li) {
+      const int layer = stat ? kBwdCoarseStaticSeq[li] : (coarse ? kBwdCoarseSeq[li] : li);
       const LayerShape sh = bwd_layer_shape(layer);
       for (int u0 = 0; u0 < sh.mb; u0 += umb) {
         // units of one or two M-blocks: BW_L5's two d pe M-blocks (4, 5) are staged BEFORE its four d h4 M-blocks — the kernel
@@ -418,12 +425,14 @@ struct Packer {
   // res (kernel variant 7, plain units only): the layers of kFineResident / kCoarseResident go there instead, unit after unit in
   // execution order in the same fragment and bias-block format but without the rounding to pieces (nerfh_layout.h: resident_offset);
   // blob and tab then hold the streamed units alone.  The set is zero-padded once to whole pieces.
+  // stat (fine = false, the "coarse." prefix): the coarse network's training query, kCoarseStaticSeq / kCoarseStaticFoldSeq (fold: fold_dir
+  // holds the coarse dir_encoding.0[:, :W] . xyz_encoding_final) with kCoarseStaticGroup.
   template <class P>
   void pack(bool fine, int umb, bool merge, std::vector<uint8_t>& blob, std::vector<uint32_t>& tab, int l5_umb = -1, bool fold = false,
-            std::vector<uint8_t>* res = nullptr) const {
-    const int* seq = fine ? (fold ? kFineFoldSeq : kFineSeq) : kCoarseSeq;
-    const int* grp = fine ? kFineGroup : kCoarseGroup;
-    const int nl = fine ? kFineLayers : kCoarseLayers;
+            std::vector<uint8_t>* res = nullptr, bool stat = false) const {
+    const int* seq = stat ? (fold ? kCoarseStaticFoldSeq : kCoarseStaticSeq) : fine ? (fold ? kFineFoldSeq : kFineSeq) : kCoarseSeq;
+    const int* grp = stat ? kCoarseStaticGroup : fine ? kFineGroup : kCoarseGroup;
+    const int nl = stat ? kCoarseStaticLayers : fine ? kFineLayers : kCoarseLayers;
     if (merge) {
       for (int li = 0; li < nl;) {
         int lj = li;
@@ -586,6 +595,15 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
   }
   const int Wd = h->desc.width;
   std::vector<float> fold_bd, fold_bt;   // netwidth 128: W_dir[:, :W] b_final, W_tr[:, :W] b_final (fold_final)
+  std::vector<float> cfold_bd;           // netwidth 128: the coarse network's W_dir[:, :W] b_final (the training query's folded kernel)
+  auto upload_net = [](PackedNet& n, const std::vector<uint8_t>& blob, const std::vector<uint32_t>& tab) {
+    int rc = upload(blob.data(), blob.size(), reinterpret_cast<void**>(&n.blob));
+    if (rc) return rc;
+    rc = upload(tab.data(), tab.size() * 4, reinterpret_cast<void**>(&n.tab));
+    if (rc) return rc;
+    n.n_units = int(tab.size() / 2);
+    return int(DFN_OK);
+  };
   if (Wd != kWidth && Wd != kMaxWidth) {   // generic-width path only
     h->committed = true;
     return DFN_OK;
@@ -616,6 +634,22 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
         if (rc) return rc;
         n.n_units = int(tab.size() / 2);
       }
+    // the coarse network's training query (dfn_mlp_coarse_static_points), forward only: the plain sequence in the staging units and at
+    // the weight scale of net[0][prec][0].  1 245 184 B (f16, 40 units), 2 488 320 B (fp32, 78 units), 2 488 320 B (split-f16, 78 units)
+    for (int prec = 0; prec < 3; ++prec) {
+      Packer pk{h, "coarse."};
+      std::vector<uint8_t> blob;
+      std::vector<uint32_t> tab;
+      PackedNet& n = h->cstatic[prec];
+      if (prec == DFN_PREC_F16) pk.pack<PrecF16>(false, unit_mb_w256<PrecF16>(), false, blob, tab, -1, false, nullptr, true);
+      else if (prec == DFN_PREC_F32) pk.pack<PrecF32>(false, unit_mb_w256<PrecF32>(), false, blob, tab, -1, false, nullptr, true);
+      else {
+        n.in_scale = h->net[0][prec][0].in_scale;
+        pk.wscale = n.in_scale / kX3ActScale;
+        pk.pack<PrecX3>(false, unit_mb_w256<PrecX3>(), false, blob, tab, -1, false, nullptr, true);
+      }
+      if (int rc = upload_net(n, blob, tab)) return rc;
+    }
   } else {
   for (int f = 0; f < 2; ++f)
     for (int prec = 0; prec < 3; ++prec)
@@ -730,6 +764,44 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
     n.n_units = int(tab.size() / 2);
     n.n_fwd_units = pk.fwd_units;
   }
+  // the coarse network's training query (dfn_mlp_coarse_static_points): the coarse weights along kCoarseStaticSeq in the staging units
+  // of the fine point query's kernels (f16: merged, variant 0's; exact fp32: one M-block; split-f16: PrecX3M16 along
+  // kCoarseStaticFoldSeq, two M-blocks, layer 5 in one-M-block units) at the coarse network's weight scale.  Two buffers per precision
+  // (blob, unit table): 334 848 B + 88 B (f16, 11 units), 688 128 B + 320 B (fp32, 40 units), 603 136 B + 168 B (split-f16, 21 units).
+  for (int prec = 0; prec < 3; ++prec) {
+    Packer pk{h, "coarse."};
+    std::vector<uint8_t> blob;
+    std::vector<uint32_t> tab;
+    PackedNet& n = h->cstatic[prec];
+    if (prec == DFN_PREC_F16) pk.pack<PrecF16>(false, unit_mb<PrecF16>(0), true, blob, tab, -1, false, nullptr, true);
+    else if (prec == DFN_PREC_F32) pk.pack<PrecF32>(false, unit_mb<PrecF32>(0), false, blob, tab, -1, false, nullptr, true);
+    else {
+      n.in_scale = h->net[0][prec][0].in_scale;   // the scan over the "coarse." weights: every coarse network's
+      pk.wscale = n.in_scale / kX3ActScale;
+      fold_final(h->params.at("coarse.dir_encoding.0.weight"), Wd / 2, Wd + kChDir, h->params.at("coarse.xyz_encoding_final.weight"),
+                 h->params.at("coarse.xyz_encoding_final.bias"), Wd, pk.fold_dir, cfold_bd);
+      constexpr int umb = unit_mb<PrecX3M16>(kFoldVariant);
+      pk.pack<PrecX3M16>(false, umb, false, blob, tab, l5_unit_mb_p<PrecX3M16>(umb), true, nullptr, true);
+    }
+    if (int rc = upload_net(n, blob, tab)) return rc;
+  }
+  // ... and its gradient blob (dfn_mlp_coarse_static_points_backward): the plain forward sequence followed by kBwdCoarseStaticSeq, exact
+  // fp32 and split-f16 at the gradient blobs' weight scale rule.  1 387 520 B + 664 B (fp32: 40 + 43 units) and 1 346 560 B + 344 B
+  // (split-f16: 21 + 22 units), 2.73 MB per handle; with the three forward networks above 4.36 MB in all.
+  for (int prec : {int(DFN_PREC_F32), int(DFN_PREC_F16X3)}) {
+    Packer pk{h, "coarse."};
+    std::vector<uint8_t> blob;
+    std::vector<uint32_t> tab;
+    PackedNet& n = h->bwd_cstatic[prec];
+    if (prec == DFN_PREC_F32) pk.pack_bwd<PrecF32, PrecF32>(blob, tab, true, true);
+    else {
+      n.in_scale = h->net[0][2][0].in_scale * 1024.f;
+      pk.wscale = n.in_scale / kX3ActScale;
+      pk.pack_bwd<PrecX3, PrecX3>(blob, tab, true, true);
+    }
+    if (int rc = upload_net(n, blob, tab)) return rc;
+    n.n_fwd_units = pk.fwd_units;
+  }
   }   // netwidth 128
   // per-ray-bias weights: transposed tails of dir_encoding.0 / transient_encoding.0 + embeddings
   const dfn_nerfh_desc& d = h->desc;
@@ -742,8 +814,9 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
   const auto& et = h->params.at("embedding_t.weight");
   std::vector<float> ex;
   const size_t o_wd = 0, o_bd = o_wd + size_t(kd) * NO, o_wt = o_bd + NO, o_bt = o_wt + size_t(nt) * NO,
-               o_ea = o_bt + NO, o_et = o_ea + ea.size(), o_bdf = o_et + et.size(), o_btf = o_bdf + NO;
-  ex.resize(o_btf + NO);
+               o_ea = o_bt + NO, o_et = o_ea + ea.size(), o_bdf = o_et + et.size(), o_btf = o_bdf + NO,
+               o_cwd = o_btf + NO, o_cbd = o_cwd + size_t(kChDir) * NO, o_cbdf = o_cbd + NO;
+  ex.resize(o_cbdf + NO);
   const int ld_d = Wd + kd, ld_t = Wd + nt;
   for (int j = 0; j < kd; ++j)
     for (int f = 0; f < NO; ++f) ex[o_wd + size_t(j) * NO + f] = wd[size_t(f) * ld_d + Wd + j];
@@ -757,6 +830,16 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
   for (int f = 0; f < NO; ++f) {
     ex[o_bdf + f] = fold_bd.empty() ? bd[f] : bd[f] + fold_bd[f];
     ex[o_btf + f] = fold_bt.empty() ? bt[f] : bt[f] + fold_bt[f];
+  }
+  {  // the coarse dir_encoding.0 [W/2, W + 27]: its 27 direction columns transposed, its bias, and the bias of the folded kernel
+    const auto& cwd = h->params.at("coarse.dir_encoding.0.weight");
+    const auto& cbd = h->params.at("coarse.dir_encoding.0.bias");
+    for (int j = 0; j < kChDir; ++j)
+      for (int f = 0; f < NO; ++f) ex[o_cwd + size_t(j) * NO + f] = cwd[size_t(f) * (Wd + kChDir) + Wd + j];
+    for (int f = 0; f < NO; ++f) {
+      ex[o_cbd + f] = cbd[f];
+      ex[o_cbdf + f] = cfold_bd.empty() ? cbd[f] : cbd[f] + cfold_bd[f];
+    }
   }
   int rc = upload(ex.data(), ex.size() * 4, reinterpret_cast<void**>(&h->extra));
   if (rc) return rc;
@@ -774,6 +857,10 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
   h->rb_fold = h->rb;
   h->rb_fold.b_dir = h->extra + o_bdf;
   h->rb_fold.b_tr = h->extra + o_btf;
+  h->rb_cstatic = dfn::RayBiasWeights{h->extra + o_cwd, h->extra + o_cbd, h->extra + o_cwd, h->extra + o_cbd, h->extra + o_ea,
+                                      h->extra + o_et, 0, 1, 1, d.n_vocab, NO};
+  h->rb_cstatic_fold = h->rb_cstatic;
+  h->rb_cstatic_fold.b_dir = h->rb_cstatic_fold.b_tr = h->extra + o_cbdf;
   h->committed = true;
   h->fast = true;
   return DFN_OK;
@@ -1371,6 +1458,47 @@ extern "C" int dfn_mlp_coarse_points_backward(dfn_nerfh_t h, int prec, const flo
   const PackedNet& n = h->bwd_coarse[prec];
   BwdArgs a{n.blob, n.tab, n.n_units, pts, nullptr, nullptr, nullptr, nullptr, grad_sigma, grad_pts, (long long)n_rows, N, n.in_scale};
   CHECK_HIP(launch_mlp_coarse_backward_pts(prec, a, device_cu_count(), HS(stream)), "dfn_mlp_coarse_points_backward");
+  return DFN_OK;
+}
+
+// nerfw.py:47-60, 326-343: the training coarse query of run_network_NeRFW on pre-sampled points, [static_rgb(3), static_sigma] per point.
+// The per-row seed table (b_dir + W_dir[:, W:W+27] . pe_dir(v) of the coarse dir_encoding.0) is written by ray_bias_kernel from a weight
+// set without appearance columns; its "shared histogram" order (hist_rows = 1, nothing to gather) is used for every row count, so a
+// row's seeds do not depend on how the caller chunks the rows.
+extern "C" int dfn_mlp_coarse_static_points(dfn_nerfh_t h, int prec, const float* pts, const float* viewdirs, size_t n_rows, int N,
+                                            float* raw4, void* bias_table, void* stream) {
+  if (int rc = check_net(h, prec, "dfn_mlp_coarse_static_points", true)) return rc;
+  if (!n_rows) return DFN_OK;
+  if (!pts || !viewdirs || !raw4 || !bias_table) return set_error(DFN_ERR_ARG, "dfn_mlp_coarse_static_points: bad argument (null pointer)");
+  if (int rc = check_points(n_rows, N, "dfn_mlp_coarse_static_points")) return rc;
+  float* table = static_cast<float*>(bias_table);
+  const bool fold = prec == DFN_PREC_F16X3 && h->desc.width == kWidth;   // the 16x16x32 kernel with the folded tail
+  CHECK_HIP(launch_ray_bias(fold ? h->rb_cstatic_fold : h->rb_cstatic, viewdirs, nullptr, 1, n_rows, table, HS(stream)),
+            "dfn_mlp_coarse_static_points(ray_bias)");
+  const PackedNet& n = h->cstatic[prec];
+  MlpArgs a{n.blob, n.tab, n.n_units, pts, nullptr, nullptr, table, raw4, nullptr, (long long)n_rows, N, 0.f, 0.f, nullptr, n.in_scale};
+  a.status = range_flag_of(h);
+  CHECK_HIP(fold ? launch_mlp_static_pts_fold(a, device_cu_count(), HS(stream))
+                 : launch_mlp_static_pts(prec, a, device_cu_count(), HS(stream), h->desc.width),
+            "dfn_mlp_coarse_static_points");
+  return DFN_OK;
+}
+
+// ... under autograd: d L / d raw4 -> [d L / d point (3), d L / d viewdir through that point (3)].
+extern "C" int dfn_mlp_coarse_static_points_backward(dfn_nerfh_t h, int prec, const float* pts, const float* viewdirs, size_t n_rows, int N,
+                                                     const float* grad_raw4, float* grad_pts6, void* bias_table, void* stream) {
+  if (int rc = check_net(h, prec, "dfn_mlp_coarse_static_points_backward", true)) return rc;
+  if (int rc = check_grad_prec(prec, "dfn_mlp_coarse_static_points_backward")) return rc;
+  if (int rc = check_grad_width(h, "dfn_mlp_coarse_static_points_backward")) return rc;
+  if (!n_rows) return DFN_OK;
+  if (!pts || !viewdirs || !grad_raw4 || !grad_pts6 || !bias_table)
+    return set_error(DFN_ERR_ARG, "dfn_mlp_coarse_static_points_backward: bad argument (null pointer)");
+  if (int rc = check_points(n_rows, N, "dfn_mlp_coarse_static_points_backward")) return rc;
+  float* table = static_cast<float*>(bias_table);
+  CHECK_HIP(launch_ray_bias(h->rb_cstatic, viewdirs, nullptr, 1, n_rows, table, HS(stream)), "dfn_mlp_coarse_static_points_backward(ray_bias)");
+  const PackedNet& n = h->bwd_cstatic[prec];
+  BwdArgs a{n.blob, n.tab, n.n_units, pts, nullptr, viewdirs, nullptr, table, grad_raw4, grad_pts6, (long long)n_rows, N, n.in_scale};
+  CHECK_HIP(launch_mlp_coarse_static_backward_pts(prec, a, device_cu_count(), HS(stream)), "dfn_mlp_coarse_static_points_backward");
   return DFN_OK;
 }
 

@@ -31,7 +31,20 @@ namespace dfn {
 // sigma = softplus(static_sigma(h8)) needs: the trunk's forward recompute, static_sigma as a head block of its own (LY_SIG), the seed
 // d sigma_pre = g sigmoid(pre) spread over d h8 by BW_SIG, then BW_L8 .. BW_L1 as below.  BwdArgs::graw is then d L / d sigma, ONE float
 // per point, and BwdArgs::gpts three floats per point.  Every #ifdef DFN_BWD_COARSE_TU below is that unit's alone.
-#if defined(DFN_BWD_COARSE_TU)
+// The coarse network's TRAINING query (dfn_mlp_coarse_static_points_backward, nerfw.py:47-60, 326-343) is a fourth unit:
+// nerfh_bwd_coarse_static_pts.hip defines DFN_BWD_PTS_TU and DFN_BWD_CSTATIC_TU and gets nerfh_coarse_static_backward_pts_kernel /
+// launch_mlp_coarse_static_backward_pts -- the points flavour without its transient branch, on the coarse network's blob
+// (kCoarseStaticSeq, then kBwdCoarseStaticSeq): BwdArgs::graw is d L / d raw4, FOUR floats per point (rgb_s, sigma_s), BwdArgs::ray_bias
+// the coarse dir_encoding.0's seed table, BwdArgs::gpts six floats per point.  BW_RGB's output alone enters BW_DIRCAT (BW_FINCAT
+// without its transient half), and in split-f16 the per-point scale is taken from the seeds (the two head derivatives), as the coarse
+// unit takes it.  Every #ifdef DFN_BWD_CSTATIC_TU below is that unit's alone.
+#if defined(DFN_BWD_CSTATIC_TU) && (!defined(DFN_BWD_PTS_TU) || defined(DFN_BWD_COARSE_TU))
+#error "the static query's gradient is a points-flavour unit of its own"
+#endif
+#if defined(DFN_BWD_CSTATIC_TU)
+#define DFN_BWD_KERNEL nerfh_coarse_static_backward_pts_kernel
+#define DFN_LAUNCH_BWD launch_mlp_coarse_static_backward_pts
+#elif defined(DFN_BWD_COARSE_TU)
 #define DFN_BWD_KERNEL nerfh_coarse_backward_pts_kernel
 #define DFN_LAUNCH_BWD launch_mlp_coarse_backward_pts
 #elif defined(DFN_BWD_PTS_TU)
@@ -128,6 +141,13 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
       for (int c = 0; c < 9; ++c) g[nb][c] = 0.f;
       g[nb][3] = (h == 0 && pt[nb] < n_pts) ? a.graw[q] : 0.f;   // d L / d sigma, one float per point; no per-ray bias table
       rb_dir[nb] = rb_tr[nb] = nullptr;
+#elif defined(DFN_BWD_CSTATIC_TU)
+#pragma unroll
+      for (int c = 0; c < 9; ++c) g[nb][c] = 0.f;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) g[nb][c] = (h == 0 && pt[nb] < n_pts) ? a.graw[size_t(q) * 4 + c] : 0.f;   // d L / d (rgb_s, sigma_s)
+      rb_dir[nb] = a.ray_bias + size_t(ray_of[nb]) * kRayBiasFloats;   // table 0 alone: the coarse network has no transient table
+      rb_tr[nb] = nullptr;
 #else
 #pragma unroll
       for (int c = 0; c < 9; ++c) g[nb][c] = (MODE != 1 && h == 0 && pt[nb] < n_pts) ? a.graw[size_t(q) * 9 + c] : 0.f;
@@ -144,6 +164,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       sp[nb] = 1.f;
+#ifndef DFN_BWD_CSTATIC_TU   // the static query's unit takes the scale from its seeds, behind the heads
       if constexpr (P::kSplit) {
         float mx = 0.f;
 #pragma unroll
@@ -155,6 +176,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
           sp[nb] = ldexpf(1.f, e < -64 ? 64 : -e);     // max |d raw| * sp in [0.5, 1) (scale capped at 2^64)
         }
       }
+#endif
     }
     st.lane_mul = 1.f;
 
@@ -258,6 +280,34 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
         for (int nb = 0; nb < NB; ++nb) relu_mask<PF, FQC>(de[nb], md[nb]);
         if constexpr (MODE == 1) mwords[16 * 64] = md[0][0];
         DFN_FLAYER(FQC, 0, true, false, de, dummy, norb);  // static_rgb
+#ifdef DFN_BWD_CSTATIC_TU
+        // the chain's seeds are the two head derivatives, d rgb_pre = g y (1 - y) and d sigma_pre = g sigmoid(pre).  split-f16: the
+        // per-point scale is taken from THEM and not from g (y (1 - y) and sigmoid(pre) may lie far below 1: the seeds' hi / lo halves
+        // would leave f16's normal range), max |seed| sp in [0.5, 1), as nerfh_coarse_backward_pts_kernel takes it from its one seed.
+        // The density seed joins at BW_FIN's slot 64 under the guard in front of BW_DIRCAT below, |d sigma_pre| sp 16 < 2^11.
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+          float seed[3];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float y = bwd_sigmoid<PF, FAST>(head[nb][c]);
+            seed[c] = h == 0 ? g[nb][c] * y * (1.f - y) : 0.f;
+          }
+          if constexpr (P::kSplit) {
+            sp[nb] = 1.f;
+            float mx = fmaxf(fmaxf(fabsf(seed[0]), fabsf(seed[1])), fmaxf(fabsf(seed[2]), fabsf(dsig_true[nb])));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            if (mx > 0.f) {
+              int e;
+              (void)frexpf(mx, &e);
+              sp[nb] = ldexpf(1.f, e < -64 ? 64 : -e);   // scale capped at 2^64, as above
+            }
+          }
+          clear<P>(drgb[nb]);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) set_slot<P>(drgb[nb], c, seed[c] * sp[nb]);
+        }
+#else
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
           clear<P>(drgb[nb]);
@@ -268,7 +318,9 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
             set_slot<P>(drgb[nb], c, h == 0 ? g[nb][c] * y * (1.f - y) * sp[nb] : 0.f);
           }
         }
+#endif
       }
+#ifndef DFN_BWD_CSTATIC_TU
       {
         FF t0[NB][FQC], t1[NB][FQC];
         DFN_FLAYER_R(FHC, 2, false, true, fin, t0, rb_tr);
@@ -302,6 +354,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
           set_slot<P>(dth[nb], 4, h == 0 ? g[nb][8] * bwd_sigmoid<PF, FAST>(head[nb][4]) * sp[nb] : 0.f);
         }
       }
+#endif
     }
 #endif
 
@@ -346,6 +399,20 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
     }
 #else
     {
+#ifdef DFN_BWD_CSTATIC_TU
+      F cat[NB][QC];   // d dir_pre alone
+      {
+        F g1[NB][QC];
+        fetch_md();
+        DFN_BLAYER_NT(SC, 2, false, false, drgb, g1, norb);  // BW_RGB
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+          apply_mask<P, QC>(g1[nb], md[nb]);
+#pragma unroll
+          for (int i = 0; i < QC; ++i) cat[nb][i] = g1[nb][i];
+        }
+      }
+#else
       F cat[NB][HC];
       {
         F g0[NB][QC], g1[NB][QC];
@@ -374,11 +441,16 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
           for (int i = 0; i < QC; ++i) { cat[nb][i] = g0[nb][i]; cat[nb][QC + i] = g1[nb][i]; }
         }
       }
+#endif
       F cat2[NB][HC + SC];
       {
         F dfin[NB][HC];
         if constexpr (P::kSplit) {
+#ifdef DFN_BWD_CSTATIC_TU
+          st.lane_mul = renorm_factor<P, QC>(cat[0], sp[0], &st.rmax);
+#else
           st.lane_mul = renorm_factor<P, HC>(cat[0], sp[0], &st.rmax);   // the two branches share sp up to here
+#endif
           // d sigma_s joins the chain after this layer (slot 64 of BW_FIN's input) at the scale chosen HERE: when the colour /
           // transient gradients of a point are orders of magnitude below its density gradient (near-duplicate samples: alpha ~ 0)
           // a factor chosen from them alone overflowed that slot's f16 halves (inf -> NaN for the whole ray).  Keep
@@ -391,7 +463,11 @@ __global__ __launch_bounds__(WAVES * 64, 1) void DFN_BWD_KERNEL(BwdArgs a) {
             st.lane_mul *= ldexpf(1.f, 11 - e);
           }
         }
+#ifdef DFN_BWD_CSTATIC_TU
+        DFN_BLAYER_NT(QC, 4, true, false, cat, dfin, norb);  // BW_DIRCAT: d final + (head) d pe_dir
+#else
         DFN_BLAYER_NT(HC, 4, true, false, cat, dfin, norb);  // BW_FINCAT: d final + (head) d pe_dir
+#endif
         if constexpr (P::kSplit) { sp[0] *= st.lane_mul; st.lane_mul = 1.f; }
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {

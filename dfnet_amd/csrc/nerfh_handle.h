@@ -29,9 +29,17 @@ struct dfn_nerfh_s {
                                    // (prec 2: split-f16 forward and backward units)
   PackedNet bwd_coarse[3];         // [prec] coarse forward units + the backward units of kBwdCoarseSeq (dfn_mlp_coarse_points_backward);
                                    // DFN_PREC_F32 and DFN_PREC_F16X3 only (plain f16 differentiates nothing: stays empty)
+  PackedNet cstatic[3];            // [prec] the coarse network along kCoarseStaticSeq (split-f16 at netwidth 128: kCoarseStaticFoldSeq, PrecX3M16):
+                                   // dfn_mlp_coarse_static_points
+  PackedNet bwd_cstatic[3];        // [prec] its forward units (plain sequence) + the backward units of kBwdCoarseStaticSeq
+                                   // (dfn_mlp_coarse_static_points_backward); netwidth 128, DFN_PREC_F32 and DFN_PREC_F16X3 only
   float* extra = nullptr;  // w_dir^T | b_dir | w_tr^T | b_tr | emb_a | emb_t | b_dir + W_dir[:, :W] b_final | b_tr + W_tr[:, :W] b_final
+                           // | coarse w_dir^T [27][W/2] | coarse b_dir | coarse b_dir + W_dir[:, :W] b_final
   dfn::RayBiasWeights rb{};
   dfn::RayBiasWeights rb_fold{};   // rb with the two folded bias vectors: the table of kernel variant 5's fine kernel, and of it alone
+  // the COARSE dir_encoding.0's seeds (the training query): 27 direction columns, no appearance columns (hist_bin = 0), no transient
+  // table (b_tr = b_dir: table 1 is written and never read); _fold: with the folded bias, the table of the split-f16 kernel at netwidth 128
+  dfn::RayBiasWeights rb_cstatic{}, rb_cstatic_fold{};
   bool fast = false;       // the register-resident MFMA kernels are packed (netwidth == dfn::kWidth)
   // Generic-width path (nerfh_train_api.hip): every parameter as a plain row-major fp32 device tensor, in the canonical
   // order of dfn_nerfh_train_param_name(); one allocation.

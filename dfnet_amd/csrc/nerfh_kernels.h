@@ -73,6 +73,13 @@ hipError_t launch_mlp_hoist(bool fine, const MlpDynArgs& a, int n_cu, hipStream_
 hipError_t launch_mlp_pts(bool fine, int prec, const MlpArgs& a, int n_cu, hipStream_t stream, int width = 128);
 hipError_t launch_mlp_pts_fold(const MlpArgs& a, int n_cu, hipStream_t stream);
 hipError_t launch_mlp_pts_half(const MlpArgs& a, int n_cu, hipStream_t stream);
+// The coarse network's training query on points (nerfh_mlp_static_pts*.hip, nerfw.py:47-60): the fine points kernel cut off behind
+// static_rgb.  a as for the points flavour; a.blob = the coarse network packed along kCoarseStaticSeq (launch_mlp_static_pts: f16 /
+// exact fp32 at netwidth 128, netwidth 256) or kCoarseStaticFoldSeq (launch_mlp_static_pts_fold: split-f16 at netwidth 128);
+// a.ray_bias = one row of ray_bias_floats(W) floats per query row whose table 0 holds b_dir + W_dir[:, W:W+27] . pe_dir(v) of the
+// COARSE dir_encoding.0 (the folded kernel: + W_dir[:, :W] . b_final), table 1 is not read; a.out = raw4 [n_rays, n_samples, 4].
+hipError_t launch_mlp_static_pts(int prec, const MlpArgs& a, int n_cu, hipStream_t stream, int width = 128);
+hipError_t launch_mlp_static_pts_fold(const MlpArgs& a, int n_cu, hipStream_t stream);
 
 // --- stages (nerfh_stages.hip)
 // (frames > 1: c2w [frames,3,4], outputs [frames,H,W,3] — one launch for the frames of a mini-batch)
@@ -166,6 +173,12 @@ hipError_t launch_mlp_fine_backward_pts(int prec, const BwdArgs& a, int n_cu, hi
 // [n_rays, n_samples] (ONE float per point), a.gpts = d L / d point [n_rays, n_samples, 3]; a.rays_d, a.viewdirs, a.z and a.ray_bias are
 // unused (sigma depends on the point alone).  The one-pass form only.
 hipError_t launch_mlp_coarse_backward_pts(int prec, const BwdArgs& a, int n_cu, hipStream_t stream, int mode = 0);
+// The input gradient of the coarse network's training query, points flavour (nerfh_bwd_coarse_static_pts.hip:
+// nerfh_coarse_static_backward_pts_kernel): a.blob = the coarse network's forward units along kCoarseStaticSeq followed by the backward
+// units of kBwdCoarseStaticSeq, a.rays_o = pts [n_rays, n_samples, 3], a.viewdirs [n_rays, 3], a.ray_bias = the coarse dir_encoding.0's
+// seed table (launch_mlp_static_pts's, unfolded), a.graw = d L / d raw4 [n_rays, n_samples, 4], a.gpts [n_rays, n_samples, 6] as the
+// fine kernel's; a.rays_d and a.z are unused.  The one-pass form only.
+hipError_t launch_mlp_coarse_static_backward_pts(int prec, const BwdArgs& a, int n_cu, hipStream_t stream, int mode = 0);
 // d L / d raw from d L / d rgb through the fine compositing (test-time, rgb only).  grad_raw_ext [n_rays, Nf, 9] (optional): a
 // gradient that reaches raw directly, added in the same kernel (graw = d raw(compositor) + grad_raw_ext); with grad_rgb == nullptr
 // graw = grad_raw_ext and the scan is skipped.  Without it: the rgb-only kernel, unchanged.

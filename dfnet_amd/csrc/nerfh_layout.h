@@ -76,6 +76,27 @@ constexpr int kCoarseGroup[] = {0, 1, 2, 3, 4, 5, 6, 7, 7};
 constexpr int kFineGroup[] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 10, 10, 10, 10, 10};
 constexpr int kCoarseLayers = sizeof(kCoarseSeq) / sizeof(int);
 constexpr int kFineLayers = sizeof(kFineSeq) / sizeof(int);
+// The coarse network's TRAINING query (nerfw.py:47-60, 326-343: the output_transient=False branch, [static_rgb(3), static_sigma]): the
+// fine sequence cut off behind static_rgb, on the coarse network's weights -- dir_encoding.0 there is [W/2, W + 27] (no appearance
+// columns), which LY_DIR / LY_DIRF read through the matrix's own leading dimension (Packer::mat).  Plain (f16, exact fp32, netwidth 256)
+// and folded (split-f16 at netwidth 128, as kFineFoldSeq); the group table is kFineGroup's head.  nerfh_mlp_static_pts*.hip.
+constexpr int kCoarseStaticSeq[] = {LY_L1, LY_L2, LY_L3, LY_L4, LY_L5, LY_L6, LY_L7, LY_L8, LY_FIN, LY_DIR, LY_RGB};
+constexpr int kCoarseStaticFoldSeq[] = {LY_L1, LY_L2, LY_L3, LY_L4, LY_L5, LY_L6, LY_L7, LY_L8, LY_SIG, LY_DIRF, LY_RGB};
+constexpr int kCoarseStaticGroup[] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9};
+constexpr int kCoarseStaticLayers = sizeof(kCoarseStaticSeq) / sizeof(int);
+static_assert(sizeof(kCoarseStaticFoldSeq) == sizeof(kCoarseStaticSeq) && sizeof(kCoarseStaticGroup) == sizeof(kCoarseStaticSeq),
+              "one entry per layer of the static sequence");
+// (M-block, 8-slot K-chunk) pairs of a sequence: x 1 (f16), x 3 (split-f16 32x32x16) or x 6 (split-f16 16x16x32) MFMAs per 32-point
+// block -- the fine sequences give the 2 160 / 1 968 of "Kernel variants" below.  What the expected time ratio of two kernels on the
+// same geometry is computed from: static 316 / fine 360 = 0.878 plain, 284 / 328 = 0.866 folded.
+DFN_HD constexpr int seq_chunks(const int* seq, int n, int W = kWidth) {
+  int c = 0;
+  for (int i = 0; i < n; ++i) c += layer_shape(seq[i], W).slots / 8 * layer_shape(seq[i], W).mb;
+  return c;
+}
+static_assert(seq_chunks(kFineSeq, kFineLayers) == 360 && seq_chunks(kFineFoldSeq, kFineLayers) == 328 &&
+              seq_chunks(kCoarseStaticSeq, kCoarseStaticLayers) == 316 && seq_chunks(kCoarseStaticFoldSeq, kCoarseStaticLayers) == 284,
+              "MFMA chunk counts of the sequences");
 
 // Feature index (within a 128- or 64-wide hidden vector) held in slot s of half h when the
 // vector was produced by M-blocks of a previous layer.
@@ -271,14 +292,21 @@ enum BwdLayerId {
   BW_L1,         // d h1_pre -> d pe_xyz (M-blocks 0,1)
   BW_COUNT,
   // the coarse network's gradient kernel only (kBwdCoarseSeq; no part of the fine blob, which packs BW_THEAD .. BW_L1):
-  BW_SIG = BW_COUNT   // d sigma_pre (slot 0 of half 0) -> d h8 (128): static_sigma's row as a column
+  BW_SIG = BW_COUNT,  // d sigma_pre (slot 0 of half 0) -> d h8 (128): static_sigma's row as a column
+  // the coarse network's training query (kBwdCoarseStaticSeq), behind BW_SIG so that no index of the blobs above moves:
+  BW_DIRCAT           // d dir_pre (64) -> d final (128) + 5th M-block: d pe_dir (27, pe_dir_feature()): BW_FINCAT without its transient half
 };
 // The coarse network's input gradient (nerfh_bwd_coarse_pts.hip): sigma = softplus(static_sigma(h8)), so d h8 is seeded by BW_SIG
 // and the chain is the trunk's.
 constexpr int kBwdCoarseSeq[] = {BW_SIG, BW_L8, BW_L7, BW_L6, BW_L5, BW_L4, BW_L3, BW_L2, BW_L1};
 constexpr int kBwdCoarseLayers = sizeof(kBwdCoarseSeq) / sizeof(int);
+// The input gradient of the coarse network's training query (nerfh_bwd_coarse_static_pts.hip): raw4 = [sigmoid(static_rgb), softplus(static_sigma)],
+// the fine chain without its transient branch, on the coarse network's weights.
+constexpr int kBwdCoarseStaticSeq[] = {BW_RGB, BW_DIRCAT, BW_FIN, BW_L8, BW_L7, BW_L6, BW_L5, BW_L4, BW_L3, BW_L2, BW_L1};
+constexpr int kBwdCoarseStaticLayers = sizeof(kBwdCoarseStaticSeq) / sizeof(int);
 DFN_HD constexpr LayerShape bwd_layer_shape(int id) {
   return id == BW_SIG ? LayerShape{16, 4}
+       : id == BW_DIRCAT ? LayerShape{32, 5}
        : id == BW_THEAD || id == BW_RGB ? LayerShape{16, 2}
        : id <= BW_TE1 ? LayerShape{32, 2}
        : id == BW_FINCAT ? LayerShape{64, 5}

@@ -40,7 +40,13 @@ namespace dfn {
 //   DFN_MLP_HOIST_TU  variant 10, on PE: the fine kernel's per-ray seeds are stored at the accumulators' scale (layer(): RAYBIAS takes
 //                     them as loaded) and uniform values are formed at their use (wave_here / args_here below, stage_issue_at),
 //                     MlpDynArgs; the unit has no coarse kernel (variant 9's runs)
-// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn|_pe|_hoist][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn|_pe|_hoist].
+//   DFN_MLP_STATIC_TU the coarse network's training query (nerfw.py:47-60, 326-343), on PTS, plain or FOLD: the fine kernel cut off
+//                     behind static_rgb (kCoarseStaticSeq / kCoarseStaticFoldSeq), 4 floats per point; the unit has that kernel alone
+// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn|_pe|_hoist][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn|_pe|_hoist];
+// DFN_MLP_STATIC_TU: nerfh_coarse_static[_fold]_pts_kernel, launch_mlp_static_pts[_fold].
+#if defined(DFN_MLP_STATIC_TU) && (!defined(DFN_MLP_PTS_TU) || defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_MAPS_TU))
+#error "the static query exists in the points flavour, plain or folded"
+#endif
 #if defined(DFN_MLP_RES_TU) && (!defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_PTS_TU))
 #error "the resident layers exist in the half-height render kernels"
 #endif
@@ -94,6 +100,12 @@ namespace dfn {
 #define DFN_COARSE_KERNEL DFN_PASTE4(nerfh_coarse, DFN_TU_TAG, DFN_TU_PTS, _kernel)
 #endif
 #define DFN_LAUNCH_MLP DFN_PASTE4(launch_mlp, DFN_TU_MAPS, DFN_TU_PTS, DFN_TU_TAG)
+#ifdef DFN_MLP_STATIC_TU   // the truncated fine kernel under a name of its own
+#undef DFN_FINE_KERNEL
+#undef DFN_LAUNCH_MLP
+#define DFN_FINE_KERNEL DFN_PASTE4(nerfh_coarse_static, DFN_TU_TAG, DFN_TU_PTS, _kernel)
+#define DFN_LAUNCH_MLP DFN_PASTE4(launch_mlp_static, DFN_TU_MAPS, DFN_TU_PTS, DFN_TU_TAG)
+#endif
 #ifdef DFN_MLP_MAPS_TU
 constexpr bool kMapsTU = true;
 #else
@@ -452,6 +464,30 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       const float* rb_dir[LP];
       ray_table(rb_dir, 0);
       layer<P, UMB, PIPE, NB, HC, MBQ, true, false, true, true, -1, true, CY>(st, smem, fin, de, head, rb_dir, carry);
+#ifdef DFN_MLP_STATIC_TU
+      // The next tile's points, prefetched by LDS-DMA as in the fine kernel, whose place for it (behind transient_encoding.0's mid_sync)
+      // does not exist here: behind dir_encoding.0's.  In the merged layout (f16: kCoarseStaticGroup puts static_rgb into this unit)
+      // that is the tile's LAST mid_sync, so nothing waits for these loads before the tile's end.  In the one- and two-M-block layouts
+      // static_rgb opens a unit and its mid_sync's vmcnt(0) covers them together with the weight DMA this unit's mid_sync issued just
+      // before them -- what transient_encoding.2's mid_sync does in the fine kernel; no wait in front of a weight DMA is added.
+      // layer()'s read-hazard counts for the pair around it: dir_encoding.0 hands its last M-block to static_rgb in `carry` (COUT ->
+      // CIN = 2), exactly the pair the fine kernel runs back to back.  The counts there are MFMA issues between an accumulator's last
+      // write and the conversion piece that reads it, all of them inside the two layer() bodies; the loads here are VMEM / SALU
+      // instructions between the bodies, which add wait states and take no MFMA issue away, and the branch around them is
+      // wave-uniform (st.more).  The fine kernel has the same block between a COUT layer and a CIN = 2 layer (t0 -> t1).
+      static_assert(!MAPS && !MASKS, "the static query has no maps and saves no masks");
+      if (st.more) {
+        const uint32_t base = uint32_t(DFN_NEXT_TILE) * uint32_t(PPT) + st.wave * (NB * 32);
+        char* slot = smem + ring_slots<P, W>() * USTRIDE + st.wave * (PF_ROUNDS * 8 * 256);
+#pragma unroll
+        for (int r = 0; r < PF_ROUNDS; ++r) {
+          const uint32_t ptn = base + r * 64 + st.lane;
+          const uint32_t q = ptn < npts ? ptn : npts - 1;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) lds_dma_b32(a.rays_o + size_t(q) * 3 + c, slot + (r * 8 + c) * 256);
+        }
+      }
+#endif
       layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE && R_RGB < 0, (CY ? 2 : -1), true, false, false, false, true, kHalfHeads, R_RGB>(st, smem, de, dummy, head, norb, carry);
       sign64(16, de[0]);
 #pragma unroll
@@ -459,6 +495,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[nb][c] = head_sigmoid<P, FAST>(head[nb][c]);
     }
+#ifndef DFN_MLP_STATIC_TU   // the static query ends behind static_rgb
     // transient branch
     {
       F t0[NB][QC], t1[NB][QC], dummy[NB][chunks_of<P>(16)];
@@ -510,6 +547,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
         else o[nb][8] = head_softplus<P, FAST>(head[nb][4]);  // C register 4 of half 0 = row 8 = transient_beta
       }
     }
+#endif
     // the lane's own sample (sample p on lane p of half 0, as the heads): PrecX3M16 lane 16 g + (l & 15) carries it as point n = g & 1
 #ifdef DFN_MLP_PTS_TU
     // points have no depths: the raw store below is the only epilogue (launch_mlp_pts refuses a.partial)
@@ -606,9 +644,15 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
         if (h == 0 && pt_own[nb] < npts) {
+#ifdef DFN_MLP_STATIC_TU
+          float* dst = a.out + (size_t)pt_own[nb] * 4;   // raw4 = (rgb_s, sigma_s); no alignment beyond a float's is asked of the caller
+#pragma unroll
+          for (int c = 0; c < 4; ++c) dst[c] = o[nb][c];
+#else
           float* dst = a.out + (size_t)pt_own[nb] * 9;
 #pragma unroll
           for (int c = 0; c < 9; ++c) dst[c] = o[nb][c];
+#endif
         }
     }
     if (st.more) {  // pick up the prefetched inputs of the next tile (this wave's own LDS slot: no barrier needed)
@@ -689,7 +733,30 @@ static hipError_t launch_pts_one(const MlpArgs& a, int n_cu, hipStream_t stream)
   static bool attr_done = false;
   return launch_tiles<MlpArgs, WAVES * NB * 32, 1, WAVES>(kern, attr_done, lds_bytes<P, UMB, WAVES, NB, W>(), a, n_cu, stream);
 }
-#if defined(DFN_MLP_HALF_TU)
+#if defined(DFN_MLP_STATIC_TU)
+// The coarse network's training query: the geometries of the fine point query per (arithmetic, width), on the networks packed along
+// kCoarseStaticSeq / kCoarseStaticFoldSeq; a.ray_bias = the coarse dir_encoding.0's seed table (one row per query row, table 0 only).
+#if defined(DFN_MLP_FOLD_TU)
+// launch_mlp_static_pts_fold: split-f16, netwidth 128 (PrecX3M16, the folded tail)
+hipError_t DFN_LAUNCH_MLP(const MlpArgs& a, int n_cu, hipStream_t stream) {
+  if (!a.ray_bias) return hipErrorInvalidValue;
+  return launch_pts_one<PM, false, kMWaves, kMUmb, kMNb, true, kWidth, true>(a, n_cu, stream);
+}
+#else
+// launch_mlp_static_pts: f16 and exact fp32 at netwidth 128, the three plain kernels of netwidth 256
+hipError_t DFN_LAUNCH_MLP(int prec, const MlpArgs& a, int n_cu, hipStream_t stream, int width) {
+  if (!a.ray_bias) return hipErrorInvalidValue;
+  if (width == 256) {
+    if (prec == 0) return launch_pts_one<PrecF16, true, 8, unit_mb_w256<PrecF16>(), 1, false, 256, true>(a, n_cu, stream);
+    if (prec == 2) return launch_pts_one<PrecX3, false, 4, unit_mb_w256<PrecX3>(), 1, false, 256, true>(a, n_cu, stream);
+    return launch_pts_one<PrecF32, false, 4, unit_mb_w256<PrecF32>(), 1, false, 256, true>(a, n_cu, stream);
+  }
+  if (width != kWidth || prec == 2) return hipErrorInvalidValue;   // split-f16 at netwidth 128: launch_mlp_static_pts_fold
+  if (prec == 0) return launch_pts_one<PrecF16, true, 8, 8, 2, true, kWidth, true>(a, n_cu, stream);
+  return launch_pts_one<PrecF32, false, 8, 1, 1, false, kWidth, true>(a, n_cu, stream);
+}
+#endif
+#elif defined(DFN_MLP_HALF_TU)
 // launch_mlp_pts_half: split-f16, netwidth 128, coarse: variant 6's half-height kernel on net[0][F16X3][6]
 hipError_t DFN_LAUNCH_MLP(const MlpArgs& a, int n_cu, hipStream_t stream) {
   return launch_pts_one<PM, false, kMWaves, kMUmb, kMNb, true, kWidth, false>(a, n_cu, stream);

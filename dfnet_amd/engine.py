@@ -288,6 +288,38 @@ class NerfHEngine:
                   "dfn_mlp_coarse_points_backward")
         return gpts
 
+    def mlp_coarse_static_points(self, pts, viewdirs, precision=None):
+        """The coarse network's training query at the caller's own points: pts [n, N, 3] and one view direction [n, 3] per row ->
+        raw [n, N, 4] = (static_rgb, static_sigma) (nerfw.py:47-60, 326-343).  Rows are chunked as the fine query's."""
+        pts, viewdirs, _ = self._point_rows(pts, viewdirs)
+        if viewdirs is None:
+            raise ValueError("mlp_coarse_static_points needs viewdirs [rows, 3]")
+        n, N = pts.shape[:2]
+        raw = torch.empty(n, N, 4, device=pts.device)
+        for r0, r1 in self._point_chunks(n, N, True) or [(0, 0)]:
+            bias = torch.empty(self.lib.dfn_fine_bias_bytes(r1 - r0), dtype=torch.uint8, device=pts.device)
+            check(self.lib.dfn_mlp_coarse_static_points(self.handle, self._prec(precision), ptr(pts[r0:r1]), ptr(viewdirs[r0:r1]), r1 - r0,
+                                                        N, ptr(raw[r0:r1]), ctypes.c_void_p(bias.data_ptr()), current_stream()),
+                  "dfn_mlp_coarse_static_points")
+        return raw
+
+    def mlp_coarse_static_points_backward(self, pts, viewdirs, grad_raw, precision=None):
+        """d L/d raw [n, N, 4] of mlp_coarse_static_points -> [n, N, 6]: d L/d point (3) and d L/d viewdir through that point (3).
+        Netwidth 128, f16x3 or f32."""
+        pts, viewdirs, _ = self._point_rows(pts, viewdirs)
+        if viewdirs is None:
+            raise ValueError("mlp_coarse_static_points_backward needs viewdirs [rows, 3]")
+        n, N = pts.shape[:2]
+        grad_raw = _f32c(grad_raw).reshape(n, N, 4)
+        gpts = torch.empty(n, N, 6, device=pts.device)
+        for r0, r1 in self._point_chunks(n, N, True) or [(0, 0)]:
+            bias = torch.empty(self.lib.dfn_fine_bias_bytes(r1 - r0), dtype=torch.uint8, device=pts.device)
+            check(self.lib.dfn_mlp_coarse_static_points_backward(self.handle, self._prec(precision), ptr(pts[r0:r1]), ptr(viewdirs[r0:r1]),
+                                                                 r1 - r0, N, ptr(grad_raw[r0:r1]), ptr(gpts[r0:r1]),
+                                                                 ctypes.c_void_p(bias.data_ptr()), current_stream()),
+                  "dfn_mlp_coarse_static_points_backward")
+        return gpts
+
     def mlp_fine_points(self, pts, viewdirs, hist, precision=None):
         """The fine network at the caller's own points: pts [n, N, 3], one view direction [n, 3] and one histogram (hist [1 | n,
         hist_bin]) per row -> raw [n, N, 9] (nerfw.py:62-95)."""

@@ -103,6 +103,27 @@ class _CoarsePointsFn(torch.autograd.Function):
         return ctx.eng.mlp_coarse_points_backward(pts, g_sigma, precision=ctx.prec), None, None
 
 
+class _CoarseStaticPointsFn(torch.autograd.Function):
+    """raw [R,N,4] = (static_rgb, static_sigma) of the coarse network's training query at pts [R,N,3] with one view direction per row;
+    backward: d L/d pts and d L/d viewdirs from d L/d raw (NerfHEngine.mlp_coarse_static_points / mlp_coarse_static_points_backward:
+    the forward is recomputed inside the gradient kernel).  The weights receive nothing."""
+
+    @staticmethod
+    def forward(ctx, pts, viewdirs, eng, prec):
+        pts, viewdirs = pts.detach().contiguous().float(), viewdirs.detach().contiguous().float()
+        ctx.eng, ctx.prec = eng, prec
+        ctx.save_for_backward(pts, viewdirs)
+        return eng.mlp_coarse_static_points(pts, viewdirs, precision=prec)
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        pts, viewdirs = ctx.saved_tensors
+        g = ctx.eng.mlp_coarse_static_points_backward(pts, viewdirs, g_raw, precision=ctx.prec)
+        g_pts = g[..., :3].contiguous() if ctx.needs_input_grad[0] else None
+        g_v = g[..., 3:].sum(dim=1) if ctx.needs_input_grad[1] else None   # one view direction per row of points
+        return g_pts, g_v, None, None
+
+
 class HipQuery:
     """Stands in for the reference's `network_query_fn` lambda (nerfw.py:425-434): carries the engine that evaluates both networks,
     and is callable as the reference's is.
@@ -112,6 +133,7 @@ class HipQuery:
     not only samples of a ray), one view direction per row of N points (viewdirs [R, 3]) and one histogram per row or one for all
     (ts [R | 1, hist_bin]).  The result keeps the leading shape of `inputs`:
       typ='coarse', test_time=True          sigma [..., N, 1]            (nerfw.py:37-46)
+      typ='coarse', test_time=False, static=True   raw [..., N, 4] = (static_rgb, static_sigma), the training query (nerfw.py:47-60)
       typ='fine',   output_transient=True   raw   [..., N, 9]            (nerfw.py:62-95)
       typ='fine',   output_transient=False  raw[..., :4] = (static_rgb, static_sigma), the four values the reference concatenates
     The networks are the ones packed into the engine: a `network_fn` / `embedding_a` / `embedding_t` that is not the module behind
@@ -122,8 +144,15 @@ class HipQuery:
     `inputs` requiring grad, sigma is attached to `inputs` (the coarse network's input-gradient kernel, netwidth 128, the precision
     rule above; `viewdirs` receives nothing: sigma does not depend on it).  With nothing to track, or under no_grad, diff=True is the
     plain query; typ='fine' accepts and ignores the keyword.
-    Refused with NotImplementedError: typ='coarse' with test_time=False (the 4-channel training query, nerfw.py:47-60), typ='coarse'
-    under autograd without diff=True, and a netwidth other than 128 or 256 (no register-resident kernels)."""
+    The coarse network's TRAINING query (typ='coarse', test_time=False: the 4-channel input of raw2outputs_NeRFW's coarse mode) is
+    opt-in through the keyword `static=True`: it needs viewdirs [R, 3], one row per row of points; `ts` is ignored (the reference
+    passes None) and output_transient=True raises ValueError (the reference's coarse module has no transient branch either).  With
+    grad enabled and `inputs` or `viewdirs` requiring it the result is attached to both (netwidth 128, the precision rule above; the
+    weights receive nothing) -- there is no earlier behaviour to preserve, so `diff` is not needed for it.  typ='fine', and
+    typ='coarse' with test_time=True, accept and ignore the keyword.
+    Refused with NotImplementedError: typ='coarse' with test_time=False without static=True (the positional call of the reference),
+    typ='coarse' with test_time=True under autograd without diff=True, and a netwidth other than 128 or 256 (no register-resident
+    kernels)."""
 
     def __init__(self, engine, netchunk=65536, trainer=None, modules=None):
         self.engine = engine
@@ -158,7 +187,7 @@ class HipQuery:
                              "engine's own weights (pass None, or the module create_nerf returned)")
 
     def __call__(self, inputs, viewdirs, ts, network_fn=None, typ='fine', embedding_a=None, embedding_t=None, output_transient=True,
-                 test_time=True, diff=False):
+                 test_time=True, diff=False, static=False):
         self.refresh()
         if typ not in ('coarse', 'fine'):
             raise ValueError(f"network_query_fn: typ must be 'coarse' or 'fine', got {typ!r}")
@@ -175,9 +204,28 @@ class HipQuery:
         pts = inputs.reshape(-1, inputs.shape[-2], 3) if inputs.dim() > 2 else inputs.reshape(-1, 1, 3)
         tracked = torch.is_grad_enabled() and (inputs.requires_grad or (viewdirs is not None and viewdirs.requires_grad))
         if typ == 'coarse':
+            if not test_time and static:
+                if output_transient:
+                    raise ValueError("network_query_fn: typ='coarse' has no transient branch: output_transient must be False")
+                if viewdirs is None:
+                    raise ValueError("network_query_fn: typ='coarse' with test_time=False needs viewdirs [R, 3]")
+                v = viewdirs.reshape(-1, 3)
+                if v.shape[0] != pts.shape[0]:
+                    raise ValueError(f"network_query_fn: viewdirs must have one row per row of points ({pts.shape[0]}), got "
+                                     f"{tuple(viewdirs.shape)}")
+                if tracked and eng.width != 128:
+                    raise NotImplementedError(f"network_query_fn: the training coarse query is differentiable at netwidth 128 only (the "
+                                              f"input-gradient kernels; this engine has netwidth {eng.width}): query under no_grad, or "
+                                              "with inputs and viewdirs detached")
+                if tracked:
+                    raw = _CoarseStaticPointsFn.apply(pts, v, eng, "f16x3" if eng.precision in ("f16", "fp16") else eng.precision)
+                else:
+                    raw = eng.mlp_coarse_static_points(pts.detach(), v.detach())
+                return raw.reshape(lead + (4,))
             if not test_time:
                 raise NotImplementedError("network_query_fn: typ='coarse' with test_time=False (the 4-channel training query, "
-                                          "nerfw.py:47-60) is not implemented; the training render evaluates it (rendering.render)")
+                                          "nerfw.py:47-60) is opt-in: pass the keyword static=True for raw [..., N, 4] = (static_rgb, "
+                                          "static_sigma); without it the training render evaluates it (rendering.render)")
             if diff and torch.is_grad_enabled() and inputs.requires_grad:
                 sigma = _CoarsePointsFn.apply(pts, eng, "f16x3" if eng.precision in ("f16", "fp16") else eng.precision)
                 return sigma.reshape(lead + (1,))

@@ -358,6 +358,22 @@ int dfn_mlp_fine_points_backward(dfn_nerfh_t h, int prec, const float* pts, cons
  * DFN_ERR_UNSUPPORTED); n_rows == 0 is DFN_OK, a null pointer DFN_ERR_ARG, n_rows * N below 2^31 as above. */
 int dfn_mlp_coarse_points_backward(dfn_nerfh_t h, int prec, const float* pts, size_t n_rows, int N, const float* grad_sigma,
                                    float* grad_pts, void* stream);
+/* cites nerfw.py:47-60, 326-343: the TRAINING coarse query of run_network_NeRFW (typ='coarse', test_time=False) on pre-sampled points:
+ * the coarse network's output_transient=False branch, raw4 [n_rows, N, 4] = [sigmoid(static_rgb) (3), softplus(static_sigma)], exactly
+ * n_rows * N * 4 floats (no alignment beyond a float's is asked of raw4).  pts [n_rows, N, 3] and viewdirs [n_rows, 3] (one view
+ * direction per row) as for dfn_mlp_fine_points; there is no histogram: the coarse dir_encoding.0 has no appearance columns.
+ * bias_table is scratch for the per-row seeds of dir_encoding.0: the fine query's buffer, dfn_fine_bias_bytes(n_rows) bytes, is enough.
+ * Every arithmetic mode; netwidth 128 and 256 (a generic width: DFN_ERR_UNSUPPORTED).  n_rows == 0 is DFN_OK, a null pointer or N < 1
+ * DFN_ERR_ARG, n_rows * N below 2^31 as above. */
+int dfn_mlp_coarse_static_points(dfn_nerfh_t h, int prec, const float* pts, const float* viewdirs, size_t n_rows, int N, float* raw4,
+                                 void* bias_table, void* stream);
+/* cites nerfw.py:47-60, 326-343: autograd through that query into its points and view directions: from grad_raw4 [n_rows, N, 4] =
+ * d L / d raw4 to grad_pts6 [n_rows, N, 6] = [d L / d point (3), d L / d viewdir through this point (3)] (the layout of
+ * dfn_mlp_fine_points_backward; a row's d L / d viewdir is the sum over its N points), exactly n_rows * N * 6 floats.  One pass,
+ * deterministic; bias_table as above.  Netwidth 128, DFN_PREC_F16X3 or DFN_PREC_F32 (plain f16 and other widths:
+ * DFN_ERR_UNSUPPORTED); status codes as above. */
+int dfn_mlp_coarse_static_points_backward(dfn_nerfh_t h, int prec, const float* pts, const float* viewdirs, size_t n_rows, int N,
+                                          const float* grad_raw4, float* grad_pts6, void* bias_table, void* stream);
 
 /* Per-ray reduction of grad_pts [n_rays, Nf, 6] (pts = o + d z, rendering.py:292,305): grad_rays_o = sum g,
  * grad_rays_d = sum z g; with derive_viewdirs != 0 the view-direction part is folded into grad_rays_d through
