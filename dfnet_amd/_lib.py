@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("DFN_LIB_PATH") or os.path.join(os.path.dirname(os.pat
 DFN_PREC_F16 = 0
 DFN_PREC_F32 = 1
 DFN_PREC_F16X3 = 2  # DFNet only: split-f16 (fp32-grade results at f16 MFMA rate)
+DFN_NET_COARSE, DFN_NET_FINE = 0, 1   # dfn_nerfh_points_train_*: the network a training query on points evaluates
 PRECISIONS = {"f16": DFN_PREC_F16, "fp16": DFN_PREC_F16, "f32": DFN_PREC_F32, "fp32": DFN_PREC_F32, "f16x3": DFN_PREC_F16X3}
 
 COMP_TEST_TIME, COMP_STATIC_ONLY, COMP_WHITE_BKGD = 1, 2, 4
@@ -190,6 +191,10 @@ SIGNATURES = {
                                               POINTER(TrainMapGrads), c_float, _P, POINTER(c_void_p), _P, c_size_t, _P]),
     "dfn_nerfh_train_backward_rays_maps": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, _P, c_float, _P,
                                                    POINTER(TrainMapGrads), c_float, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
+    "dfn_nerfh_points_train_workspace_bytes": (c_size_t, [_P, c_int, c_size_t, c_int]),
+    "dfn_nerfh_points_train_forward": (c_int, [_P, c_int, POINTER(c_void_p), _P, _P, _P, c_size_t, c_size_t, c_int, _P, _P, c_size_t, _P]),
+    "dfn_nerfh_points_train_backward": (c_int, [_P, c_int, POINTER(c_void_p), _P, c_size_t, c_size_t, c_int, _P, _P, POINTER(c_void_p),
+                                                _P, c_size_t, _P]),
     "dfn_nerfh_generic_workspace_bytes": (c_size_t, [_P, c_size_t, c_int, c_int]),
     "dfn_nerfh_generic_render_rays": (c_int, [_P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, c_float, c_float, _P, _P, _P, _P,
                                               _P, c_size_t, _P]),

@@ -718,3 +718,242 @@ int train_backward(const char* fn, dfn_nerfh_s* h, const float* const* params, c
 
 }  // namespace fused
 }  // namespace dfn
+
+// ------------------------------------------------------------------------------------------ a training query on points
+// dfn_nerfh_points_train_*: the machinery above for ONE network on given points (reference: models/nerfw.py:47-95, 297-354 under
+// autograd with respect to the parameters).  The chains are those of nerfh_fused_chain_pts.hip, everything behind them — stream,
+// reduction, per-row sums, tail products, embedding scatter, range guard — is the step's, on this network's jobs and tensors alone.
+namespace {
+// Workspace of one query: everything its backward reads lives here (several queries may be in flight on one handle), including
+// the query's own range word — the step's word (range_flag + 2) would be cleared by the next query's forward.
+struct PtsWs {
+  int* range_word;
+  float *dir_in, *t_in, *gsum, *gray, *wscratch, *partial;
+  NetWs net;
+  size_t total;
+};
+size_t points_tail_scratch_floats(const Geo& g, bool fine, size_t R) {
+  size_t sum = gemm_wgrad_scratch_floats(kWidth / 2, fine ? g.ld_df : g.ld_dc, (long long)R);
+  if (fine) sum += gemm_wgrad_scratch_floats(kWidth / 2, g.ld_t, (long long)R);
+  return sum + 1024;
+}
+PtsWs carve_points(char* base, const dfn_nerfh_desc& d, bool fine, size_t R, int N, bool split_fine) {
+  PtsWs w{};
+  const Geo g = geo_of(d);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += al256(bytes); return p; };
+  auto takef = [&](size_t floats) { return reinterpret_cast<float*>(take(floats * 4)); };
+  const int planes = planes_of(fine, split_fine);
+  w.range_word = reinterpret_cast<int*>(take(sizeof(int)));
+  w.dir_in = takef(R * size_t(fine ? g.ld_df : g.ld_dc));
+  w.t_in = fine ? takef(R * size_t(g.ld_t)) : nullptr;
+  w.gsum = takef(R * size_t(fine ? kWidth : kWidth / 2));
+  w.gray = fine ? takef(R * size_t(g.ld_df > g.ld_t ? g.ld_df : g.ld_t)) : nullptr;
+  w.wscratch = takef(points_tail_scratch_floats(g, fine, R));
+  NetWs& n = w.net;
+  n.P = (long long)R * N;
+  n.n_wt = chain_wave_tiles(n.P);
+  n.z = nullptr;
+  n.gpre = nullptr;
+  n.ray_bias = takef(R * kRayBiasFloats);
+  n.masks = reinterpret_cast<uint32_t*>(take(n.n_wt * kMaskWords * 64 * 4));
+  n.gscale = takef(size_t(GA_COUNT) * n.n_wt);
+  size_t xb = 0, gb = 0;
+  for (int a = 0; a < (fine ? int(XA_COUNT) : kXCountCoarse); ++a) { n.x_off[a] = xb; xb += n.n_wt * kXChunks[a] * size_t(1024 * planes); }
+  for (int a = 0; a < (fine ? int(GA_COUNT) : kGCountCoarse); ++a) { n.g_off[a] = gb; gb += n.n_wt * (fine ? kGChunksFine : kGChunksCoarse)[a] * size_t(1024 * planes); }
+  n.x = take(xb);
+  n.g = take(gb);
+  {
+    State dummy;
+    WJob jobs[kMaxJobs];
+    int nj = 0;
+    float* part = nullptr;
+    size_t floats = 0;
+    make_jobs(fine, n, dummy, part, jobs, nj);
+    for (int j = 0; j < nj; ++j) floats += size_t(jobs[j].n_chunks) * jobs[j].nb_g * (jobs[j].nb_x + jobs[j].has_bias) * 1024;
+    w.partial = takef(floats);
+  }
+  w.total = off;
+  return w;
+}
+// what every points entry refuses before it looks at its pointers (`fn`: the entry's name)
+int check_points_train(dfn_nerfh_t h, int net, size_t n_rows, int N, const char* fn) {
+  if (!h) return set_error(DFN_ERR_ARG, "%s: null handle", fn);
+  if (!h->committed) return set_error(DFN_ERR_STATE, "%s: dfn_nerfh_commit() has not been called", fn);
+  if (!available(h))
+    return set_error(DFN_ERR_UNSUPPORTED, "%s: the fused training chains exist for netwidth %d only (this handle: %d); there is no "
+                     "layer-by-layer points path", fn, kWidth, h->desc.width);
+  if (h->train_exact)
+    return set_error(DFN_ERR_UNSUPPORTED, "%s: the handle is in DFN_TRAIN_EXACT mode; there is no layer-by-layer points path "
+                     "(dfn_nerfh_set_train_mode: DFN_TRAIN_FUSED or DFN_TRAIN_FUSED_SPLIT)", fn);
+  if (net != DFN_NET_COARSE && net != DFN_NET_FINE) return set_error(DFN_ERR_ARG, "%s: unknown net %d (DFN_NET_COARSE, DFN_NET_FINE)", fn, net);
+  if (N < 1) return set_error(DFN_ERR_ARG, "%s: bad argument (N >= 1)", fn);
+  if (n_rows > ((size_t(1) << 31) - 1) / size_t(N)) return set_error(DFN_ERR_ARG, "%s: n_rows * N must stay below 2^31 (chunk by rows)", fn);
+  return DFN_OK;
+}
+// this network's entries of the 64-pointer arrays (and, for the fine network, the two embeddings) must be there
+template <class T>
+int check_net_pointers(T* const* arr, bool fine, const char* what, const char* fn) {
+  const int p0 = fine ? kCoarseParams : 0, n = fine ? kFineParams : kCoarseParams;
+  for (int i = p0; i < p0 + n; ++i)
+    if (!arr[i]) return set_error(DFN_ERR_ARG, "%s: %s[%d] is null", fn, what, i);
+  if (fine)
+    for (int i = kCoarseParams + kFineParams; i < kCoarseParams + kFineParams + 2; ++i)
+      if (!arr[i]) return set_error(DFN_ERR_ARG, "%s: %s[%d] is null", fn, what, i);
+  return DFN_OK;
+}
+}  // namespace
+
+extern "C" size_t dfn_nerfh_points_train_workspace_bytes(dfn_nerfh_t h, int net, size_t n_rows, int N) {
+  if (!h || (net != DFN_NET_COARSE && net != DFN_NET_FINE) || N < 1 || h->desc.width != kWidth) return 0;
+  if (n_rows > ((size_t(1) << 31) - 1) / size_t(N)) return 0;
+  return carve_points(nullptr, h->desc, net == DFN_NET_FINE, n_rows ? n_rows : 1, N, h->train_split_fine).total;
+}
+
+extern "C" int dfn_nerfh_points_train_forward(dfn_nerfh_t h, int net, const float* const* params, const float* pts, const float* viewdirs,
+                                              const float* hist, size_t hist_rows, size_t n_rows, int N, float* raw, void* workspace,
+                                              size_t workspace_bytes_, void* stream) {
+  const char* fn = "dfn_nerfh_points_train_forward";
+  if (int rc = check_points_train(h, net, n_rows, N, fn)) return rc;
+  if (!n_rows) return DFN_OK;
+  const bool fine = net == DFN_NET_FINE;
+  if (!params || !pts || !viewdirs || !raw || !workspace || (fine && (!hist || (hist_rows != 1 && hist_rows != n_rows))))
+    return set_error(DFN_ERR_ARG, "%s: bad argument (null pointer, or hist_rows not 1 or n_rows)", fn);
+  if (int rc = check_net_pointers(params, fine, "params", fn)) return rc;
+  if (!h->fused)
+    if (int rc = build_state(h)) return rc;
+  const State& st = *static_cast<State*>(h->fused);
+  const size_t R = n_rows;
+  const PtsWs w = carve_points(static_cast<char*>(workspace), h->desc, fine, R, N, h->train_split_fine);
+  if (w.total > workspace_bytes_) return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes_, w.total);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const Geo g = geo_of(h->desc);
+  const dfn_nerfh_desc& d = h->desc;
+  const int W = kWidth, planes = planes_of(fine, h->train_split_fine);
+  const float* const* pn = params + (fine ? kCoarseParams : 0);
+  const int kd = fine ? g.kd_f : g.kd_c, ld_dir = fine ? g.ld_df : g.ld_dc;
+  {   // this network's per-row inputs from the view directions as given; the query's range word cleared
+    PointsRowPrepArgs pa{};
+    pa.viewdirs = viewdirs; pa.R = R;
+    pa.hist = fine ? hist : nullptr; pa.hist_rows = hist_rows;
+    pa.emb_a = fine ? params[kCoarseParams + kFineParams] : nullptr; pa.emb_t = fine ? params[kCoarseParams + kFineParams + 1] : nullptr;
+    pa.hist_bin = d.hist_bin; pa.dim_a = d.dim_a; pa.dim_t = d.dim_t; pa.n_vocab = d.n_vocab;
+    pa.dir_in = w.dir_in; pa.ld_dir = ld_dir; pa.t_in = w.t_in; pa.ld_t = g.ld_t;
+    pa.range_word = w.range_word;
+    CHECK_HIP(launch_points_row_prep(pa, s), "points train forward: per-row inputs");
+  }
+  {   // the live weights of this network -> its forward and backward staging units (the other network's two blobs are skipped)
+    PackArgs4 pa{};
+    const float in_scale = train_scale(h, fine);
+    for (int pass = 0; pass < 2; ++pass) {
+      const DevBlob& b = st.blob[fine][pass];
+      pa.b[2 * int(fine) + pass] = PackBlob{b.welem, b.n_w, b.belem, b.n_b, b.blob, in_scale / kX3ActScale, in_scale};
+    }
+    for (int i = 0; i < 64; ++i) pa.params[i] = params[i];
+    pa.status = w.range_word;
+    CHECK_HIP(launch_pack4(pa, s), "points train forward: weight packing");
+  }
+  {
+    PointsRowBiasArgs ba{pn[2 * DIR], pn[2 * DIR + 1], W + kd, kd, w.dir_in, ld_dir, nullptr, nullptr, 0, 0, nullptr, 0, w.net.ray_bias};
+    if (fine) { ba.w_te = pn[2 * TE0]; ba.b_te = pn[2 * TE0 + 1]; ba.ldw_te = W + g.nt; ba.nt = g.nt; ba.t_in = w.t_in; ba.ld_t = g.ld_t; }
+    CHECK_HIP(launch_points_row_bias(ba, R, s), "points train forward: per-row bias table");
+  }
+  ChainArgs a = chain_args(h, st, fine, 0, w.net, pts, nullptr, R, N);
+  a.raw_out = raw;
+  a.status = w.range_word;
+  CHECK_HIP(launch_points_forward_chain(fine, planes, a, device_cu_count(), s), "points train forward: chain");
+  return DFN_OK;
+}
+
+extern "C" int dfn_nerfh_points_train_backward(dfn_nerfh_t h, int net, const float* const* params, const float* hist, size_t hist_rows,
+                                               size_t n_rows, int N, const float* raw, const float* grad_raw, float* const* grads,
+                                               void* workspace, size_t workspace_bytes_, void* stream) {
+  const char* fn = "dfn_nerfh_points_train_backward";
+  if (int rc = check_points_train(h, net, n_rows, N, fn)) return rc;
+  if (!n_rows) return DFN_OK;
+  const bool fine = net == DFN_NET_FINE;
+  if (!params || !raw || !grad_raw || !grads || !workspace || (fine && (!hist || (hist_rows != 1 && hist_rows != n_rows))))
+    return set_error(DFN_ERR_ARG, "%s: bad argument (null pointer, or hist_rows not 1 or n_rows)", fn);
+  if (int rc = check_net_pointers(params, fine, "params", fn)) return rc;
+  if (int rc = check_net_pointers(grads, fine, "grads", fn)) return rc;
+  if (!h->fused) return set_error(DFN_ERR_STATE, "%s: no forward pass on this handle", fn);
+  const State& st = *static_cast<State*>(h->fused);
+  const size_t R = n_rows;
+  const PtsWs w = carve_points(static_cast<char*>(workspace), h->desc, fine, R, N, h->train_split_fine);
+  if (w.total > workspace_bytes_) return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes_, w.total);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const Geo g = geo_of(h->desc);
+  const dfn_nerfh_desc& d = h->desc;
+  const int W = kWidth, W2 = kWidth / 2, planes = planes_of(fine, h->train_split_fine);
+  const float* const* pn = params + (fine ? kCoarseParams : 0);
+  float* const* gn = grads + (fine ? kCoarseParams : 0);
+  float* g_emb_a = fine ? grads[kCoarseParams + kFineParams] : nullptr;
+  float* g_emb_t = fine ? grads[kCoarseParams + kFineParams + 1] : nullptr;
+  if (fine) {   // the scatters at the end accumulate
+    CHECK_HIP(hipMemsetAsync(g_emb_a, 0, size_t(d.n_vocab) * d.dim_a * sizeof(float), s), "points train backward: zero embedding_a grad");
+    CHECK_HIP(hipMemsetAsync(g_emb_t, 0, size_t(d.n_vocab) * d.dim_t * sizeof(float), s), "points train backward: zero embedding_t grad");
+  }
+  {   // data-gradient chain, seeded from d L / d raw and the post-activation raw
+    ChainArgs a = chain_args(h, st, fine, 1, w.net, nullptr, nullptr, R, N);
+    a.gpre = grad_raw;
+    a.raw_out = const_cast<float*>(raw);   // read only (nerfh_fused_train.h)
+    a.status = w.range_word;
+    CHECK_HIP(launch_points_backward_chain(fine, planes, a, device_cu_count(), s), "points train backward: chain");
+  }
+  {   // weight gradients of this network's jobs: stream, then the fixed-order reduction into its gradient tensors
+    WgradArgs wa{};
+    ReduceArgs ra{};
+    float* part = w.partial;
+    const int wgs = make_jobs(fine, w.net, st, part, wa.job, wa.n_jobs);
+    wa.n_wt = int(w.net.n_wt);
+    CHECK_HIP(launch_wgrad_stream(wa, wgs, planes, s), "points train backward: weight-gradient stream");
+    for (int j = 0; j < wa.n_jobs; ++j) {
+      const WJob& q = wa.job[j];
+      ra.job[ra.n_jobs++] = RJob{q.partial, q.nb_g, q.nb_x, q.has_bias, q.n_chunks, q.map_off};
+    }
+    ra.map = st.map;
+    for (int i = 0; i < 64; ++i) ra.grads[i] = grads[i];
+    CHECK_HIP(launch_wgrad_reduce(ra, s), "points train backward: weight-gradient reduction");
+  }
+  // the columns beyond `final` of dir_encoding.0 / transient_encoding.0 multiply per-row inputs: per-row sums, then the small products
+  CHECK_HIP(launch_frag_ray_sum(w.net.g + w.net.g_off[GA_CAT], fine ? 8 : 4, planes, w.net.gscale + size_t(GA_CAT) * w.net.n_wt, R, N, w.gsum,
+                                fine ? W : W2, s),
+            "points train backward: per-row sums");
+  const int kd = fine ? g.kd_f : g.kd_c, ld_dir = fine ? g.ld_df : g.ld_dc, ldw_dir = W + kd, ldw_te0 = W + g.nt;
+  const float* gsum_dir = fine ? w.gsum + W2 : w.gsum;   // fine: [d t0 (64) | d dir_h (64)] per row
+  const int ldg = fine ? W : W2;
+  const WgradJob tails[2] = {{gsum_dir, ldg, W2, Seg{w.dir_in, ld_dir, kd, 1, W}, gn[2 * DIR], ldw_dir, nullptr},
+                             {w.gsum, ldg, W2, Seg{w.t_in, g.ld_t, g.nt, 1, W}, fine ? gn[2 * TE0] : nullptr, ldw_te0, nullptr}};
+  const int n_tails = fine ? 2 : 1;
+  if (gemm_wgrad_multi_ok(tails, n_tails, (long long)R)) {
+    CHECK_HIP(gemm_wgrad_multi(tails, n_tails, w.wscratch, (long long)R, s), "points train backward: per-row tails");
+  } else {
+    for (int t = 0; t < n_tails; ++t)
+      CHECK_HIP(gemm_wgrad(tails[t].G, tails[t].ldg, tails[t].N, tails[t].x, tails[t].dW, tails[t].ldw, nullptr, w.wscratch, (long long)R, s),
+                "points train backward: per-row tail");
+  }
+  if (fine) {
+    CHECK_HIP(gemm_bwd(w.gsum, W, W2, pn[2 * TE0], ldw_te0, W, g.nt, w.gray, g.ld_t, 0, nullptr, 0, (long long)R, s), "points train backward: d t");
+    CHECK_HIP(embedding_scatter(w.gray, g.ld_t, 0, hist, hist_rows, d.hist_bin, d.dim_t, d.n_vocab, R, g_emb_t, s), "points train backward: embedding_t grad");
+    CHECK_HIP(gemm_bwd(w.gsum + W2, W, W2, pn[2 * DIR], ldw_dir, W + kChDir, g.na, w.gray, g.ld_df, 0, nullptr, 0, (long long)R, s), "points train backward: d a");
+    CHECK_HIP(embedding_scatter(w.gray, g.ld_df, 0, hist, hist_rows, d.hist_bin, d.dim_a, d.n_vocab, R, g_emb_a, s), "points train backward: embedding_a grad");
+  }
+  {   // a query whose operands left the split-f16 range leaves zeros in ITS tensors (the other network's are not listed)
+    GuardArgs ga{};
+    int n = 0;
+    for (int l = 0; l < (fine ? kFineLayers_ : kCoarseLayers_); ++l) {
+      const int p = weight_param(fine, l);
+      ga.grads[n] = grads[p]; ga.numel[n++] = uint32_t(rows_of(l)) * uint32_t(cols_of(l, fine, g));
+      ga.grads[n] = grads[p + 1]; ga.numel[n++] = uint32_t(rows_of(l));
+    }
+    if (fine) {
+      ga.grads[n] = g_emb_a; ga.numel[n++] = uint32_t(d.n_vocab) * uint32_t(d.dim_a);
+      ga.grads[n] = g_emb_t; ga.numel[n++] = uint32_t(d.n_vocab) * uint32_t(d.dim_t);
+    }
+    ga.n = n;
+    ga.step_flag = w.range_word;
+    ga.range_flag = h->range_flag;
+    CHECK_HIP(launch_grads_guard(ga, s), "points train backward: range guard");
+  }
+  return DFN_OK;
+}

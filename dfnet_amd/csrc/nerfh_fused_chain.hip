@@ -13,6 +13,13 @@
 //             so a point far below its wave's largest gradient needs no precision of its own, and the stored halves stay in
 //             f16's range whatever the gradient magnitude.
 // The weight gradients are then a pure stream over (G_l, X_l): nerfh_fused_wgrad.hip.  Layouts: nerfh_fused_train.h.
+//
+// The POINTS flavour (a training query on given points, dfn_nerfh_points_train_*: one network at a time, no rays and no compositor)
+// is a translation unit of its own: nerfh_fused_chain_pts.hip defines DFN_CHAIN_PTS_TU, includes this file and gets
+// train_fwd_chain_pts_kernel / train_bwd_chain_pts_kernel with their two launchers and nothing else.  There the forward chain loads
+// the point from ChainArgs::rays_o = pts [P, 3], and the backward chain forms its seed from d L / d raw (ChainArgs::gpre) and the
+// POST-activation raw (ChainArgs::raw_out, read only): g y (1 - y) on the sigmoid channels, g (1 - e^-y) on the softplus ones.  Every
+// branch on kPts below is that unit's alone; without the flag this file compiles to the code object it always had.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -26,6 +33,13 @@ namespace fused {
 namespace {
 using P = PrecX3;
 using F = half8x2;
+#ifdef DFN_CHAIN_PTS_TU
+constexpr bool kPts = true;
+#define train_fwd_chain_kernel train_fwd_chain_pts_kernel
+#define train_bwd_chain_kernel train_bwd_chain_pts_kernel
+#else
+constexpr bool kPts = false;
+#endif
 constexpr int NB = 1, WAVES = 8, UMB = 2;
 constexpr int HC = 8, QC = 4, PC = 4, SC = 2;   // chunks of a 128- / 64- / encoding- / head-wide operand
 constexpr uint32_t kFwdStride = unit_bytes<P>(96, UMB);   // largest forward unit: two M-blocks of layer 5 (96 slots)
@@ -91,9 +105,11 @@ DFN_DEV float renorm_wave(const F (&v)[N], float sp_now) {
 }
 }  // namespace
 
+#ifndef DFN_CHAIN_PTS_TU
 size_t chain_wave_tiles(long long n_points) {
   return size_t((n_points + kTilePoints - 1) / kTilePoints) * WAVES;
 }
+#endif
 
 // ------------------------------------------------------------------------------------------ forward
 template <bool FINE, int PL>
@@ -115,7 +131,10 @@ __global__ __launch_bounds__(WAVES * 64, 1) void train_fwd_chain_kernel(ChainArg
     const uint32_t q = uint32_t(pt < n_pts ? pt : n_pts - 1);
     const uint32_t ray = q / uint32_t(a.n_samples);
     float x[NB][3];
-    {
+    if constexpr (kPts) {   // the point as given (ChainArgs::rays_o = pts [P, 3]); `ray` = its row, for the per-row bias table
+#pragma unroll
+      for (int c = 0; c < 3; ++c) x[0][c] = a.rays_o[size_t(q) * 3 + c];
+    } else {
       const float z = a.z[q];
 #pragma unroll
       for (int c = 0; c < 3; ++c) x[0][c] = add_rn(a.rays_o[ray * 3 + c], mul_rn(a.rays_d[ray * 3 + c], z));
@@ -244,6 +263,11 @@ DFN_DEV void train_bwd_chain_body(const ChainArgs& a, char* smem, const int blk,
       const float* src = a.gpre + size_t(pt < n_pts ? pt : n_pts - 1) * RAWC;
 #pragma unroll
       for (int c = 0; c < RAWC; ++c) g[c] = on ? src[c] : 0.f;
+      if constexpr (kPts) {   // gpre holds d L / d raw: the heads' derivatives from their outputs y (head_prime_kernel's expressions)
+        const float* y = a.raw_out + size_t(pt < n_pts ? pt : n_pts - 1) * RAWC;
+#pragma unroll
+        for (int c = 0; c < RAWC; ++c) g[c] = on ? g[c] * ((c == 3 || c >= 7) ? -expm1f(-y[c]) : y[c] * (1.f - y[c])) : 0.f;
+      }
     }
     const float* const norb[NB] = {};
     const size_t wt = size_t(tile) * WAVES + st.wave;
@@ -409,12 +433,14 @@ __global__ __launch_bounds__(WAVES * 64, 1) void train_bwd_chain_kernel(ChainArg
 // tiles = 4.5 per CU, 384 coarse tiles = 1.5 per CU) that fills the half-tile tails of both chains: 6.0 tile times instead of
 // 5 + 2.  One stream, one launch: the same overlap from a second HIP stream gave the time back through slower launches of every
 // other kernel of the step, and hipExtAnyOrderLaunch is ignored on this part (LABBOOK R6.17).
+#ifndef DFN_CHAIN_PTS_TU
 template <int PLF>
 __global__ __launch_bounds__(WAVES * 64, 1) void train_bwd_chain_pair_kernel(ChainArgs fine, ChainArgs coarse, int n_fine) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if (int(blockIdx.x) < n_fine) train_bwd_chain_body<true, PLF>(fine, smem, int(blockIdx.x), n_fine);
   else train_bwd_chain_body<false, 2>(coarse, smem, int(blockIdx.x) - n_fine, int(gridDim.x) - n_fine);
 }
+#endif
 
 // ------------------------------------------------------------------------------------------ launch
 template <class K>
@@ -433,14 +459,22 @@ static hipError_t launch_chain(K kern, bool& attr_done, uint32_t lds, const Chai
   return hipGetLastError();
 }
 
+#ifdef DFN_CHAIN_PTS_TU
+hipError_t launch_points_forward_chain(bool fine, int planes, const ChainArgs& a, int n_cu, hipStream_t s) {
+#else
 hipError_t launch_train_forward_chain(bool fine, int planes, const ChainArgs& a, int n_cu, hipStream_t s) {
+#endif
   static bool done[3] = {false, false, false};
   if (!fine) return planes == 2 ? launch_chain(train_fwd_chain_kernel<false, 2>, done[0], 3 * kFwdStride, a, n_cu, s) : hipErrorInvalidValue;
   if (planes == 1) return launch_chain(train_fwd_chain_kernel<true, 1>, done[1], 3 * kFwdStride, a, n_cu, s);
   if (planes == 2) return launch_chain(train_fwd_chain_kernel<true, 2>, done[2], 3 * kFwdStride, a, n_cu, s);
   return hipErrorInvalidValue;
 }
+#ifdef DFN_CHAIN_PTS_TU
+hipError_t launch_points_backward_chain(bool fine, int planes, const ChainArgs& a, int n_cu, hipStream_t s) {
+#else
 hipError_t launch_train_backward_chain(bool fine, int planes, const ChainArgs& a, int n_cu, hipStream_t s) {
+#endif
   static bool done[3] = {false, false, false};
   if (!fine) return planes == 2 ? launch_chain(train_bwd_chain_kernel<false, 2>, done[0], 3 * kBwdStride, a, n_cu, s) : hipErrorInvalidValue;
   if (planes == 1) return launch_chain(train_bwd_chain_kernel<true, 1>, done[1], 3 * kBwdStride, a, n_cu, s);
@@ -448,6 +482,7 @@ hipError_t launch_train_backward_chain(bool fine, int planes, const ChainArgs& a
   return hipErrorInvalidValue;
 }
 
+#ifndef DFN_CHAIN_PTS_TU
 hipError_t launch_train_backward_chain_pair(int planes_fine, const ChainArgs& fine, const ChainArgs& coarse, int n_cu, hipStream_t s) {
   static bool done[2] = {false, false};
   const long long pf = (long long)fine.n_rays * fine.n_samples, pc = (long long)coarse.n_rays * coarse.n_samples;
@@ -466,6 +501,7 @@ hipError_t launch_train_backward_chain_pair(int planes_fine, const ChainArgs& fi
   else hipLaunchKernelGGL(train_bwd_chain_pair_kernel<2>, dim3(gf + gc), dim3(WAVES * 64), 3 * kBwdStride, s, fine, coarse, gf);
   return hipGetLastError();
 }
+#endif
 
 }  // namespace fused
 }  // namespace dfn

@@ -92,6 +92,28 @@ hipError_t launch_train_backward_chain(bool fine, int planes, const ChainArgs& a
 // both networks' data-gradient chains as the two halves of one grid (nerfh_fused_chain.hip: train_bwd_chain_pair_kernel)
 hipError_t launch_train_backward_chain_pair(int planes_fine, const ChainArgs& fine, const ChainArgs& coarse, int n_cu, hipStream_t s);
 size_t chain_wave_tiles(long long n_points);   // wave-tiles the chain kernels write (whole tiles)
+// The chains on GIVEN points, one network at a time (nerfh_fused_chain_pts.hip; dfn_nerfh_points_train_*).  Same ChainArgs, read
+// differently: rays_o = pts [P, 3] (rays_d, z unused); n_rays = rows, n_samples = points per row; backward: gpre = d L / d raw
+// (POST-activation, [P, 9] / [P, 4]) and raw_out = the forward's raw, read only — the chain forms the pre-activation seed itself.
+hipError_t launch_points_forward_chain(bool fine, int planes, const ChainArgs& a, int n_cu, hipStream_t s);
+hipError_t launch_points_backward_chain(bool fine, int planes, const ChainArgs& a, int n_cu, hipStream_t s);
+// ... and the two per-row kernels in front of them (nerfh_fused_points.hip).  Row inputs of ONE network from view directions as given
+// (not normalised: nerfw.py:47-95 embeds input_dirs as they come): dir_in[r] = [pe_dir(v) | embedding_a[hist] (emb_a != nullptr)],
+// t_in[r] = embedding_t[hist] (t_in != nullptr), padding zeroed; *range_word = 0.
+struct PointsRowPrepArgs {
+  const float* viewdirs; size_t R;
+  const float* hist; size_t hist_rows; const float* emb_a; const float* emb_t; int hist_bin, dim_a, dim_t, n_vocab;
+  float* dir_in; int ld_dir; float* t_in; int ld_t;
+  int* range_word;
+};
+hipError_t launch_points_row_prep(const PointsRowPrepArgs& a, hipStream_t s);
+// one network's bias table, as launch_ray_bias_train_pair below forms two (w_te == nullptr: table 0 only)
+struct PointsRowBiasArgs {
+  const float* w_dir; const float* b_dir; int ldw_dir; int kd; const float* dir_in; int ld_dir;
+  const float* w_te; const float* b_te; int ldw_te; int nt; const float* t_in; int ld_t;
+  float* table;
+};
+hipError_t launch_points_row_bias(const PointsRowBiasArgs& a, size_t R, hipStream_t s);
 
 // ---- weight-gradient stream
 struct WJob {

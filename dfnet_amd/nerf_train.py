@@ -227,6 +227,69 @@ class NerfHTrainer:
                                       ptr(go), ptr(gdir), *ws, ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), current_stream()), name)
         return go, gdir
 
+    # ------------------------------------------------------------------ a training query on points (one network)
+    def net_slots(self, net):
+        """Positions in `params` of what a training query of `net` ('coarse' | 'fine') differentiates: that network's tensors and, for the
+        fine one, the two embedding tables (run_network_NeRFW, nerfw.py:47-95)."""
+        if net not in ("coarse", "fine"):
+            raise ValueError(f"net must be 'coarse' or 'fine', got {net!r}")
+        pre = (net + ".",) + (("embedding_a.", "embedding_t.") if net == "fine" else ())
+        return [i for i, k in enumerate(self.names) if k.startswith(pre)]
+
+    def net_params(self, net):
+        return [self.params[i] for i in self.net_slots(net)]
+
+    def _points_mode(self, split):
+        check(self.lib.dfn_nerfh_set_train_mode(self.engine.handle, 2 if split else 0), "dfn_nerfh_set_train_mode")
+
+    def points_forward(self, net, pts, viewdirs, hist=None):
+        """network_query_fn(pts, ..., test_time=False) of ONE network with what its weight gradients need kept (dfn_nerfh_points_train_forward;
+        netwidth 128, the fused chains): pts [R, N, 3], viewdirs [R, 3] (as given), hist [R | 1, hist_bin] (fine; ignored for 'coarse')
+        -> (raw [R, N, 9] | [R, N, 4], saved).  The workspace is allocated here and owned by `saved`, not the trainer's: several queries
+        can be live in one graph.  The live master weights are split at the operand scale of the engine's last commit."""
+        fine = net == "fine"
+        self.net_slots(net)
+        pts, viewdirs = _f32c(pts), _f32c(viewdirs).reshape(-1, 3)
+        if pts.dim() != 3 or pts.shape[-1] != 3 or viewdirs.shape[0] != pts.shape[0]:
+            raise ValueError(f"points_forward: pts [R, N, 3] and viewdirs [R, 3], got {tuple(pts.shape)} and {tuple(viewdirs.shape)}")
+        R, N, dev = pts.shape[0], pts.shape[1], pts.device
+        if fine:
+            if hist is None:
+                raise ValueError("points_forward: net='fine' needs hist [R | 1, hist_bin]")
+            hist = _f32c(hist).reshape(-1, self.hist_bin)
+            if hist.shape[0] not in (1, R):
+                raise ValueError(f"hist must have 1 or {R} rows of {self.hist_bin} bins")
+        else:
+            hist = None
+        split = bool(self.fused_split)
+        self._points_mode(split)
+        nid = _lib.DFN_NET_FINE if fine else _lib.DFN_NET_COARSE
+        raw = torch.empty(R, N, 9 if fine else 4, device=dev)
+        ws = torch.empty(self.lib.dfn_nerfh_points_train_workspace_bytes(self.engine.handle, nid, R, N), dtype=torch.uint8, device=dev)
+        check(self.lib.dfn_nerfh_points_train_forward(self.engine.handle, nid, self._ptr_array(self.params), ptr(pts), ptr(viewdirs), ptr(hist),
+                                                      0 if hist is None else hist.shape[0], R, N, ptr(raw), ctypes.c_void_p(ws.data_ptr()),
+                                                      ws.numel(), current_stream()), "dfn_nerfh_points_train_forward")
+        return raw, dict(net=net, nid=nid, hist=hist, R=R, N=N, raw=raw, ws=ws, split=split, exact=False)
+
+    def points_backward(self, saved, g_raw, grads=None):
+        """d L / d raw [R, N, 9 | 4] of a points_forward() -> the gradient tensors of that network's parameters (net_params(net) order),
+        overwritten; the other network's are never touched.  grads: a list as long as `params` to write into (entries of the other
+        network may be None); None: fresh tensors.  X and the ReLU masks of `saved` survive (a second backward is fine), G is rewritten."""
+        s, slots = saved, self.net_slots(saved["net"])
+        if grads is None:
+            grads = [None] * len(self.params)
+            for i in slots:
+                grads[i] = torch.empty_like(self.params[i])
+        g_raw = _f32c(g_raw).reshape(s["raw"].shape)
+        self._points_mode(s["split"])   # the workspace was laid out in this mode
+        gptrs = (ctypes.c_void_p * len(grads))(*[None if g is None else ptr(g) for g in grads])
+        hist = s["hist"]
+        check(self.lib.dfn_nerfh_points_train_backward(self.engine.handle, s["nid"], self._ptr_array(self.params), ptr(hist),
+                                                       0 if hist is None else hist.shape[0], s["R"], s["N"], ptr(s["raw"]), ptr(g_raw), gptrs,
+                                                       ctypes.c_void_p(s["ws"].data_ptr()), s["ws"].numel(), current_stream()),
+              "dfn_nerfh_points_train_backward")
+        return [grads[i] for i in slots]
+
     def recommit(self):
         """Re-pack the engine from the live master weights: dfn_nerfh_commit re-derives the split-f16 operand scales, which is also
         what the fused training chains scale the step's weights by (csrc/nerfh_fused_api.hip: train_scale)."""
@@ -391,6 +454,49 @@ class _RenderTrainFn(torch.autograd.Function):
         else:
             grads = [None] * len(tr.params)
         return (None, None, g_o if ctx.needs_input_grad[2] else None, g_d if ctx.needs_input_grad[3] else None) + (None,) * 9 + tuple(grads)
+
+
+class _PointsTrainFn(torch.autograd.Function):
+    """network_query_fn(pts, ..., test_time=False) as an autograd node of ONE network's parameters (`params`: that network's tensors
+    and, for net='fine', the two embedding tables — NerfHTrainer.net_params(net)): raw [R, N, 9 | 4] from NerfHTrainer.points_forward,
+    the weight gradients from points_backward on the node's own workspace (several nodes can be live in one graph; a second backward
+    under retain_graph=True reuses the stored layer inputs).  When pts or viewdirs require grad they receive theirs from the engine's
+    input-gradient kernels (mlp_fine_points_backward / mlp_coarse_static_points_backward on the engine's packed copy of the same weights,
+    fp32-grade arithmetic as every tracked query; one view direction per row: summed over the row)."""
+
+    @staticmethod
+    def forward(ctx, net, trainer, pts, viewdirs, hist, *params):
+        pts, viewdirs = pts.detach().contiguous().float(), viewdirs.detach().contiguous().float().reshape(-1, 3)
+        raw, saved = trainer.points_forward(net, pts, viewdirs, hist)
+        ctx.net, ctx.trainer, ctx.saved, ctx.n_params = net, trainer, saved, len(params)
+        ctx.slot_of = {id(p): j for j, p in enumerate(trainer.net_params(net))}
+        ctx.param_ids = [id(p) for p in params]
+        ctx.save_for_backward(pts, viewdirs, raw, *params)   # (version-checked: an optimizer step between forward and backward is an error)
+        return raw
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        pts, viewdirs, raw = ctx.saved_tensors[:3]
+        tr, s = ctx.trainer, ctx.saved
+        g_raw = g_raw.contiguous().float()
+        g_pts = g_v = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            eng = tr.engine
+            prec = "f16x3" if eng.precision in ("f16", "fp16") else eng.precision
+            if ctx.net == "fine":
+                g = eng.mlp_fine_points_backward(pts, viewdirs, s["hist"], g_raw, precision=prec)
+            else:
+                g = eng.mlp_coarse_static_points_backward(pts, viewdirs, g_raw, precision=prec)
+            g_pts = g[..., :3].contiguous() if ctx.needs_input_grad[2] else None
+            g_v = g[..., 3:].sum(dim=1) if ctx.needs_input_grad[3] else None
+        grads = [None] * ctx.n_params
+        if any(ctx.needs_input_grad[5:]):
+            got = tr.points_backward(s, g_raw)
+            _after_node_backward(tr, s, g_raw.device)
+            for j, pid in enumerate(ctx.param_ids):
+                if pid in ctx.slot_of and ctx.needs_input_grad[5 + j]:
+                    grads[j] = got[ctx.slot_of[pid]]
+        return (None, None, g_pts, g_v, None) + tuple(grads)
 
 
 def _after_node_backward(tr, saved, dev):

@@ -106,7 +106,8 @@ class _CoarsePointsFn(torch.autograd.Function):
 class _CoarseStaticPointsFn(torch.autograd.Function):
     """raw [R,N,4] = (static_rgb, static_sigma) of the coarse network's training query at pts [R,N,3] with one view direction per row;
     backward: d L/d pts and d L/d viewdirs from d L/d raw (NerfHEngine.mlp_coarse_static_points / mlp_coarse_static_points_backward:
-    the forward is recomputed inside the gradient kernel).  The weights receive nothing."""
+    the forward is recomputed inside the gradient kernel).  The weights receive nothing here: network_query_fn(..., train=True) attaches
+    them (nerf_train._PointsTrainFn)."""
 
     @staticmethod
     def forward(ctx, pts, viewdirs, eng, prec):
@@ -138,7 +139,7 @@ class HipQuery:
       typ='fine',   output_transient=False  raw[..., :4] = (static_rgb, static_sigma), the four values the reference concatenates
     The networks are the ones packed into the engine: a `network_fn` / `embedding_a` / `embedding_t` that is not the module behind
     it raises ValueError (None is accepted).  With grad enabled and `inputs` or `viewdirs` requiring it, typ='fine' is differentiable
-    with respect to both (the weights receive no gradient here: that is the training step's job), in fp32-grade arithmetic as
+    with respect to both (the weights receive no gradient here: that is `train=True` below, or the training step), in fp32-grade arithmetic as
     `render` under autograd: an engine whose precision is plain f16 differentiates in split-f16.
     typ='coarse' is differentiable on request, as sample_pdf(diff=True) is: with `diff=True`, test_time=True, grad enabled and
     `inputs` requiring grad, sigma is attached to `inputs` (the coarse network's input-gradient kernel, netwidth 128, the precision
@@ -150,6 +151,17 @@ class HipQuery:
     grad enabled and `inputs` or `viewdirs` requiring it the result is attached to both (netwidth 128, the precision rule above; the
     weights receive nothing) -- there is no earlier behaviour to preserve, so `diff` is not needed for it.  typ='fine', and
     typ='coarse' with test_time=True, accept and ignore the keyword.
+    WEIGHT gradients are opt-in through the keyword `train=True` (without it every call is what it was): the query becomes an autograd
+    expression of the network's parameters, as the reference's network_query_fn(..., test_time=False) is (nerfw.py:47-95, 297-354) --
+    typ='fine': raw [..., N, 9] (or [..., :4]) attached to network_fine's parameters and both embedding weights; typ='coarse' with
+    test_time=False: raw [..., N, 4] attached to network_fn's parameters (static=True is implied, output_transient=True a ValueError).
+    With grad enabled the result is attached to `inputs` / `viewdirs` too when they require grad; under no_grad it is the plain forward
+    of the same kernels.  It runs the fused training chains on the LIVE master weights (netwidth 128; NerfHTrainer.points_forward /
+    points_backward, one workspace per call, so several queries may be live in one graph), at the operand scale of the engine's last
+    commit.  Stored operands follow trainer.fused_split: the fine network's default is one f16 plane, whose weight gradients are
+    f16-grade (1e-3) on queries of a few hundred points; fused_split = True gives fp32-grade ones.  Refused with NotImplementedError,
+    each naming the way out: no trainer behind the query (create_nerf with no_grad_update), a netwidth other than 128, and
+    typ='coarse' with test_time=True (the sigma-only query is not a training query).
     Refused with NotImplementedError: typ='coarse' with test_time=False without static=True (the positional call of the reference),
     typ='coarse' with test_time=True under autograd without diff=True, and a netwidth other than 128 or 256 (no register-resident
     kernels)."""
@@ -187,7 +199,7 @@ class HipQuery:
                              "engine's own weights (pass None, or the module create_nerf returned)")
 
     def __call__(self, inputs, viewdirs, ts, network_fn=None, typ='fine', embedding_a=None, embedding_t=None, output_transient=True,
-                 test_time=True, diff=False, static=False):
+                 test_time=True, diff=False, static=False, train=False):
         self.refresh()
         if typ not in ('coarse', 'fine'):
             raise ValueError(f"network_query_fn: typ must be 'coarse' or 'fine', got {typ!r}")
@@ -195,6 +207,8 @@ class HipQuery:
         self._check_module(embedding_a, 2, "embedding_a")
         self._check_module(embedding_t, 3, "embedding_t")
         eng = self.engine
+        if train:
+            return self._train_query(inputs, viewdirs, ts, typ, output_transient, test_time)
         if not eng.fast:
             raise NotImplementedError(f"network_query_fn: point queries exist for netwidth 128 and 256 (the register-resident "
                                       f"kernels); this engine has netwidth {eng.width}")
@@ -245,6 +259,45 @@ class HipQuery:
             raw = eng.mlp_fine_points(pts.detach(), v.detach(), hist)
         raw = raw.reshape(lead + (9,))
         return raw if output_transient else raw[..., :4]
+
+    def _train_query(self, inputs, viewdirs, ts, typ, output_transient, test_time):
+        """__call__(..., train=True): the query as an autograd expression of the network's PARAMETERS (and of both embedding tables for
+        typ='fine'), as the reference's network_query_fn(..., test_time=False) is (nerfw.py:15-95, 297-354) — nerf_train._PointsTrainFn on
+        the fused training chains (netwidth 128).  Attached to `inputs` / `viewdirs` as well when they require grad; under no_grad the
+        plain forward of the same kernels."""
+        from .nerf_train import _PointsTrainFn
+        eng, tr = self.engine, self.trainer
+        if typ == 'coarse' and test_time:
+            raise NotImplementedError("network_query_fn: train=True with typ='coarse' and test_time=True: the sigma-only query is not a "
+                                      "training query (the reference evaluates it under no_grad); pass test_time=False for raw "
+                                      "[..., N, 4] = (static_rgb, static_sigma) attached to network_fn's parameters")
+        if typ == 'coarse' and output_transient:
+            raise ValueError("network_query_fn: typ='coarse' has no transient branch: output_transient must be False")
+        if tr is None:
+            raise NotImplementedError("network_query_fn: train=True needs the trainer behind the engine (weight gradients): create_nerf "
+                                      "without no_grad_update attaches one, or set query.trainer = NerfHTrainer(engine, network_fn, "
+                                      "network_fine, embedding_a, embedding_t)")
+        if eng.width != 128:
+            raise NotImplementedError(f"network_query_fn: train=True runs on the fused training chains, which exist for netwidth 128 only "
+                                      f"(this engine has netwidth {eng.width}); train through rendering.render(test_time=False) / "
+                                      "NerfHTrainer.train_step, which take any width on the exact step")
+        if inputs.shape[-1] != 3 or inputs.dim() < 2:
+            raise ValueError(f"network_query_fn: inputs must be [..., N, 3], got {tuple(inputs.shape)}")
+        fine = typ == 'fine'
+        if viewdirs is None or (fine and ts is None):
+            raise ValueError("network_query_fn: train=True needs viewdirs [R, 3]" + (" and ts [R | 1, hist_bin]" if fine else ""))
+        lead = tuple(inputs.shape[:-1])
+        pts = inputs.reshape(-1, inputs.shape[-2], 3) if inputs.dim() > 2 else inputs.reshape(-1, 1, 3)
+        v = viewdirs.reshape(-1, 3)
+        if v.shape[0] != pts.shape[0]:
+            raise ValueError(f"network_query_fn: viewdirs must have one row per row of points ({pts.shape[0]}), got {tuple(viewdirs.shape)}")
+        hist = ts.detach().float().reshape(-1, eng.hist_bin).contiguous() if fine else None
+        if torch.is_grad_enabled():
+            raw = _PointsTrainFn.apply(typ, tr, pts, v, hist, *tr.net_params(typ))
+        else:
+            raw, _ = tr.points_forward(typ, pts, v, hist)
+        raw = raw.reshape(lead + (9 if fine else 4,))
+        return raw if (not fine or output_transient) else raw[..., :4]
 
 
 def create_nerf(args):

@@ -808,6 +808,33 @@ int dfn_nerfh_train_backward_rays_maps(dfn_nerfh_t h, const float* const* params
                                        const float* grad_raw_ext, float* grad_rays_o, float* grad_rays_d, void* workspace,
                                        size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- a TRAINING query on points: one network under autograd with respect to its parameters
+ * run_network_NeRFW with test_time=False on given points (models/nerfw.py:47-95, 297-354): in the reference
+ * network_query_fn(pts, ...) is an autograd expression of the network's parameters and, for the fine network, of both embedding
+ * tables — whatever the caller does with raw (the composed chain query -> raw2outputs_NeRFW -> sample_pdf -> query, a depth prior, a
+ * regulariser on raw).  The fused step's chains on points instead of rays, for ONE network (`net`): pts [n_rows, N, 3], one view
+ * direction per row (viewdirs [n_rows, 3], used as given), hist [hist_rows, hist_bin] with hist_rows 1 or n_rows (fine network; ignored
+ * and may be NULL for the coarse one) -> raw [n_rows, N, 9] (fine) / [n_rows, N, 4] = (static_rgb, static_sigma) (coarse), exactly that
+ * many floats written; the workspace keeps what the backward needs.  dfn_nerfh_points_train_backward: grad_raw = d L / d raw (same
+ * shape, POST-activation) -> the gradient of every parameter of that network and, for the fine one, of both embedding tables,
+ * overwritten (not accumulated); tensors of the other network are never touched.  `params` / `grads`: the arrays of
+ * dfn_nerfh_train_param_name; entries of the network not asked for may be NULL.  The weights are split at the operand scale of the
+ * last dfn_nerfh_commit; a query whose operands left that range leaves ZEROS in its gradients and raises the handle's range flag, as
+ * a fused step does.  Several queries may be in flight on one handle, each on its own workspace; a backward reads the weights its
+ * network's LAST forward packed.  Stored planes follow the train mode (fine: one, or two under DFN_TRAIN_FUSED_SPLIT; coarse: two), and
+ * so does the workspace size: forward, backward and the size query of one workspace run in the same mode.
+ * Netwidth 128, fused modes only (another width or DFN_TRAIN_EXACT: DFN_ERR_UNSUPPORTED — there is no layer-by-layer points path).
+ * DFN_ERR_ARG: null handle or pointer, N < 1, unknown net, hist_rows not 1 or n_rows, n_rows * N >= 2^31, workspace too small;
+ * DFN_ERR_STATE: uncommitted handle, backward with no forward on the handle; n_rows == 0 is DFN_OK. */
+enum { DFN_NET_COARSE = 0, DFN_NET_FINE = 1 };
+size_t dfn_nerfh_points_train_workspace_bytes(dfn_nerfh_t h, int net, size_t n_rows, int N);
+int dfn_nerfh_points_train_forward(dfn_nerfh_t h, int net, const float* const* params, const float* pts, const float* viewdirs,
+                                   const float* hist, size_t hist_rows, size_t n_rows, int N, float* raw,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+int dfn_nerfh_points_train_backward(dfn_nerfh_t h, int net, const float* const* params, const float* hist, size_t hist_rows,
+                                    size_t n_rows, int N, const float* raw, const float* grad_raw, float* const* grads,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* Test-time render_rays for ANY netwidth on the same layer-by-layer exact-fp32 path (the register-resident kernels
  * behind dfn_render_rays exist for netwidth 128 and 256): models/rendering.py:245-337 with test_time=True, from
  * the handle's committed parameters.  raw [n_rays, Nc+Ni, 9] is required (output and scratch). */
