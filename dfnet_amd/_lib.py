@@ -76,6 +76,9 @@ SIGNATURES = {
     "dfn_nerfh_destroy": (c_int, [_P]),
     "dfn_nerfh_set_param": (c_int, [_P, c_char_p, _P, c_size_t]),
     "dfn_nerfh_commit": (c_int, [_P]),
+    "dfn_nerfh_recommit_device": (c_int, [_P, _P, _P]),
+    "dfn_nerfh_packed_buffer": (c_int, [_P, c_int, POINTER(c_char_p), POINTER(c_void_p), POINTER(c_size_t), POINTER(c_float)]),
+    "dfn_nerfh_recommit_selfcheck": (c_int, [c_int]),
     "dfn_feature_cosine_state_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dfn_feature_cosine_forward": (c_int, [_P, c_size_t, _P, c_size_t, _P, c_int, c_int, c_int, c_size_t, _P, _P, c_size_t, _P]),
     "dfn_feature_cosine_backward": (c_int, [_P, c_size_t, _P, c_size_t, _P, c_int, c_int, c_int, c_size_t, _P, _P, _P, c_size_t, _P]),

@@ -2,6 +2,7 @@
 // nerfh_train_api.hip (training path, generic-width path).
 #pragma once
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -17,6 +18,16 @@ struct PackedNet {
   float in_scale = 1.f;  // split-f16: weight scale x activation scale carried by the accumulators
   char* res_blob = nullptr;   // kernel variant 7: the LDS-resident layers (blob / tab then hold the streamed units only)
   uint32_t res_bytes = 0;
+};
+
+// One device buffer of the last dfn_nerfh_commit, in commit order (dfn_nerfh_packed_buffer, dfn_nerfh_recommit_device).
+// net: index of its PackedNet (nerfh_net_at; -1: extra, gen_blob); scale: dfn::recommit scale class of a split-f16 buffer, else -1.
+struct PackedBufInfo {
+  std::string name;
+  void* ptr = nullptr;
+  size_t bytes = 0;
+  int net = -1;
+  int scale = -1;
 };
 
 struct dfn_nerfh_s {
@@ -58,5 +69,26 @@ struct dfn_nerfh_s {
   bool train_exact = false;    // dfn_nerfh_set_train_mode: run the training step on the layer-by-layer exact-fp32 products even at netwidth 128
   hipStream_t side_stream = nullptr;
   hipEvent_t side_ev[2] = {nullptr, nullptr};
+  std::vector<PackedBufInfo> bufs;     // the buffers the last commit produced
+  std::set<std::string> stale_params;  // host copies (params) a device re-commit left behind: dfn_nerfh_commit waits for all of them to be set again
+  void* recommit = nullptr;            // dfn::recommit::State: the uploaded plan of dfn_nerfh_recommit_device (built on its first call)
 };
+
+// Every PackedNet of a handle under one index: net[f][prec][var], half_maps, bwd, bwd_coarse, cstatic, bwd_cstatic.
+constexpr int kNerfhNets = 2 * 3 * dfn::kVariants + 1 + 4 * 3;
+inline PackedNet* nerfh_net_at(dfn_nerfh_s* h, int i) {
+  constexpr int nv = 2 * 3 * dfn::kVariants;
+  if (i < 0 || i >= kNerfhNets) return nullptr;
+  if (i < nv) return &h->net[0][0][0] + i;
+  i -= nv;
+  if (i == 0) return &h->half_maps;
+  i -= 1;
+  PackedNet* groups[4] = {h->bwd, h->bwd_coarse, h->cstatic, h->bwd_cstatic};
+  return groups[i / 3] + i % 3;
+}
+inline int nerfh_net_index(dfn_nerfh_s* h, const PackedNet* n) {
+  for (int i = 0; i < kNerfhNets; ++i)
+    if (nerfh_net_at(h, i) == n) return i;
+  return -1;
+}
 

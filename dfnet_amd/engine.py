@@ -109,6 +109,8 @@ class NerfHEngine:
         self._ws = None
         self.lindisp = False
         self.coarse_f16 = False
+        self._param_numel = None     # {canonical name: numel} of the last load_numpy (None: never committed)
+        self.device_commits = 0      # load_device() calls that re-packed the engine on the GPU
 
     def set_render_options(self, lindisp=False, coarse_f16=None):
         """render_rays options that every entry point of this handle applies (dfn_nerfh_set_render_options): lindisp = coarse
@@ -140,7 +142,67 @@ class NerfHEngine:
             check(self.lib.dfn_nerfh_set_param(self.handle, name.encode(), a.ctypes.data_as(ctypes.c_void_p), a.size),
                   f"dfn_nerfh_set_param({name})")
         check(self.lib.dfn_nerfh_commit(self.handle), "dfn_nerfh_commit")
+        self._param_numel = {name: int(np.asarray(arr).size) for name, arr in items}
         return self
+
+    def _canonical_names(self):
+        return [self.lib.dfn_nerfh_train_param_name(i).decode() for i in range(self.lib.dfn_nerfh_train_param_count())]
+
+    def device_ready(self, tensors):
+        """Can load_device() take these tensors: the engine has been committed once on the host (load_numpy) and every tensor is a
+        contiguous fp32 CUDA tensor of its parameter's size, in canonical order."""
+        if self._param_numel is None or tensors is None:
+            return False
+        names = self._canonical_names()
+        return len(tensors) == len(names) and all(
+            t is not None and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == self._param_numel[k]
+            for k, t in zip(names, tensors))
+
+    def load_device(self, tensors):
+        """Re-commit from tensors that live on the GPU (dfn_nerfh_recommit_device): `tensors` in the canonical order of
+        dfn_nerfh_train_param_name(), contiguous fp32 CUDA tensors.  Every packed buffer of the engine is rewritten in place on the
+        current stream, byte for byte what load_numpy would have packed from the same values; nothing goes through the host except
+        one 8-byte read of the two weight maxima (one wait for the current stream at netwidth 128 and 256).  Refused before a first
+        load_numpy (the host commit lays the buffers out).  Work on other streams that reads this engine is the caller's to order."""
+        names = self._canonical_names()
+        if len(tensors) != len(names):
+            raise ValueError(f"load_device: {len(tensors)} tensors, the NeRF-H layout has {len(names)} parameters")
+        for k, t in zip(names, tensors):
+            if t is None:
+                continue   # the library refuses a null entry by name
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError(f"load_device: parameter {k} must be a contiguous fp32 CUDA tensor")
+            if self._param_numel is not None and t.numel() != self._param_numel[k]:
+                raise ValueError(f"load_device: parameter {k} has {t.numel()} elements, the engine was committed with {self._param_numel[k]}")
+        ptrs = (ctypes.c_void_p * len(names))(*[None if t is None else t.data_ptr() for t in tensors])
+        check(self.lib.dfn_nerfh_recommit_device(self.handle, ptrs, current_stream()), "dfn_nerfh_recommit_device")
+        self.device_commits += 1
+        return self
+
+    def module_tensors(self, network_fn, network_fine, embedding_a, embedding_t):
+        """The parameters of the four modules in canonical order (None when they do not make up the NeRF-H layout)."""
+        lookup = {}
+        for pre, mod in (("coarse.", network_fn), ("fine.", network_fine), ("embedding_a.", embedding_a), ("embedding_t.", embedding_t)):
+            for k, p in mod.named_parameters():
+                lookup[pre + k] = p.detach()
+        names = self._canonical_names()
+        return [lookup[k] for k in names] if len(lookup) == len(names) and all(k in lookup for k in names) else None
+
+    def load_modules_device(self, network_fn, network_fine, embedding_a, embedding_t):
+        """load_device() from torch modules with the reference's state_dict layout whose parameters live on the GPU."""
+        tensors = self.module_tensors(network_fn, network_fine, embedding_a, embedding_t)
+        if tensors is None:
+            raise ValueError("load_modules_device: the modules' parameters do not match the NeRF-H layout")
+        return self.load_device(tensors)
+
+    def packed_buffers(self):
+        """[(name, device pointer, bytes, in_scale)] of every device buffer of the last commit (dfn_nerfh_packed_buffer)."""
+        out, i = [], 0
+        name, ptr, nbytes, scale = ctypes.c_char_p(), ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_float()
+        while self.lib.dfn_nerfh_packed_buffer(self.handle, i, ctypes.byref(name), ctypes.byref(ptr), ctypes.byref(nbytes), ctypes.byref(scale)) == 0:
+            out.append((name.value.decode(), ptr.value, nbytes.value, scale.value))
+            i += 1
+        return out
 
     def load_modules(self, network_fn, network_fine, embedding_a, embedding_t):
         """Take the weights of torch modules with the reference's state_dict layout."""

@@ -30,6 +30,7 @@ def _f32c(t):
     return t.contiguous().float()
 
 
+DEVICE_RECOMMIT = True   # NerfHTrainer.recommit: re-pack the engine on the GPU from the master weights (False: through the host, load_numpy)
 TRAIN_MAP_NAMES = ("depth", "depth0")   # what ret_maps may name in training mode (rendering.py:241, fine and coarse pass)
 
 
@@ -292,8 +293,14 @@ class NerfHTrainer:
 
     def recommit(self):
         """Re-pack the engine from the live master weights: dfn_nerfh_commit re-derives the split-f16 operand scales, which is also
-        what the fused training chains scale the step's weights by (csrc/nerfh_fused_api.hip: train_scale)."""
-        sd = {k: p.detach().cpu().numpy() for k, p in zip(self.names, self.params)}
+        what the fused training chains scale the step's weights by (csrc/nerfh_fused_api.hip: train_scale).  DEVICE_RECOMMIT: on the
+        GPU from the master tensors themselves (NerfHEngine.load_device: the same bytes and scales, no host copy, the fused step keeps
+        its tables); with the switch off, or on an engine that was never packed, through the host."""
+        tensors = [p.detach() for p in self.params]
+        if DEVICE_RECOMMIT and self.engine.device_ready(tensors):
+            self.engine.load_device(tensors)
+            return
+        sd ={k: p.detach().cpu().numpy() for k, p in zip(self.names, self.params)}
         cut = lambda pre: {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
         self.engine.load_numpy(cut("coarse."), cut("fine."), sd["embedding_a.weight"], sd["embedding_t.weight"])
 

@@ -15,6 +15,8 @@ import torch.nn as nn
 from .engine import NerfHEngine
 from . import optim
 
+DEVICE_RECOMMIT = True   # HipQuery.refresh: re-pack the engine from the modules' CUDA parameters on the GPU (False: through the host, load_modules)
+
 img2mse = lambda x, y: torch.mean((x - y) ** 2)
 mse2psnr = lambda x: -10. * torch.log(x) / torch.log(torch.Tensor([10.]))
 
@@ -187,7 +189,13 @@ class HipQuery:
             return
         cur = self._versions()
         if self.stale or cur != self._packed_versions:
-            self.engine.load_modules(*self.modules)
+            # DEVICE_RECOMMIT: the parameters live on the GPU and the engine has been packed once, so it is re-packed there
+            # (NerfHEngine.load_device: no host copy, no host packer); otherwise, and with the switch off, through the host as before
+            tensors = self.engine.module_tensors(*self.modules) if DEVICE_RECOMMIT else None
+            if self.engine.device_ready(tensors):
+                self.engine.load_device(tensors)
+            else:
+                self.engine.load_modules(*self.modules)
             self.stale = False
             self._packed_versions = cur
 

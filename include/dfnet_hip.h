@@ -72,6 +72,29 @@ int dfn_nerfh_destroy(dfn_nerfh_t h);
 int dfn_nerfh_set_param(dfn_nerfh_t h, const char* name, const float* host, size_t numel);
 /* Pack all parameters into the MFMA fragment layouts and upload them (synchronous). */
 int dfn_nerfh_commit(dfn_nerfh_t h);
+/* Re-commit from parameters that already live on the device: rewrites IN PLACE every device buffer the last dfn_nerfh_commit
+ * produced (packed networks of every variant and precision, resident blobs, gradient blobs, the coarse training query's blobs, the
+ * per-ray-bias weights with their folded bias vectors, the plain copies of the generic path), byte for byte what dfn_nerfh_set_param
+ * x N + dfn_nerfh_commit would have produced from the same values, the split-f16 weight scales (in_scale) included.  Nothing is
+ * freed or allocated after the first call (which builds and uploads the plan of the handle's geometry, once per handle): every
+ * pointer stays what it was, unit tables are geometry and are not touched, the fused training step keeps its state.
+ * `params`: a HOST array of dfn_nerfh_train_param_count() DEVICE pointers (contiguous fp32) in the order of
+ * dfn_nerfh_train_param_name(), as the training entries take them.
+ * Everything is enqueued on `stream`; a caller with renders of this handle in flight on ANOTHER stream orders them against it itself,
+ * as for any buffer.  Netwidth 128 and 256: the weight scales are host floats handed to the kernels as arguments, so the call reduces
+ * the two maxima on the device and WAITS for `stream` once to read 8 bytes back before it enqueues the pack; other widths do not wait.
+ * Afterwards the host copies of dfn_nerfh_set_param are stale: dfn_nerfh_commit returns DFN_ERR_STATE until every parameter has been
+ * set again.  DFN_ERR_STATE: the handle was never committed on the host; DFN_ERR_ARG: params NULL or one of its entries NULL. */
+int dfn_nerfh_recommit_device(dfn_nerfh_t h, const float* const* params, void* stream);
+/* Read-only inspection: device buffer `index` of the last commit, in commit order -- its name, device pointer, size and the in_scale of
+ * the packed network it belongs to (1 for a buffer without one).  Any output may be NULL.  DFN_ERR_ARG past the end gives the count;
+ * DFN_ERR_STATE on an uncommitted handle. */
+int dfn_nerfh_packed_buffer(dfn_nerfh_t h, int index, const char** name, const void** device_ptr, size_t* bytes, float* in_scale);
+/* Host-only check of the device re-commit's plan for a netwidth (no device call, runs without a GPU): packs one fixed pseudo-random
+ * parameter set with the plan recorded, packs a second one, executes the plan on the host over the first set's buffers with the
+ * second set's values and compares every buffer byte for byte.  DFN_OK (dfn_last_error() then holds the plan's entry and byte
+ * counts), DFN_ERR_STATE with the first difference, DFN_ERR_ARG for a netwidth dfn_nerfh_create refuses. */
+int dfn_nerfh_recommit_selfcheck(int width);
 /* Options of render_rays that the reference passes as keyword arguments (rendering.py:245-256), applied by every entry point
  * that takes this handle until changed.  DFN_RENDER_LINDISP: the coarse depths are linear in disparity, z = 1 / ((1 - t) / near +
  * t / far) (rendering.py:272-273; near must be > 0).  white_bkgd is not offered: in the reference it reaches the coarse compositor
