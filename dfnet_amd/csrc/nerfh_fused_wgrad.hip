@@ -304,7 +304,7 @@ hipError_t launch_grads_guard(const GuardArgs& a, hipStream_t s) {
 
 // ------------------------------------------------------------------------------------------ per-step weight packing
 // Every f16 fragment element of a chain blob is one master weight (or zero): hi = f16(w x wscale), lo = f16(w x wscale - hi), as
-// the host packer of nerfh_api.hip writes them at commit; the bias fragments are fp32 x bscale.
+// the host packer of nerfh_pack.hip writes them at commit; the bias fragments are fp32 x bscale.
 __global__ __launch_bounds__(256) void pack_units4_kernel(PackArgs4 a) {
   const PackBlob& b = a.b[blockIdx.y];
   const int stride = gridDim.x * blockDim.x;

@@ -1,5 +1,5 @@
-// nerfh_handle.h — the NeRF-H handle behind dfn_nerfh_t, shared by nerfh_api.hip (test-time render path) and
-// nerfh_train_api.hip (training path, generic-width path).
+// nerfh_handle.h — the NeRF-H handle behind dfn_nerfh_t, shared by nerfh_pack.hip (its life and the host packer behind
+// dfn_nerfh_commit), nerfh_api.hip (test-time render path) and nerfh_train_api.hip (training path, generic-width path).
 #pragma once
 #include <map>
 #include <set>

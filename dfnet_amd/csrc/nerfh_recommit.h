@@ -1,4 +1,4 @@
-// nerfh_recommit.h — the device-side re-commit of a NeRF-H handle (dfn_nerfh_recommit_device): what nerfh_api.hip (the host packer,
+// nerfh_recommit.h — the device-side re-commit of a NeRF-H handle (dfn_nerfh_recommit_device): what nerfh_pack.hip (the host packer,
 // which emits the plan) and nerfh_recommit.hip (the kernels that execute it) share.
 //
 // A plan is the host packer's own record of where every packed element came from.  While dfn_nerfh_commit's packing code runs in plan
@@ -51,13 +51,19 @@ struct HostPlan {
   }
 };
 
-// sexp of dfn_nerfh_commit: the largest |w| of a network lands in (0.5, 1]
+// One power-of-two weight scale per network: the largest |w| lands in (0.5, 1].  The lo halves of most weights are then f16
+// subnormals — still exact to 2^-24 of the largest weight (the matrix cores do not flush f16 denormals), which is fp32's resolution —
+// and the accumulators (in_scale x the value = 16 x value / max|w|) fit f16 up to |value| = 4094 max|w|: that is what lets the render
+// kernels narrow BEFORE they scale (X3Piece: one packed multiply per result pair instead of two).
 inline float weight_scale(float wmax) {
   int sexp = wmax > 0.f ? -int(std::ceil(std::log2(wmax))) : 0;
   sexp = sexp < -8 ? -8 : (sexp > 24 ? 24 : sexp);
   return std::ldexp(1.f, sexp);
 }
-// in_scale of the four scale classes from the two maxima, with dfn_nerfh_commit's expressions
+// The scales of the four classes from the two maxima: the one place that states them, for the host packer (nerfh_pack.hip:
+// commit_core) and the device re-commit alike.  in_scale = weight scale x activation scale, what the accumulators carry.  The
+// gradient kernels scale their accumulators in fp32 BEFORE narrowing them (store_hidden), so their weights sit x 1024 higher, where
+// every lo half is a normal f16 (largest |w| near 2^10: 22 bits per weight) instead of at the render kernels' unit scale.
 inline void scales_from_max(const float wmax[2], float in_scale[kScales], float wscale[kScales]) {
   for (int f = 0; f < 2; ++f) {
     in_scale[f] = weight_scale(wmax[f]) * kX3ActScale;
@@ -121,9 +127,9 @@ DFN_HD inline size_t arena_off(int pseudo, int W) {
 DFN_HD inline size_t arena_floats(int W) { return arena_off(kPseudo, W); }
 // fold k of 3: A = parameter a [W/2][lda], F / bF = xyz_encoding_final of the same network, bA = A's bias (canonical indices)
 struct FoldSpec { int a, F, bF, bA, lda; };
-void fold_specs(const dfn_nerfh_desc& desc, FoldSpec out[3]);   // nerfh_api.hip
+void fold_specs(const dfn_nerfh_desc& desc, FoldSpec out[3]);   // nerfh_pack.hip
 
-// nerfh_api.hip: run the packer in plan mode over a scratch parameter set of the handle's geometry (no device call)
+// nerfh_pack.hip: run the packer in plan mode over a scratch parameter set of the handle's geometry (no device call)
 int build_plan(const dfn_nerfh_desc& desc, HostPlan& plan, std::vector<BufShape>& shapes);
 // nerfh_recommit.hip: frees the uploaded plan of a handle (dfn_nerfh_destroy)
 void destroy_state(dfn_nerfh_s* h);

@@ -2,6 +2,7 @@
 host-only selfcheck executes the packer's plan against the packer's values byte for byte, and arguments are refused before any
 device work."""
 import ctypes
+import json
 import os
 import re
 
@@ -40,6 +41,18 @@ def test_selfcheck_plan_reproduces_the_packer(width):
     text = lib.dfn_last_error().decode()
     assert f"netwidth {width}:" in text and "bytes written per re-commit" in text
     print(text)
+
+
+@pytest.mark.parametrize("width", [128, 256, 64])
+def test_packer_output_matches_the_recorded_digest(width):
+    """Every packed buffer of the selfcheck's parameter set B -- name, size, bytes, unit table, unit counts, in_scale, in enumeration
+    order -- hashes to the digest recorded in tests/golden/pack_digest.json: a change of the host packer's output shows here."""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "pack_digest.json")))["digest"]
+    lib = _lib.load()
+    assert lib.dfn_nerfh_recommit_selfcheck(width) == 0, lib.dfn_last_error().decode()
+    m = re.search(r"packed digest ([0-9a-f]{16})$", lib.dfn_last_error().decode())
+    assert m, "the selfcheck's text carries no digest"
+    assert m.group(1) == golden[str(width)]
 
 
 def test_selfcheck_refuses_an_odd_width():
