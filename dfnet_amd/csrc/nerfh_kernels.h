@@ -65,6 +65,9 @@ hipError_t launch_mlp_pe(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t s
 // formed at the use instead of parked in VGPR lanes.  Variant 9's arguments otherwise.
 // fine = false is refused: the coarse kernel has no per-ray seeds and stays launch_mlp_pe's.
 hipError_t launch_mlp_hoist(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
+// Kernel variant 11 (nerfh_mlp_sel.hip): variant 10's fine kernel (fine = true: the scaled table, as launch_mlp_hoist) and variant 9's
+// coarse kernel (fine = false) with one select per head value.  Variant 9's arguments.
+hipError_t launch_mlp_sel(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
 
 // The points flavour (nerfh_mlp_pts*.hip): a.rays_o is pts [n_rays, n_samples, 3] (n_rays = query rows), a.rays_d, a.z and a.partial
 // are unused (a.partial must be null: the raw route only), a.ray_bias has one row per query row.  launch_mlp_pts: f16 / exact fp32 at

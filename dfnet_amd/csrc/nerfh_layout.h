@@ -158,7 +158,7 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //   variant 1: 4 waves per workgroup, 2 workgroups per CU, a unit = 2 M-blocks (f16) / one M-block (f32)
 //   variant 2: 4 waves per workgroup x 3 point blocks, 1 workgroup per CU (1 wave per SIMD, 512 VGPRs), unit as variant 0
 //   variant 3: variant 0's geometry without the pipelined epilogue (A/B reference)
-// 4 to 10 exist in split-f16 at netwidth 128 only and each is the one before it with one thing more (kVariantFacts); every other
+// 4 to 11 exist in split-f16 at netwidth 128 only and each is the one before it with one thing more (kVariantFacts); every other
 // arithmetic mode, width and gradient path under them runs the `base` variant's kernels on its networks, and which kernel, network and
 // per-ray table a call runs is nerfh_route.h:
 //   variant 4: variant 0 on 16x16x32 MFMAs (PrecX3M16)
@@ -186,6 +186,12 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //              parked in VGPR lanes and read back by v_readlane_b32 (79 -> 39 parked SGPRs, 231 -> 62 lane reads per tile).  The same
 //              values by the same arithmetic: variant 9's outputs bit for bit, on its networks, resident blob and counters.  The
 //              coarse kernel has no RAYBIAS layer and parks nothing: variant 9's runs
+//   variant 11: variant 10 with the head values of a PrecX3M16 head block SELECTED by one v_cndmask_b32 each (nerfh_mlp_sel.hip;
+//              layer() in nerfh_mlp_core.h: the two candidates go through an opaque copy, so the select of two extracted elements is
+//              not rewritten as one extract with a lane-dependent index -- a chain of 15 compares and 16 selects per index register,
+//              whose masks were the scalar pressure variant 10 fought: 4 023 -> 3 754 vector instructions per fine tile, 39 -> 0
+//              parked SGPRs).  The same value on the same lane: variant 10's outputs bit for bit, on its networks, resident blob,
+//              scaled table and counters.  The unit has a coarse kernel too (variant 9's code with the select: 2 728 -> 2 707)
 constexpr int kVariants = 8;   // packed networks per (coarse | fine, arithmetic): dfn_nerfh_s::net
 constexpr int kFoldVariant = 5;
 constexpr int kHalfVariant = 6;
@@ -193,9 +199,11 @@ constexpr int kResidentVariant = 7;
 constexpr int kDynVariant = 8;
 constexpr int kKeptVariant = 9;
 constexpr int kHoistVariant = 10;
-constexpr int kLastVariant = kHoistVariant;   // DFN_MLP_VARIANT = 0 .. kLastVariant
-// kept: the encoding, for the skip concat; hoisted: the fused fine kernel is nerfh_mlp_hoist.hip's and its per-ray table holds in_scale x the seeds
-struct VariantFacts { int base; bool fold, half, resident, claimed, kept, hoisted; };
+constexpr int kSelVariant = 11;
+constexpr int kLastVariant = kSelVariant;   // DFN_MLP_VARIANT = 0 .. kLastVariant
+// kept: the encoding, for the skip concat; hoisted: the fused fine kernel is nerfh_mlp_hoist.hip's and its per-ray table holds in_scale x the seeds;
+// sel: the coarse and the fused fine kernel are nerfh_mlp_sel.hip's (the fine one reads the scaled table as variant 10's)
+struct VariantFacts { int base; bool fold, half, resident, claimed, kept, hoisted, sel; };
 constexpr VariantFacts kVariantFacts[kLastVariant + 1] = {
     {0, false, false, false, false}, {1, false, false, false, false}, {2, false, false, false, false}, {3, false, false, false, false},
     {4, false, false, false, false},
@@ -205,9 +213,10 @@ constexpr VariantFacts kVariantFacts[kLastVariant + 1] = {
     {4, true, true, true, true},      // kDynVariant
     {4, true, true, true, true, true},   // kKeptVariant
     {4, true, true, true, true, true, true},   // kHoistVariant: variant 9's row (its plain kernels are variant 4's too) and the new fact
+    {4, true, true, true, true, true, true, true},   // kSelVariant: variant 10's row and the new fact
 };
 // What a process runs without DFN_MLP_VARIANT; the variant whose kernels the point queries run whatever it says
-constexpr int kSelectedByDefault = kHoistVariant;
+constexpr int kSelectedByDefault = kSelVariant;
 constexpr int kDefaultVariant = kResidentVariant;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));

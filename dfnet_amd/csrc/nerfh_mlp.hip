@@ -40,9 +40,11 @@ namespace dfn {
 //   DFN_MLP_HOIST_TU  variant 10, on PE: the fine kernel's per-ray seeds are stored at the accumulators' scale (layer(): RAYBIAS takes
 //                     them as loaded) and uniform values are formed at their use (wave_here / args_here below, stage_issue_at),
 //                     MlpDynArgs; the unit has no coarse kernel (variant 9's runs)
+//   DFN_MLP_SEL_TU    variant 11, on HOIST: one select per head value (layer(): the candidates behind an opaque copy), coarse and fine,
+//                     MlpDynArgs; the coarse kernel is variant 9's code under the unit's flags
 //   DFN_MLP_STATIC_TU the coarse network's training query (nerfw.py:47-60, 326-343), on PTS, plain or FOLD: the fine kernel cut off
 //                     behind static_rgb (kCoarseStaticSeq / kCoarseStaticFoldSeq), 4 floats per point; the unit has that kernel alone
-// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn|_pe|_hoist][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn|_pe|_hoist];
+// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn|_pe|_hoist|_sel][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn|_pe|_hoist|_sel];
 // DFN_MLP_STATIC_TU: nerfh_coarse_static[_fold]_pts_kernel, launch_mlp_static_pts[_fold].
 #if defined(DFN_MLP_STATIC_TU) && (!defined(DFN_MLP_PTS_TU) || defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_MAPS_TU))
 #error "the static query exists in the points flavour, plain or folded"
@@ -59,7 +61,13 @@ namespace dfn {
 #if defined(DFN_MLP_HOIST_TU) && !defined(DFN_MLP_PE_TU)
 #error "the hoisted per-tile work is taken out of the kernels with the kept encoding"
 #endif
-#if defined(DFN_MLP_HOIST_TU)
+#if defined(DFN_MLP_SEL_TU) && !defined(DFN_MLP_HOIST_TU)
+#error "the selected head values exist in the unit with the hoisted per-tile work"
+#endif
+#if defined(DFN_MLP_SEL_TU)
+#define DFN_TU_TAG _sel
+#define DFN_MLP_KARGS MlpDynArgs
+#elif defined(DFN_MLP_HOIST_TU)
 #define DFN_TU_TAG _hoist
 #define DFN_MLP_KARGS MlpDynArgs
 #elif defined(DFN_MLP_PE_TU)
@@ -800,8 +808,10 @@ hipError_t DFN_LAUNCH_MLP(bool fine, int prec, const MlpArgs& a, int n_cu, hipSt
 // launch_mlp_pe: variant 9's, variant 8's arguments, LDS map and grid (this body under DFN_MLP_PE_TU: nerfh_mlp_pe.hip).
 // launch_mlp_hoist: variant 10's fine kernel, variant 9's arguments, LDS map and grid; a.ray_bias holds in_scale x the seeds
 // (nerfh_mlp_hoist.hip); no coarse kernel.
+// launch_mlp_sel: variant 11's two kernels (nerfh_mlp_sel.hip): launch_mlp_hoist's fine kernel and launch_mlp_pe's coarse kernel with one
+// select per head value, their arguments, LDS map and grid.
 hipError_t DFN_LAUNCH_MLP(bool fine, const DFN_MLP_KARGS& a, int n_cu, hipStream_t stream) {
-#ifdef DFN_MLP_HOIST_TU
+#if defined(DFN_MLP_HOIST_TU) && !defined(DFN_MLP_SEL_TU)
   void (*kern)(DFN_MLP_KARGS) = fine ? DFN_FINE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true> : nullptr;
 #else
   void (*kern)(DFN_MLP_KARGS) = fine ? DFN_FINE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true> : DFN_COARSE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true>;

@@ -771,7 +771,18 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
 #pragma unroll
               for (int c = 0; c < 8; ++c) {
                 if (HALF && c >= 4) head[nb][c] = 0.f;   // half 1 was not computed (fragments q = nb only)
+#ifdef DFN_MLP_SEL_TU
+                // kernel variant 11: the two candidates behind an opaque copy.  The select of two extractelements of one vector is
+                // otherwise folded into one extract with a lane-dependent index, and an f32x16 in VGPRs has no indexed read: 15
+                // v_cmp_eq_u32 + 16 v_cndmask_b32 per index register, the 15 masks held in SGPR pairs.  This is one v_cndmask_b32.
+                else {
+                  float a0 = v[8 * (c >> 2) + (c & 3)], a1 = v[8 * (c >> 2) + 4 + (c & 3)];
+                  asm("" : "+v"(a0), "+v"(a1));
+                  head[nb][c] = g1 ? a1 : a0;
+                }
+#else
                 else head[nb][c] = g1 ? v[8 * (c >> 2) + 4 + (c & 3)] : v[8 * (c >> 2) + (c & 3)];
+#endif
               }
             }
           }
