@@ -89,6 +89,9 @@ SIGNATURES = {
     "dfn_nerfh_range_status": (c_int, [_P, POINTER(c_int), _P]),
     "dfn_nerfh_range_status_async": (c_int, [_P, _P, _P]),
     "dfn_ndc_rays": (c_int, [c_int, c_int, c_float, c_float, _P, _P, c_size_t, _P, _P, _P]),
+    # models/ray_utils.py:27-44 and rendering.py:364-371 under autograd: the adjoints of ndc_rays and of viewdirs = d / |d|
+    "dfn_ndc_rays_backward": (c_int, [c_int, c_int, c_float, c_float, _P, _P, c_size_t, _P, _P, _P, _P, _P]),
+    "dfn_viewdirs_backward": (c_int, [_P, _P, c_size_t, c_int, _P, _P]),
     "dfn_sample_fine_opt": (c_int, [_P, c_size_t, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P]),
     "dfn_raygen": (c_int, [c_int, c_int, c_float, _P, _P, _P, _P, _P]),
     "dfn_raygen_frames": (c_int, [c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P]),
@@ -184,6 +187,12 @@ SIGNATURES = {
     "dfn_nerfh_train_tables_selfcheck": (c_int, [_P]),
     "dfn_nerfh_train_forward": (c_int, [_P, POINTER(c_void_p), _P, _P, _P, c_size_t, c_size_t, c_int, c_int, c_float, c_float,
                                         _P, _P, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "dfn_nerfh_train_forward_v": (c_int, [_P, POINTER(c_void_p), _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, c_float, c_float,
+                                          _P, _P, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "dfn_nerfh_train_backward_rays_v": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, _P, c_float, _P, _P, _P, _P, c_float, _P,
+                                                _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
+    "dfn_nerfh_train_backward_rays_maps_v": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_size_t, c_int, c_int, _P, c_float, _P,
+                                                     POINTER(TrainMapGrads), c_float, _P, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
     "dfn_nerfw_loss": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_int, c_float, c_float, _P, _P, _P, _P, _P]),
     "dfn_nerfh_train_backward": (c_int, [_P, POINTER(c_void_p), _P, c_size_t, c_size_t, c_int, c_int, _P, c_float, _P, _P, _P, _P,
                                          c_float, _P, POINTER(c_void_p), _P, c_size_t, _P]),

@@ -301,6 +301,27 @@ extern "C" int dfn_ndc_rays(int H, int W, float focal, float near, const float* 
   return DFN_OK;
 }
 
+extern "C" int dfn_ndc_rays_backward(int H, int W, float focal, float near, const float* rays_o, const float* rays_d, size_t n,
+                                     const float* grad_ndc_o, const float* grad_ndc_d, float* grad_rays_o, float* grad_rays_d,
+                                     void* stream) {
+  if (!n) return DFN_OK;
+  if (!rays_o || !rays_d || !grad_rays_o || !grad_rays_d || H < 1 || W < 1 || !(focal > 0.f))
+    return set_error(DFN_ERR_ARG, "dfn_ndc_rays_backward: bad argument");
+  if (!grad_ndc_o && !grad_ndc_d)
+    return set_error(DFN_ERR_ARG, "dfn_ndc_rays_backward: bad argument (neither grad_ndc_o nor grad_ndc_d is given)");
+  CHECK_HIP(launch_ndc_rays_backward(H, W, focal, near, rays_o, rays_d, n, grad_ndc_o, grad_ndc_d, grad_rays_o, grad_rays_d, HS(stream)),
+            "dfn_ndc_rays_backward");
+  return DFN_OK;
+}
+
+extern "C" int dfn_viewdirs_backward(const float* rays_d, const float* grad_viewdirs, size_t n, int accumulate, float* grad_rays_d,
+                                     void* stream) {
+  if (!n) return DFN_OK;
+  if (!rays_d || !grad_viewdirs || !grad_rays_d) return set_error(DFN_ERR_ARG, "dfn_viewdirs_backward: bad argument (null pointer)");
+  CHECK_HIP(launch_viewdirs_backward(rays_d, grad_viewdirs, n, accumulate, grad_rays_d, HS(stream)), "dfn_viewdirs_backward");
+  return DFN_OK;
+}
+
 extern "C" int dfn_upsample_bicubic(const float* in, int H, int W, int C, int outH, int outW, float* out, void* stream) {
   if (!in || !out || H < 1 || W < 1 || C < 1 || outH < 1 || outW < 1) return set_error(DFN_ERR_ARG, "dfn_upsample_bicubic: bad argument");
   CHECK_HIP(launch_bicubic(in, H, W, C, outH, outW, out, HS(stream)), "dfn_upsample_bicubic");

@@ -543,15 +543,15 @@ ChainArgs chain_args(const dfn_nerfh_s* h, const State& st, bool fine, int pass,
 // (sized for the larger layout, so that a workspace stays valid across dfn_nerfh_set_train_mode)
 size_t workspace_bytes(const dfn_nerfh_s* h, size_t R, int Nc, int Ni) { return carve(nullptr, h->desc, R, Nc, Ni, true).total; }
 
-int train_forward(dfn_nerfh_s* h, const float* const* params, const float* rays_o, const float* rays_d, const float* hist, size_t hist_rows,
-                  size_t R, int Nc, int Ni, float near, float far, const float* t_rand, const float* noise, float raw_noise_std,
+int train_forward(const char* fn, dfn_nerfh_s* h, const float* const* params, const float* rays_o, const float* rays_d,
+                  const float* viewdirs, const float* hist, size_t hist_rows, size_t R, int Nc, int Ni, float near, float far, const float* t_rand, const float* noise, float raw_noise_std,
                   const float* u, float* rgb, float* disp, float* acc, float* raw, float* rgb0, float* disp0, float* acc0, float* z_std,
                   float* beta, void* workspace, size_t workspace_bytes_, hipStream_t s) {
   if (!h->fused)
     if (int rc = build_state(h)) return rc;
   const State& st = *static_cast<State*>(h->fused);
   const Ws w = carve(static_cast<char*>(workspace), h->desc, R, Nc, Ni, h->train_split_fine);
-  if (w.total > workspace_bytes_) return set_error(DFN_ERR_ARG, "dfn_nerfh_train_forward: workspace too small (%zu < %zu)", workspace_bytes_, w.total);
+  if (w.total > workspace_bytes_) return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes_, w.total);
   const Geo g = geo_of(h->desc);
   const dfn_nerfh_desc& d = h->desc;
   const int Nf = Nc + Ni, W = kWidth;
@@ -562,7 +562,7 @@ int train_forward(dfn_nerfh_s* h, const float* const* params, const float* rays_
   const int n_cu = device_cu_count();
   {   // view directions, both networks' per-ray input rows, the stratified coarse depths, the step's range word cleared: one launch
     TrainRayPrepArgs pa{};
-    pa.rays_d = rays_d; pa.R = R;
+    pa.rays_d = rays_d; pa.R = R; pa.viewdirs = viewdirs;
     pa.hist = hist; pa.hist_rows = hist_rows; pa.emb_a = emb_a; pa.emb_t = emb_t;
     pa.hist_bin = d.hist_bin; pa.dim_a = d.dim_a; pa.dim_t = d.dim_t; pa.n_vocab = d.n_vocab;
     pa.view = w.view; pa.dir_c = w.dir_c; pa.ld_dc = g.ld_dc; pa.dir_f = w.dir_f; pa.ld_df = g.ld_df; pa.t_in = w.t_in; pa.ld_t = g.ld_t;

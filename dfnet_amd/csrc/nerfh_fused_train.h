@@ -188,8 +188,9 @@ hipError_t launch_frag_ray_sum_pair(const char* arr_f, int kc_f, int planes_f, c
 struct State;
 bool available(const dfn_nerfh_s* h);
 size_t workspace_bytes(const dfn_nerfh_s* h, size_t n_rays, int Nc, int Ni);
-int train_forward(dfn_nerfh_s* h, const float* const* params, const float* rays_o, const float* rays_d, const float* hist, size_t hist_rows,
-                  size_t n_rays, int Nc, int Ni, float near, float far, const float* t_rand, const float* noise, float raw_noise_std,
+// fn: the calling entry's name (messages); viewdirs [n_rays,3]: view directions used as given, nullptr = rays_d normalised
+int train_forward(const char* fn, dfn_nerfh_s* h, const float* const* params, const float* rays_o, const float* rays_d,
+                  const float* viewdirs, const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far, const float* t_rand, const float* noise, float raw_noise_std,
                   const float* u, float* rgb, float* disp, float* acc, float* raw, float* rgb0, float* disp0, float* acc0, float* z_std,
                   float* beta, void* workspace, size_t workspace_bytes, hipStream_t s);
 // fn: the calling entry's name (messages); cg: what the compositing-backward stage starts from (train::composite_backward) — everything

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void ray_grad_reduce_kernel(const float* __res
       for (int c = 0; c < 3; ++c) {
         grad_o[ray * 3 + c] = so[c] + (accumulate ? grad_o[ray * 3 + c] : 0.f);
         grad_d[ray * 3 + c] = sd[c] + (accumulate ? grad_d[ray * 3 + c] : 0.f);
-        if (grad_v) grad_v[ray * 3 + c] = sv[c];
+        if (grad_v) grad_v[ray * 3 + c] = sv[c] + (accumulate ? grad_v[ray * 3 + c] : 0.f);
       }
     }
   }

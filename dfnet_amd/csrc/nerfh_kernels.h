@@ -91,6 +91,12 @@ hipError_t launch_raygen(int H, int W, float focal, const float* c2w, float* ray
 hipError_t launch_viewdirs(const float* rays_d, size_t n, float* viewdirs, hipStream_t stream);
 hipError_t launch_ndc_rays(int H, int W, float focal, float near, const float* rays_o, const float* rays_d, size_t n, float* out_o,
                            float* out_d, hipStream_t stream);
+// the adjoints of ndc_rays (grad_ndc_o / grad_ndc_d: either may be nullptr = zeros; outputs must not alias inputs) and of v = d / |d|
+hipError_t launch_ndc_rays_backward(int H, int W, float focal, float near, const float* rays_o, const float* rays_d, size_t n,
+                                    const float* grad_ndc_o, const float* grad_ndc_d, float* grad_rays_o, float* grad_rays_d,
+                                    hipStream_t stream);
+hipError_t launch_viewdirs_backward(const float* rays_d, const float* grad_viewdirs, size_t n, int accumulate, float* grad_rays_d,
+                                    hipStream_t stream);
 hipError_t launch_posenc(const float* x, size_t n, int L, int mode, float* out, hipStream_t stream);
 
 struct RayBiasWeights {       // device pointers, fp32
@@ -198,7 +204,8 @@ struct MapGrads {
 hipError_t launch_composite_fine_backward_all(const float* raw, const float* z, size_t n_rays, int Nf, float beta_min, const MapGrads& g,
                                               float* graw, hipStream_t stream, const float* grad_raw_ext = nullptr);
 // Per-ray reduction of the per-sample gradients: d o = sum g, d d = sum z g (+ viewdir normalisation when
-// `derive_viewdirs`), d viewdirs = sum gv (when grad_viewdirs != nullptr).  accumulate: add to what grad_o / grad_d hold.
+// `derive_viewdirs`), d viewdirs = sum gv (when grad_viewdirs != nullptr).  accumulate: add to what grad_o / grad_d
+// (and grad_viewdirs) hold.
 hipError_t launch_ray_grad_reduce(const float* gpts, const float* z, const float* rays_d, size_t n_rays, int Nf,
                                   int derive_viewdirs, float* grad_o, float* grad_d, float* grad_viewdirs,
                                   hipStream_t stream, int accumulate = 0);

@@ -108,6 +108,67 @@ hipError_t launch_ndc_rays(int H, int W, float focal, float near, const float* r
   return hipGetLastError();
 }
 
+// Vector-Jacobian product of ndc_rays (models/ray_utils.py:27-44 under autograd): d L/d (o, d) from d L/d (o', d').  The shifted origin
+// has o_z + t d_z = -near identically, so the third components of o' and d' are constants, and with e = Go' - Gd' (d'_x = sx d_x/d_z -
+// o'_x):  a = e_x sx / (-near) = d L/d (o_x + t d_x),  b likewise,  gt = a d_x + b d_y = d L/d t,  t = -(near + o_z) / d_z:
+//   g_o = (a, b, -gt / d_z)
+//   g_d = (a t + Gd'_x sx / d_z,  b t + Gd'_y sy / d_z,  gt (near + o_z) / d_z^2 - (Gd'_x sx d_x + Gd'_y sy d_y) / d_z^2)
+// go / gd: either may be nullptr (zeros).  One thread per ray; no guard for d_z == 0 (the reference gives inf there too).
+__global__ __launch_bounds__(256) void ndc_rays_backward_kernel(float sx, float sy, float near, const float* __restrict__ ro,
+                                                                const float* __restrict__ rd, size_t n, const float* __restrict__ go,
+                                                                const float* __restrict__ gd, float* __restrict__ grad_o,
+                                                                float* __restrict__ grad_d) {
+  for (size_t r = blockIdx.x * size_t(blockDim.x) + threadIdx.x; r < n; r += size_t(gridDim.x) * blockDim.x) {
+    const float dx = rd[r * 3], dy = rd[r * 3 + 1], dz = rd[r * 3 + 2], oz = ro[r * 3 + 2];
+    const float gox = go ? go[r * 3] : 0.f, goy = go ? go[r * 3 + 1] : 0.f;
+    const float gdx = gd ? gd[r * 3] : 0.f, gdy = gd ? gd[r * 3 + 1] : 0.f;
+    const float inv_z = 1.f / dz;
+    const float t = -(near + oz) * inv_z;
+    const float a = (gox - gdx) * sx / -near, b = (goy - gdy) * sy / -near;
+    const float gt = a * dx + b * dy;
+    const float px = gdx * sx * inv_z, py = gdy * sy * inv_z;   // d L/d (d_x / d_z), d L/d (d_y / d_z), over d_z
+    grad_o[r * 3] = a;
+    grad_o[r * 3 + 1] = b;
+    grad_o[r * 3 + 2] = -gt * inv_z;
+    grad_d[r * 3] = a * t + px;
+    grad_d[r * 3 + 1] = b * t + py;
+    grad_d[r * 3 + 2] = (-gt * t - (px * dx + py * dy)) * inv_z;
+  }
+}
+hipError_t launch_ndc_rays_backward(int H, int W, float focal, float near, const float* rays_o, const float* rays_d, size_t n,
+                                    const float* grad_ndc_o, const float* grad_ndc_d, float* grad_rays_o, float* grad_rays_d,
+                                    hipStream_t stream) {
+  if (!n) return hipSuccess;
+  const float sx = float(-1. / (double(W) / (2. * double(focal)))), sy = float(-1. / (double(H) / (2. * double(focal))));
+  hipLaunchKernelGGL(ndc_rays_backward_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, sx, sy, near, rays_o, rays_d, n, grad_ndc_o,
+                     grad_ndc_d, grad_rays_o, grad_rays_d);
+  return hipGetLastError();
+}
+
+// Adjoint of v = d / |d| (rendering.py:366-371) as a stage of its own: grad_d (+)= (gv - v (v . gv)) / |d| — what
+// ray_grad_reduce_kernel folds in with derive_viewdirs (nerfh_grad_stages.hip), for a view direction that is a tensor of its own.
+__global__ __launch_bounds__(256) void viewdirs_backward_kernel(const float* __restrict__ d, const float* __restrict__ gv, size_t n,
+                                                                int accumulate, float* __restrict__ grad_d) {
+  for (size_t r = blockIdx.x * size_t(blockDim.x) + threadIdx.x; r < n; r += size_t(gridDim.x) * blockDim.x) {
+    const float d0 = d[r * 3], d1 = d[r * 3 + 1], d2 = d[r * 3 + 2];
+    float v0, v1, v2;
+    normalize3(d0, d1, d2, v0, v1, v2);
+    const float inv = 1.f / sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+    const float g0 = gv[r * 3], g1 = gv[r * 3 + 1], g2 = gv[r * 3 + 2];
+    const float dot = v0 * g0 + v1 * g1 + v2 * g2;
+    grad_d[r * 3] = (g0 - v0 * dot) * inv + (accumulate ? grad_d[r * 3] : 0.f);
+    grad_d[r * 3 + 1] = (g1 - v1 * dot) * inv + (accumulate ? grad_d[r * 3 + 1] : 0.f);
+    grad_d[r * 3 + 2] = (g2 - v2 * dot) * inv + (accumulate ? grad_d[r * 3 + 2] : 0.f);
+  }
+}
+hipError_t launch_viewdirs_backward(const float* rays_d, const float* grad_viewdirs, size_t n, int accumulate, float* grad_rays_d,
+                                    hipStream_t stream) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(viewdirs_backward_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, rays_d, grad_viewdirs, n, accumulate,
+                     grad_rays_d);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------ posenc (test entry)
 __global__ __launch_bounds__(256) void posenc_kernel(const float* __restrict__ x, size_t n, int L, int mode,
                                                      float* __restrict__ out) {

@@ -58,6 +58,7 @@ hipError_t posenc_points(const float* rays_o, const float* rays_d, const float* 
 // viewdirs + both networks' per-ray input rows + stratified coarse depths + the step's range word, one launch (nerfh_train.hip)
 struct TrainRayPrepArgs {
   const float* rays_d; size_t R;
+  const float* viewdirs;   // [R,3] view directions used as given (dfn_nerfh_train_forward_v); nullptr: rays_d normalised
   const float* hist; size_t hist_rows; const float* emb_a; const float* emb_t; int hist_bin, dim_a, dim_t, n_vocab;
   float* view; float* dir_c; int ld_dc; float* dir_f; int ld_df; float* t_in; int ld_t;
   const float* t_rand; int Nc; float near, far; int lindisp; float* z;

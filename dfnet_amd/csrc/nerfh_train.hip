@@ -987,7 +987,8 @@ __global__ __launch_bounds__(128) void train_ray_prep_kernel(TrainRayPrepArgs a)
   for (size_t ray = blockIdx.x; ray < a.R; ray += gridDim.x) {
     if (threadIdx.x == 0) {
       float vx, vy, vz;
-      normalize3(a.rays_d[ray * 3], a.rays_d[ray * 3 + 1], a.rays_d[ray * 3 + 2], vx, vy, vz);
+      if (a.viewdirs) { vx = a.viewdirs[ray * 3]; vy = a.viewdirs[ray * 3 + 1]; vz = a.viewdirs[ray * 3 + 2]; }   // as given
+      else normalize3(a.rays_d[ray * 3], a.rays_d[ray * 3 + 1], a.rays_d[ray * 3 + 2], vx, vy, vz);
       s_v[0] = vx; s_v[1] = vy; s_v[2] = vz;
       a.view[ray * 3] = vx; a.view[ray * 3 + 1] = vy; a.view[ray * 3 + 2] = vz;
     }

@@ -357,32 +357,32 @@ extern "C" size_t dfn_nerfh_train_workspace_bytes(dfn_nerfh_t h, size_t n_rays, 
   return fz > exact ? fz : exact;   // either mode fits
 }
 
-extern "C" int dfn_nerfh_train_forward(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
-                                       const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
-                                       const float* t_rand, const float* noise, float raw_noise_std, const float* u, float* rgb,
-                                       float* disp, float* acc, float* raw, float* rgb0, float* disp0, float* acc0, float* z_std,
-                                       float* beta, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_forward")) return rc;
-  if (!n_rays) return DFN_OK;
+namespace {
+// dfn_nerfh_train_forward (viewdirs == nullptr: the view directions are rays_d normalised) and dfn_nerfh_train_forward_v (as given)
+int train_forward_impl(const char* fn, dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                       const float* viewdirs, const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
+                       const float* t_rand, const float* noise, float raw_noise_std, const float* u, float* rgb, float* disp, float* acc,
+                       float* raw, float* rgb0, float* disp0, float* acc0, float* z_std, float* beta, void* workspace,
+                       size_t workspace_bytes, void* stream) {
   if (!params || !rays_o || !rays_d || !hist || !rgb || !disp || !acc || !raw || !rgb0 || !disp0 || !acc0 || !z_std || !beta ||
       !workspace || (hist_rows != 1 && hist_rows != n_rays))
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_train_forward: bad argument (hist_rows must be 1 or n_rays)");
+    return set_error(DFN_ERR_ARG, "%s: bad argument (hist_rows must be 1 or n_rays)", fn);
   h->train_forward_exact = !use_fused(h);
   h->train_forward_split = h->train_split_fine;
   if (use_fused(h))
-    return fused::train_forward(h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, rgb,
-                                disp, acc, raw, rgb0, disp0, acc0, z_std, beta, workspace, workspace_bytes, HS(stream));
+    return fused::train_forward(fn, h, params, rays_o, rays_d, viewdirs, hist, hist_rows, n_rays, Nc, Ni, near, far, t_rand, noise,
+                                raw_noise_std, u, rgb, disp, acc, raw, rgb0, disp0, acc0, z_std, beta, workspace, workspace_bytes, HS(stream));
   const Dims m = dims_of(h->desc);
   const TrainWs w = carve_train(static_cast<float*>(workspace), m, n_rays, Nc, Ni, true);
-  if (w.total > workspace_bytes)
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_train_forward: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+  if (w.total > workspace_bytes) return set_error(DFN_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, w.total);
   hipStream_t s = HS(stream);
   const size_t R = n_rays;
   const int Nf = Nc + Ni;
   const Net nc = net_of(params, nullptr, false), nf = net_of(params, nullptr, true);
   const float* emb_a = params[kCoarseParams + kFineParams];
   const float* emb_t = params[kCoarseParams + kFineParams + 1];
-  CHECK_HIP(launch_viewdirs(rays_d, R, w.view, s), "train forward: viewdirs");
+  if (viewdirs) CHECK_HIP(hipMemcpyAsync(w.view, viewdirs, R * 3 * sizeof(float), hipMemcpyDeviceToDevice, s), "train forward: viewdirs");
+  else CHECK_HIP(launch_viewdirs(rays_d, R, w.view, s), "train forward: viewdirs");
   CHECK_HIP(ray_inputs(w.view, nullptr, 1, nullptr, nullptr, m.hist_bin, m.dim_a, m.dim_t, m.n_vocab, R, w.dir_c, m.ld_dc, nullptr, 0, s),
             "train forward: coarse ray inputs");
   CHECK_HIP(ray_inputs(w.view, hist, hist_rows, emb_a, emb_t, m.hist_bin, m.dim_a, m.dim_t, m.n_vocab, R, w.dir_f, m.ld_df, w.t_in,
@@ -398,6 +398,30 @@ extern "C" int dfn_nerfh_train_forward(dfn_nerfh_t h, const float* const* params
   // training compositing: joint rgb, depth = sum w z, beta = sum w_t beta_t + beta_min (flags = 0)
   CHECK_HIP(launch_composite_fine(raw, w.z_f, R, Nf, 0.1f, 0, rgb, disp, acc, nullptr, nullptr, beta, s), "train forward: fine composite");
   return DFN_OK;
+}
+}  // namespace
+
+extern "C" int dfn_nerfh_train_forward(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                                       const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near, float far,
+                                       const float* t_rand, const float* noise, float raw_noise_std, const float* u, float* rgb,
+                                       float* disp, float* acc, float* raw, float* rgb0, float* disp0, float* acc0, float* z_std,
+                                       float* beta, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_forward")) return rc;
+  if (!n_rays) return DFN_OK;
+  return train_forward_impl("dfn_nerfh_train_forward", h, params, rays_o, rays_d, nullptr, hist, hist_rows, n_rays, Nc, Ni, near, far, t_rand,
+                            noise, raw_noise_std, u, rgb, disp, acc, raw, rgb0, disp0, acc0, z_std, beta, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dfn_nerfh_train_forward_v(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                                         const float* viewdirs, const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni,
+                                         float near, float far, const float* t_rand, const float* noise, float raw_noise_std,
+                                         const float* u, float* rgb, float* disp, float* acc, float* raw, float* rgb0, float* disp0,
+                                         float* acc0, float* z_std, float* beta, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_forward_v")) return rc;
+  if (!n_rays) return DFN_OK;
+  return train_forward_impl("dfn_nerfh_train_forward_v", h, params, rays_o, rays_d, viewdirs, hist, hist_rows, n_rays, Nc, Ni, near, far,
+                            t_rand, noise, raw_noise_std, u, rgb, disp, acc, raw, rgb0, disp0, acc0, z_std, beta, workspace, workspace_bytes,
+                            stream);
 }
 
 extern "C" int dfn_nerfw_loss(const float* rgb, const float* rgb0, const float* beta, const float* raw, const float* target,
@@ -558,8 +582,8 @@ namespace {
 // dfn_nerfh_train_backward_rays and dfn_nerfh_train_backward_rays_maps: they differ in the compositing-backward stage alone (CompGrads)
 int train_backward_rays_impl(const char* fn, dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
                              const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise, float raw_noise_std,
-                             const float* raw, const CompGrads& cg, float* grad_rays_o, float* grad_rays_d, void* workspace,
-                             size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+                             const float* raw, const CompGrads& cg, float* grad_rays_o, float* grad_rays_d, float* grad_viewdirs,
+                             void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream) {
   if (!params || !rays_o || !rays_d || !hist || !raw || !grad_rays_o || !grad_rays_d || !workspace || !scratch ||
       (hist_rows != 1 && hist_rows != n_rays))
     return set_error(DFN_ERR_ARG, "%s: bad argument", fn);
@@ -584,13 +608,45 @@ int train_backward_rays_impl(const char* fn, dfn_nerfh_t h, const float* const* 
                             hist, hist_rows, nullptr, nullptr, R, s, false, g_pe, g_dpe))
     return rc;
   CHECK_HIP(posenc_backward(rays_o, rays_d, w.view, w.z_f, g_pe, g_dpe, 28, R, Nf, gpts, s), "train backward (rays): fine encodings");
-  CHECK_HIP(launch_ray_grad_reduce(gpts, w.z_f, rays_d, R, Nf, 1, grad_rays_o, grad_rays_d, nullptr, s), "train backward (rays): fine reduction");
+  // grad_viewdirs given (the forward took its view directions as given): d L / d viewdirs goes there and grad_rays_d keeps the point
+  // path alone; the coarse pass accumulates into what the fine pass wrote, as for grad_rays_o / grad_rays_d
+  const int derive = grad_viewdirs ? 0 : 1;
+  CHECK_HIP(launch_ray_grad_reduce(gpts, w.z_f, rays_d, R, Nf, derive, grad_rays_o, grad_rays_d, grad_viewdirs, s), "train backward (rays): fine reduction");
   if (int rc = net_backward(net_of(params, nullptr, false), m, bufs_of(w, m, false, nullptr, R, Nc, Ni), bwd_bufs_of(w, false), false, hist, hist_rows,
                             nullptr, nullptr, R, s, false, g_pe, g_dpe))
     return rc;
   CHECK_HIP(posenc_backward(rays_o, rays_d, w.view, w.z_c, g_pe, g_dpe, 28, R, Nc, gpts, s), "train backward (rays): coarse encodings");
-  CHECK_HIP(launch_ray_grad_reduce(gpts, w.z_c, rays_d, R, Nc, 1, grad_rays_o, grad_rays_d, nullptr, s, 1), "train backward (rays): coarse reduction");
+  CHECK_HIP(launch_ray_grad_reduce(gpts, w.z_c, rays_d, R, Nc, derive, grad_rays_o, grad_rays_d, grad_viewdirs, s, 1), "train backward (rays): coarse reduction");
   return DFN_OK;
+}
+}  // namespace
+
+namespace {
+int train_backward_rays_entry(const char* fn, dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                              const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise, float raw_noise_std,
+                              const float* raw, const float* g_rgb, const float* g_rgb0, const float* g_beta, float g_tsigma,
+                              const float* g_tsigma_dense, float* grad_rays_o, float* grad_rays_d, float* grad_viewdirs, void* workspace,
+                              size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  if (int rc = check_train_args(h, Nc, Ni, fn)) return rc;
+  if (!n_rays) return DFN_OK;
+  if (!g_rgb || !g_rgb0 || !g_beta) return set_error(DFN_ERR_ARG, "%s: bad argument", fn);
+  return train_backward_rays_impl(fn, h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni, noise, raw_noise_std, raw,
+                                  CompGrads{g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense, nullptr, nullptr}, grad_rays_o, grad_rays_d,
+                                  grad_viewdirs, workspace, workspace_bytes, scratch, scratch_bytes, stream);
+}
+int train_backward_rays_maps_entry(const char* fn, dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                                   const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise,
+                                   float raw_noise_std, const float* raw, const dfn_train_map_grads* grads, float g_tsigma,
+                                   const float* grad_raw_ext, float* grad_rays_o, float* grad_rays_d, float* grad_viewdirs, void* workspace,
+                                   size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  if (int rc = check_train_args(h, Nc, Ni, fn)) return rc;
+  if (!n_rays) return DFN_OK;
+  const TrainMapGrads g = map_grads_of(grads);
+  if (!g.any_fine() && !g.any_coarse() && !grad_raw_ext && g_tsigma == 0.f)
+    return set_error(DFN_ERR_ARG, "%s: bad argument (no upstream gradient, no grad_raw_ext and no g_tsigma)", fn);
+  return train_backward_rays_impl(fn, h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni, noise, raw_noise_std, raw,
+                                  CompGrads{nullptr, nullptr, nullptr, g_tsigma, nullptr, &g, grad_raw_ext}, grad_rays_o, grad_rays_d,
+                                  grad_viewdirs, workspace, workspace_bytes, scratch, scratch_bytes, stream);
 }
 }  // namespace
 
@@ -600,12 +656,20 @@ extern "C" int dfn_nerfh_train_backward_rays(dfn_nerfh_t h, const float* const* 
                                              const float* g_beta, float g_tsigma, const float* g_tsigma_dense, float* grad_rays_o,
                                              float* grad_rays_d, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
                                              void* stream) {
-  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_backward_rays")) return rc;
-  if (!n_rays) return DFN_OK;
-  if (!g_rgb || !g_rgb0 || !g_beta) return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward_rays: bad argument");
-  return train_backward_rays_impl("dfn_nerfh_train_backward_rays", h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni, noise,
-                                  raw_noise_std, raw, CompGrads{g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense, nullptr, nullptr},
-                                  grad_rays_o, grad_rays_d, workspace, workspace_bytes, scratch, scratch_bytes, stream);
+  return train_backward_rays_entry("dfn_nerfh_train_backward_rays", h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni, noise,
+                                   raw_noise_std, raw, g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense, grad_rays_o, grad_rays_d, nullptr,
+                                   workspace, workspace_bytes, scratch, scratch_bytes, stream);
+}
+
+extern "C" int dfn_nerfh_train_backward_rays_v(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                                               const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise,
+                                               float raw_noise_std, const float* raw, const float* g_rgb, const float* g_rgb0,
+                                               const float* g_beta, float g_tsigma, const float* g_tsigma_dense, float* grad_rays_o,
+                                               float* grad_rays_d, float* grad_viewdirs, void* workspace, size_t workspace_bytes,
+                                               void* scratch, size_t scratch_bytes, void* stream) {
+  return train_backward_rays_entry("dfn_nerfh_train_backward_rays_v", h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni, noise,
+                                   raw_noise_std, raw, g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense, grad_rays_o, grad_rays_d,
+                                   grad_viewdirs, workspace, workspace_bytes, scratch, scratch_bytes, stream);
 }
 
 extern "C" int dfn_nerfh_train_backward_rays_maps(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
@@ -613,14 +677,20 @@ extern "C" int dfn_nerfh_train_backward_rays_maps(dfn_nerfh_t h, const float* co
                                                   float raw_noise_std, const float* raw, const dfn_train_map_grads* grads, float g_tsigma,
                                                   const float* grad_raw_ext, float* grad_rays_o, float* grad_rays_d, void* workspace,
                                                   size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream) {
-  if (int rc = check_train_args(h, Nc, Ni, "dfn_nerfh_train_backward_rays_maps")) return rc;
-  if (!n_rays) return DFN_OK;
-  const TrainMapGrads g = map_grads_of(grads);
-  if (!g.any_fine() && !g.any_coarse() && !grad_raw_ext && g_tsigma == 0.f)
-    return set_error(DFN_ERR_ARG, "dfn_nerfh_train_backward_rays_maps: bad argument (no upstream gradient, no grad_raw_ext and no g_tsigma)");
-  return train_backward_rays_impl("dfn_nerfh_train_backward_rays_maps", h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni, noise,
-                                  raw_noise_std, raw, CompGrads{nullptr, nullptr, nullptr, g_tsigma, nullptr, &g, grad_raw_ext},
-                                  grad_rays_o, grad_rays_d, workspace, workspace_bytes, scratch, scratch_bytes, stream);
+  return train_backward_rays_maps_entry("dfn_nerfh_train_backward_rays_maps", h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni,
+                                        noise, raw_noise_std, raw, grads, g_tsigma, grad_raw_ext, grad_rays_o, grad_rays_d, nullptr,
+                                        workspace, workspace_bytes, scratch, scratch_bytes, stream);
+}
+
+extern "C" int dfn_nerfh_train_backward_rays_maps_v(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                                                    const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise,
+                                                    float raw_noise_std, const float* raw, const dfn_train_map_grads* grads,
+                                                    float g_tsigma, const float* grad_raw_ext, float* grad_rays_o, float* grad_rays_d,
+                                                    float* grad_viewdirs, void* workspace, size_t workspace_bytes, void* scratch,
+                                                    size_t scratch_bytes, void* stream) {
+  return train_backward_rays_maps_entry("dfn_nerfh_train_backward_rays_maps_v", h, params, rays_o, rays_d, hist, hist_rows, n_rays, Nc, Ni,
+                                        noise, raw_noise_std, raw, grads, g_tsigma, grad_raw_ext, grad_rays_o, grad_rays_d, grad_viewdirs,
+                                        workspace, workspace_bytes, scratch, scratch_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------ generic-width test-time render

@@ -1072,6 +1072,37 @@ def ndc_rays(H, W, focal, near, rays_o, rays_d):
     return oo, od
 
 
+def ndc_rays_backward(H, W, focal, near, rays_o, rays_d, grad_ndc_o=None, grad_ndc_d=None):
+    """ndc_rays under autograd (models/ray_utils.py:27-44): (d L/d rays_o, d L/d rays_d) [n,3] from the gradients of the NDC rays, either
+    of which may be None = zeros (dfn_ndc_rays_backward)."""
+    if grad_ndc_o is None and grad_ndc_d is None:
+        raise ValueError("ndc_rays_backward: grad_ndc_o and grad_ndc_d are both None")
+    o, d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
+    g_o, g_d = (None if g is None else _f32c(g).reshape(-1, 3) for g in (grad_ndc_o, grad_ndc_d))
+    n = o.shape[0]
+    if d.shape[0] != n or any(g is not None and g.shape[0] != n for g in (g_o, g_d)):
+        raise ValueError(f"ndc_rays_backward: rays and gradients must have {n} rows")
+    go, gd = torch.empty_like(o), torch.empty_like(d)
+    check(_lib.load().dfn_ndc_rays_backward(int(H), int(W), float(focal), float(near), ptr(o), ptr(d), n, ptr(g_o), ptr(g_d), ptr(go),
+                                            ptr(gd), current_stream()), "dfn_ndc_rays_backward")
+    return go, gd
+
+
+def viewdirs_backward(rays_d, grad_viewdirs, out=None):
+    """viewdirs = d / |d| under autograd (rendering.py:364-371): d L/d rays_d [n,3] = (g - v (v.g)) / |d| (dfn_viewdirs_backward).
+    out [n,3]: a contiguous fp32 buffer the result is ADDED to (and which is returned)."""
+    d, g = _f32c(rays_d).reshape(-1, 3), _f32c(grad_viewdirs).reshape(-1, 3)
+    if g.shape[0] != d.shape[0] or (out is not None and out.shape != d.shape):
+        raise ValueError(f"viewdirs_backward: gradients must have {d.shape[0]} rows of 3")
+    if out is not None and (out.device != d.device or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError(f"viewdirs_backward: out must be a contiguous fp32 tensor on {d.device}, got {out.dtype} {out.device} "
+                         f"contiguous={out.is_contiguous()}")
+    gd = torch.empty_like(d) if out is None else out
+    check(_lib.load().dfn_viewdirs_backward(ptr(d), ptr(g), d.shape[0], 0 if out is None else 1, ptr(gd), current_stream()),
+          "dfn_viewdirs_backward")
+    return gd
+
+
 def sample_fine(sigma, Ni, near, far, want_aux=False, lindisp=False):
     lib = _lib.load()
     sigma = _f32c(sigma)

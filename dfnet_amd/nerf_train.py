@@ -118,15 +118,22 @@ class NerfHTrainer:
         exact fp32, activations kept: what backward_rays() needs)."""
         check(self.lib.dfn_nerfh_set_train_mode(self.engine.handle, 1 if exact else (2 if self.fused_split else 0)), "dfn_nerfh_set_train_mode")
 
-    def forward(self, rays_o, rays_d, hist, Nc, Ni, near, far, t_rand=None, noise=None, raw_noise_std=0., u=None, exact=None, maps=False):
+    def forward(self, rays_o, rays_d, hist, Nc, Ni, near, far, t_rand=None, noise=None, raw_noise_std=0., u=None, exact=None, maps=False,
+                viewdirs=None):
         """Training-mode render_rays -> dict(rgb_map, disp_map, acc_map, raw, rgb0, disp0, acc0, z_std, beta,
         transient_sigmas); keeps what backward() needs.  exact: force the layer-by-layer exact-fp32 step (None: `self.exact`).
-        maps: also depth and depth0 [n], the sums w z of rendering.py:241 in the fine and the coarse pass (dfn_nerfh_train_depths)."""
+        maps: also depth and depth0 [n], the sums w z of rendering.py:241 in the fine and the coarse pass (dfn_nerfh_train_depths).
+        viewdirs [n,3]: the view directions of both networks, used as given (rendering.py:364-376 with ndc / c2w_staticcam;
+        dfn_nerfh_train_forward_v); None: rays_d normalised.  backward_rays() then returns their gradient as a third tensor."""
         exact = self.exact if exact is None else bool(exact)
         self.set_mode(exact)
         exact = exact or self.engine.width != 128    # what RAN: only netwidth 128 has the fused chains, any other width is the exact step
         rays_o, rays_d = _f32c(rays_o).reshape(-1, 3), _f32c(rays_d).reshape(-1, 3)
         n, dev = rays_o.shape[0], rays_o.device
+        if viewdirs is not None:
+            viewdirs = _f32c(viewdirs).reshape(-1, 3)
+            if viewdirs.shape[0] != n:
+                raise ValueError(f"viewdirs must have {n} rows, got {tuple(viewdirs.shape)}")
         hist = _f32c(hist).reshape(-1, self.hist_bin)
         if hist.shape[0] not in (1, n):
             raise ValueError(f"img_idx must have 1 or {n} rows of {self.hist_bin} bins")
@@ -137,19 +144,20 @@ class NerfHTrainer:
         out = {k: torch.empty(n, *sh, device=dev) for k, sh in (("rgb_map", (3,)), ("disp_map", ()), ("acc_map", ()), ("raw", (Nf, 9)),
                                                                  ("rgb0", (3,)), ("disp0", ()), ("acc0", ()), ("z_std", ()), ("beta", ()))}
         ws = self._workspace(n, Nc, Ni, dev)
-        check(self.lib.dfn_nerfh_train_forward(self.engine.handle, self._ptr_array(self.params), ptr(rays_o), ptr(rays_d), ptr(hist),
-                                               hist.shape[0], n, Nc, Ni, float(near), float(far), ptr(t_rand), ptr(noise),
-                                               float(raw_noise_std), ptr(u), ptr(out["rgb_map"]), ptr(out["disp_map"]), ptr(out["acc_map"]),
-                                               ptr(out["raw"]), ptr(out["rgb0"]), ptr(out["disp0"]), ptr(out["acc0"]), ptr(out["z_std"]),
-                                               ptr(out["beta"]), ctypes.c_void_p(ws.data_ptr()), ws.numel(), current_stream()),
-              "dfn_nerfh_train_forward")
+        name = "dfn_nerfh_train_forward" if viewdirs is None else "dfn_nerfh_train_forward_v"
+        rays = (ptr(rays_o), ptr(rays_d)) + (() if viewdirs is None else (ptr(viewdirs),))
+        check(getattr(self.lib, name)(self.engine.handle, self._ptr_array(self.params), *rays, ptr(hist),
+                                      hist.shape[0], n, Nc, Ni, float(near), float(far), ptr(t_rand), ptr(noise),
+                                      float(raw_noise_std), ptr(u), ptr(out["rgb_map"]), ptr(out["disp_map"]), ptr(out["acc_map"]),
+                                      ptr(out["raw"]), ptr(out["rgb0"]), ptr(out["disp0"]), ptr(out["acc0"]), ptr(out["z_std"]),
+                                      ptr(out["beta"]), ctypes.c_void_p(ws.data_ptr()), ws.numel(), current_stream()), name)
         out["transient_sigmas"] = out["raw"][..., 7]
         if maps:
             out["depth"], out["depth0"] = torch.empty(n, device=dev), torch.empty(n, device=dev)
             check(self.lib.dfn_nerfh_train_depths(self.engine.handle, n, Nc, Ni, ptr(out["raw"]), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
                                                   ptr(out["depth"]), ptr(out["depth0"]), current_stream()), "dfn_nerfh_train_depths")
         self._saved = dict(hist=hist, n=n, Nc=Nc, Ni=Ni, noise=noise, raw_noise_std=float(raw_noise_std), raw=out["raw"], ws=ws, exact=exact,
-                           rays_o=rays_o, rays_d=rays_d)
+                           rays_o=rays_o, rays_d=rays_d, viewdirs_given=viewdirs is not None)
         return out
 
     def loss(self, out, target, coef=1., lambda_u=0.01):
@@ -213,7 +221,8 @@ class NerfHTrainer:
     def backward_rays(self, g_rgb=None, g_rgb0=None, g_beta=None, g_tsigma=0., g_tsigma_dense=None, saved=None, g_maps=None, g_raw=None):
         """(d L / d rays_o, d L / d rays_d) [n,3] of the last forward(exact=True): the reference's training render is differentiable
         w.r.t. its rays under autograd (rendering.py:245-337); both networks contribute.  g_maps / g_raw as in backward()
-        (dfn_nerfh_train_backward_rays_maps)."""
+        (dfn_nerfh_train_backward_rays_maps).  After a forward(viewdirs=...) the result is (d L / d rays_o, d L / d rays_d,
+        d L / d viewdirs): the view directions were an input of their own, and rays_d receives the point path alone (the *_v entries)."""
         s = self._saved if saved is None else saved
         if s is None or not s["exact"]:
             raise RuntimeError("NerfHTrainer.backward_rays() needs a forward(exact=True): the fused chain keeps no activations")
@@ -223,10 +232,14 @@ class NerfHTrainer:
         scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
         maps, comp, held = self._comp_operands(s, g_rgb, g_rgb0, g_beta, g_tsigma, g_tsigma_dense, g_maps, g_raw)
         name = "dfn_nerfh_train_backward_rays_maps" if maps else "dfn_nerfh_train_backward_rays"
+        gv = torch.empty(s["n"], 3, device=dev) if s.get("viewdirs_given") else None
+        out = (ptr(go), ptr(gdir))
+        if gv is not None:
+            name, out = name + "_v", out + (ptr(gv),)
         step, ws = self._step_args(s)
         check(getattr(self.lib, name)(self.engine.handle, self._ptr_array(self.params), ptr(s["rays_o"]), ptr(s["rays_d"]), *step, *comp,
-                                      ptr(go), ptr(gdir), *ws, ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), current_stream()), name)
-        return go, gdir
+                                      *out, *ws, ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), current_stream()), name)
+        return (go, gdir) if gv is None else (go, gdir, gv)
 
     # ------------------------------------------------------------------ a training query on points (one network)
     def net_slots(self, net):
@@ -409,16 +422,19 @@ class _RenderTrainFn(torch.autograd.Function):
     uses, losses.py:43-52); the other outputs are marked non-differentiable.
     diff_maps (render(test_time=False, diff_maps=True)): EVERY output is attached, and depth, depth0 follow the ten: all but z_std (a
     function of the detached z_samples, rendering.py:302,327) are differentiable, as the reference's are (rendering.py:161-243, :295-331).
-    An output the loss does not use arrives as None = a NULL upstream pointer.  The forward values are the same bits either way."""
+    An output the loss does not use arrives as None = a NULL upstream pointer.  The forward values are the same bits either way.
+    viewdirs (render(ndc / c2w_staticcam, diff_view=True), rendering.py:364-376): None, or the view directions [n,3] as a tensor input
+    of its own - used as given by both networks, and d L / d viewdirs comes back as that input's gradient while rays_d receives the
+    point path alone."""
 
     NAMES = ("rgb", "disp", "acc", None, "rgb0", "disp0", "acc0", None, "beta", None, "depth", "depth0")   # outputs -> dfn_train_map_grads
 
     @staticmethod
-    def forward(ctx, diff_maps, trainer, rays_o, rays_d, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, *params):
+    def forward(ctx, diff_maps, trainer, rays_o, rays_d, viewdirs, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, *params):
         # gradients w.r.t. the rays (pose optimisation through the training render) come from the exact step, which keeps activations
-        ctx.want_rays = bool(ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+        ctx.want_rays = bool(any(ctx.needs_input_grad[2:5]))
         out = trainer.forward(rays_o, rays_d, hist, Nc, Ni, near, far, t_rand, noise, raw_noise_std, u, exact=True if ctx.want_rays else None,
-                              maps=diff_maps)
+                              maps=diff_maps, viewdirs=None if viewdirs is None else viewdirs.detach())
         ctx.diff_maps = diff_maps
         ctx.trainer = trainer
         ctx.saved = trainer._saved
@@ -451,16 +467,18 @@ class _RenderTrainFn(torch.autograd.Function):
             z3, z1 = torch.zeros(n, 3, device=dev), torch.zeros(n, device=dev)
             ops = dict(g_rgb=z3 if gs[0] is None else gs[0], g_rgb0=z3 if gs[4] is None else gs[4], g_beta=z1 if gs[8] is None else gs[8],
                        g_tsigma_dense=g_ts)
-        g_o = g_d = None
+        g_o = g_d = g_v = None
         if ctx.want_rays:   # before the weight gradients: they reuse the gradient buffers of the workspace
-            g_o, g_d = tr.backward_rays(saved=s, **ops)
-        if any(ctx.needs_input_grad[13:]):
+            g_o, g_d, *rest = tr.backward_rays(saved=s, **ops)
+            g_v = rest[0] if rest else None
+        if any(ctx.needs_input_grad[14:]):
             grads = [torch.empty_like(p) for p in tr.params]
             tr.backward(grads=grads, saved=s, **ops)
             _after_node_backward(tr, s, dev)
         else:
             grads = [None] * len(tr.params)
-        return (None, None, g_o if ctx.needs_input_grad[2] else None, g_d if ctx.needs_input_grad[3] else None) + (None,) * 9 + tuple(grads)
+        return (None, None, g_o if ctx.needs_input_grad[2] else None, g_d if ctx.needs_input_grad[3] else None,
+                g_v if ctx.needs_input_grad[4] else None) + (None,) * 9 + tuple(grads)
 
 
 class _PointsTrainFn(torch.autograd.Function):
@@ -517,13 +535,15 @@ def _after_node_backward(tr, saved, dev):
                                 "trainer.recommit() (weights outgrew the committed scale) or set trainer.exact = True")
 
 
-def render_train(trainer, rays_o, rays_d, hist, Nc, Ni, near, far, perturb, raw_noise_std, retraw, draws=None, diff_maps=False, maps=()):
+def render_train(trainer, rays_o, rays_d, hist, Nc, Ni, near, far, perturb, raw_noise_std, retraw, draws=None, diff_maps=False, maps=(),
+                 viewdirs=None):
     """The training branch of rendering.render(): [rgb, disp, acc, extras] with the reference's extras keys.  diff_maps: every output
-    attached (_RenderTrainFn's diff_maps mode), and the depths named by `maps` (out of depth, depth0) among the extras."""
+    attached (_RenderTrainFn's diff_maps mode), and the depths named by `maps` (out of depth, depth0) among the extras.  viewdirs [n,3]:
+    explicit view directions (the node's viewdirs input); None: rays_d normalised."""
     n = rays_o.reshape(-1, 3).shape[0]
     t_rand, noise, u = draws if draws is not None else NerfHTrainer.draw(n, Nc, Ni, float(perturb), rays_o.device)
     (rgb, disp, acc, raw, rgb0, disp0, acc0, z_std, beta, ts, *depths) = _RenderTrainFn.apply(
-        bool(diff_maps), trainer, rays_o, rays_d, hist, int(Nc), int(Ni), float(near), float(far), t_rand, noise, float(raw_noise_std), u, *trainer.params)
+        bool(diff_maps), trainer, rays_o, rays_d, viewdirs, hist, int(Nc), int(Ni), float(near), float(far), t_rand, noise, float(raw_noise_std), u, *trainer.params)
     extras = {'rgb0': rgb0, 'disp0': disp0, 'acc0': acc0, 'z_std': z_std, 'transient_sigmas': ts, 'beta': beta}
     if retraw:
         extras['raw'] = raw

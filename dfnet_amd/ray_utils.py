@@ -1,4 +1,4 @@
-"""Mirror of /root/reference/script/models/ray_utils.py:5-15 on the HIP raygen kernel."""
+"""Mirror of /root/reference/script/models/ray_utils.py:5-15 and :27-46 on the HIP raygen and NDC kernels."""
 import torch
 
 from . import engine as _engine
@@ -13,10 +13,16 @@ def get_rays(H, W, focal, c2w):
     return o, d
 
 
-def ndc_rays(H, W, focal, near, rays_o, rays_d):
-    """Forward-facing rays in normalised device coordinates (ray_utils.py:27-46); same shapes as the inputs."""
+def ndc_rays(H, W, focal, near, rays_o, rays_d, diff=False):
+    """Forward-facing rays in normalised device coordinates (ray_utils.py:27-46); same shapes as the inputs.
+    diff=False (the default): the result is detached whatever the inputs require.  diff=True: under grad mode with rays_o or rays_d
+    requiring grad the NDC rays are attached to them, as the reference's torch expression is (backward: dfn_ndc_rays_backward); the
+    values are the same bits either way."""
     dev = torch.device("cuda", torch.cuda.current_device())
     o = torch.as_tensor(rays_o, dtype=torch.float32, device=dev)
     d = torch.as_tensor(rays_d, dtype=torch.float32, device=dev)
+    if diff and torch.is_grad_enabled() and (o.requires_grad or d.requires_grad):
+        from .rendering import _NdcRaysFn
+        return _NdcRaysFn.apply(o, d, int(H), int(W), float(focal), float(near))
     no, nd = _engine.ndc_rays(H, W, focal, near, o.reshape(-1, 3), d.reshape(-1, 3))
     return no.reshape(o.shape), nd.reshape(d.shape)

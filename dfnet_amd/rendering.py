@@ -10,7 +10,9 @@ frame-sharded loop with one gather when torch.distributed is initialised (dfnet_
 Test-time kwargs (`render_kwargs_test`: perturb=0, raw_noise_std=0, test_time=True) run on the packed MFMA engine;
 training kwargs (`render_kwargs_train`: test_time=False, perturb, raw_noise_std) run on the exact-fp32 training kernels and
 return tensors attached to autograd with the reference's extras (dfnet_amd/nerf_train.py).  `lindisp` works everywhere; `ndc`
-and `c2w_staticcam` at test time without autograd (their only use in the reference: LLFF-style visualisation), at every netwidth.  `white_bkgd=True`
+and `c2w_staticcam` at test time without autograd (their only use in the reference: LLFF-style visualisation), at every netwidth, and with
+render(..., diff_view=True) under autograd and in training mode too (the view directions become a tensor of their own: `_ViewdirsFn`,
+`_NdcRaysFn` and the explicit-viewdirs form of the render nodes).  `white_bkgd=True`
 raises: it is not a working option of this path in the reference either (rendering.py:295 passes it to the coarse compositor as
 `output_transient`, which fails with a TypeError at test time and mis-slices the 4-channel coarse output in training).
 
@@ -71,19 +73,24 @@ def _two_pass():
     return GRAD_TWO_PASS and GRAD_PRECISION == "f16x3"
 
 
-def _tracked_forward(ctx, eng, o, d, v, hist, Nc, Ni, near, far, retraw=False, names=()):
+def _tracked_forward(ctx, eng, o, d, v, hist, Nc, Ni, near, far, retraw=False, names=(), view_given=False):
     """The forward of every tracked render -> (rgb, disp, acc, {name: map} for `names`, raw if retraw else None).  Leaves on ctx
     what _tracked_backward starts from: the engine, the route taken and the render options as plain Python state, the tensors
-    through save_for_backward."""
-    ctx.eng, ctx.opts = eng, (Nc, Ni, near, far, eng.lindisp)
+    through save_for_backward.  view_given: v is an input of its own (not d/|d|): every route renders with it as given, and the
+    backward returns d L/d v beside a d L/d rays_d that holds the point path alone."""
+    ctx.eng, ctx.opts, ctx.view_given = eng, (Nc, Ni, near, far, eng.lindisp), view_given
     if eng.width != 128:
         # the register-resident gradient kernels (and their saved state) are netwidth 128: other widths render as usual and the
         # backward is the stateless generic-width gradient, which recomputes the forward layer by layer in exact fp32.  At
         # netwidth 256 (fast render kernels) GRAD_FORWARD_PRECISION, when set, names the arithmetic of this tracked forward.
         ctx.route = "generic"
         prec = GRAD_FORWARD_PRECISION if eng.fast else None
-        rgb, disp, acc, raw, maps = eng.render_rays_maps(o, d, hist, Nc, Ni, near, far, retraw=retraw, precision=prec, maps=names)
-        ctx.save_for_backward(o, d, hist)
+        if view_given:
+            rgb, disp, acc, raw, maps = eng.render_rays_maps(o, d, hist, Nc, Ni, near, far, viewdirs=v, retraw=retraw, precision=prec, maps=names)
+            ctx.save_for_backward(o, d, hist, v)
+        else:
+            rgb, disp, acc, raw, maps = eng.render_rays_maps(o, d, hist, Nc, Ni, near, far, retraw=retraw, precision=prec, maps=names)
+            ctx.save_for_backward(o, d, hist)
         return rgb, disp, acc, maps, raw   # no raw is kept (the gradient recomputes it): the rendered tensor is the caller's own
     ctx.route = "two_pass" if _two_pass() else "one_pass"
     rgb, disp, acc, z, raw, *masks = eng.render_rays_saving(o, d, v, hist, Nc, Ni, near, far, precision=GRAD_FORWARD_PRECISION,
@@ -95,7 +102,8 @@ def _tracked_forward(ctx, eng, o, d, v, hist, Nc, Ni, near, far, retraw=False, n
 
 
 def _tracked_backward(ctx, g_rgb, g_raw=None, g_maps=None):
-    """(d L/d rays_o, d L/d rays_d, None) from the state _tracked_forward left on ctx.  g_raw: d L/d of the raw that retraw returned.
+    """(d L/d rays_o, d L/d rays_d, None) from the state _tracked_forward left on ctx - or, after a forward with view_given,
+    (d L/d rays_o, d L/d rays_d through the points alone, d L/d viewdirs).  g_raw: d L/d of the raw that retraw returned.
     g_maps None: d L/d rgb alone (never None: autograd materialises an unused output's gradient as zeros), through the rgb-only
     compositing backward (composite_fine_backward; g_raw is added afterwards).
     g_maps = {name: d L/d output or None} (diff_maps): with g_rgb, the upstream gradients of every compositor output, through
@@ -109,15 +117,17 @@ def _tracked_backward(ctx, g_rgb, g_raw=None, g_maps=None):
         if not g_maps and g_raw is None:
             g_maps = dict(rgb=torch.zeros(saved[0].shape[0], 3, device=saved[0].device))
     if ctx.route == "generic":
-        o, d, hist = saved
+        o, d, hist = saved[:3]
         eng.set_render_options(lindisp=lindisp)
-        return eng.render_rays_backward(o, d, hist, Nc, Ni, near, far, g_rgb, precision="generic", grad_raw=g_raw, grad_maps=g_maps)
+        return eng.render_rays_backward(o, d, hist, Nc, Ni, near, far, g_rgb, viewdirs=saved[3] if ctx.view_given else None,
+                                        precision="generic", grad_raw=g_raw, grad_maps=g_maps)
     o, d, v, hist, z, raw = saved[:6]
     masks = saved[6] if ctx.route == "two_pass" else None
+    derive = not ctx.view_given
     if g_maps is None:
-        return eng.backward_from_saved(o, d, v, hist, z, raw, g_rgb, True, precision=GRAD_PRECISION, masks=masks, grad_raw=g_raw)
+        return eng.backward_from_saved(o, d, v, hist, z, raw, g_rgb, derive, precision=GRAD_PRECISION, masks=masks, grad_raw=g_raw)
     graw = eng.composite_fine_backward_maps(raw, z, g_maps, grad_raw=g_raw)
-    return eng.backward_from_saved(o, d, v, hist, z, raw, None, True, precision=GRAD_PRECISION, masks=masks, graw=graw)
+    return eng.backward_from_saved(o, d, v, hist, z, raw, None, derive, precision=GRAD_PRECISION, masks=masks, graw=graw)
 
 
 class _RenderImageFn(torch.autograd.Function):
@@ -159,6 +169,48 @@ class _RaygenFn(torch.autograd.Function):
         H, W, focal = ctx.cfg
         z = lambda g: torch.zeros(H * W, 3, device=(go if go is not None else gd).device) if g is None else g.contiguous()
         return _e.raygen_backward(H, W, focal, z(go), z(gd)), None, None, None
+
+
+class _NdcRaysFn(torch.autograd.Function):
+    """ndc_rays as an autograd node (ray_utils.py:27-44): (rays_o, rays_d) in normalised device coordinates, shaped like the inputs;
+    backward: d L/d (rays_o, rays_d) from the gradients of the NDC rays (dfn_ndc_rays_backward).  The forward is engine.ndc_rays: the
+    same bits as the untracked call."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, H, W, focal, near):
+        from . import engine as _e
+        o, d = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float()
+        no, nd = _e.ndc_rays(H, W, focal, near, o.reshape(-1, 3), d.reshape(-1, 3))
+        ctx.save_for_backward(o, d)
+        ctx.cfg = (H, W, focal, near)
+        ctx.set_materialize_grads(False)
+        return no.reshape(o.shape), nd.reshape(d.shape)
+
+    @staticmethod
+    def backward(ctx, g_no, g_nd):
+        from . import engine as _e
+        o, d = ctx.saved_tensors
+        if g_no is None and g_nd is None:
+            return (None,) * 6
+        go, gd = _e.ndc_rays_backward(*ctx.cfg, o, d, g_no, g_nd)
+        return go.reshape(o.shape), gd.reshape(d.shape), None, None, None, None
+
+
+class _ViewdirsFn(torch.autograd.Function):
+    """viewdirs = rays_d / |rays_d| (rendering.py:364-371) as an autograd node: the torch expression of the untracked path (the same
+    bits) forward, dfn_viewdirs_backward backward."""
+
+    @staticmethod
+    def forward(ctx, rays_d):
+        d = rays_d.detach().contiguous().float()
+        ctx.save_for_backward(d)
+        return d / torch.norm(d, dim=-1, keepdim=True)
+
+    @staticmethod
+    def backward(ctx, g_v):
+        from . import engine as _e
+        d, = ctx.saved_tensors
+        return _e.viewdirs_backward(d, g_v).reshape(d.shape)
 
 
 class _RenderFramesFn(torch.autograd.Function):
@@ -209,14 +261,17 @@ class _RenderRaysFn(torch.autograd.Function):
     names None: rgb (and raw) alone are differentiable, disp and acc come back detached and there are no maps.
     names a tuple (render(diff_maps=True)): EVERY output is attached - disp_map, acc_map and the maps named by ret_maps are differentiable
     functions of raw in the reference (raw2outputs_NeRFW, rendering.py:161-243) - and their upstream gradients go through the compositing
-    backward for every output (_tracked_backward)."""
+    backward for every output (_tracked_backward).
+    viewdirs (render(ndc / c2w_staticcam, diff_view=True), rendering.py:364-376): None, or the view directions [n,3] as a tensor input of
+    its own - rendered with as given, d L/d viewdirs returned as that input's gradient, and rays_d then receives the point path alone."""
 
     @staticmethod
-    def forward(ctx, rays_o, rays_d, eng, hist, Nc, Ni, near, far, retraw=False, names=None):
+    def forward(ctx, rays_o, rays_d, eng, hist, Nc, Ni, near, far, retraw=False, names=None, viewdirs=None):
         o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
-        v = d / torch.norm(d, dim=-1, keepdim=True)
+        v = d / torch.norm(d, dim=-1, keepdim=True) if viewdirs is None else viewdirs.detach().contiguous()
         ctx.names, ctx.retraw = names, retraw
-        rgb, disp, acc, maps, raw = _tracked_forward(ctx, eng, o, d, v, hist, Nc, Ni, near, far, retraw, names or ())
+        rgb, disp, acc, maps, raw = _tracked_forward(ctx, eng, o, d, v, hist, Nc, Ni, near, far, retraw, names or (),
+                                                     view_given=viewdirs is not None)
         if names is None:
             ctx.mark_non_differentiable(disp, acc)
         else:
@@ -227,8 +282,8 @@ class _RenderRaysFn(torch.autograd.Function):
     def backward(ctx, g_rgb, g_disp, g_acc, *rest):
         g_raw = rest[-1] if ctx.retraw else None
         g_maps = None if ctx.names is None else dict(zip(("disp", "acc") + ctx.names, (g_disp, g_acc) + rest))
-        go, gd, _ = _tracked_backward(ctx, g_rgb, g_raw, g_maps)
-        return (go, gd) + (None,) * 8
+        go, gd, gv = _tracked_backward(ctx, g_rgb, g_raw, g_maps)
+        return (go, gd) + (None,) * 8 + (gv if ctx.view_given else None,)
 
 
 def _set_options(eng, kw, near):
@@ -239,13 +294,14 @@ def _set_options(eng, kw, near):
     eng.set_render_options(lindisp=lindisp)
 
 
-def _check_test_time(kw, ndc, c2w_staticcam, use_viewdirs, training=False, tracked=False, ret_maps=False, diff_maps=False):
+def _check_test_time(kw, ndc, c2w_staticcam, use_viewdirs, training=False, tracked=False, ret_maps=False, diff_maps=False, diff_view=False):
     bad = []
     if kw.get('white_bkgd', False):
         raise TypeError("render(): white_bkgd=True is not a working option of the NeRF-H path: the reference hands it to the coarse "
                         "compositor as output_transient (models/rendering.py:295) and fails the same way")
-    if (ndc or c2w_staticcam is not None) and (training or tracked):
-        bad.append("ndc / c2w_staticcam together with " + ("training-mode rendering" if training else "autograd"))
+    if (ndc or c2w_staticcam is not None) and (training or tracked) and not diff_view:
+        bad.append("ndc / c2w_staticcam together with " + ("training-mode rendering" if training else "autograd") +
+                   " without diff_view=True (render(..., diff_view=True) opts in; render_frames has no such form)")
     if ret_maps and (training or tracked) and not diff_maps:
         bad.append("ret_maps together with " + ("training-mode rendering without diff_maps" if training else
                                                 "autograd (the maps are not differentiable)"))
@@ -270,9 +326,48 @@ def _shaped(lead, rgb, disp, acc, extras):
     return [rgb.reshape(lead + [3]), disp.reshape(lead), acc.reshape(lead), {k: v.reshape(lead + list(v.shape[1:])) for k, v in extras.items()}]
 
 
+def _diff_view_rays(H, W, focal, rays, c2w, c2w_staticcam, ndc, dev):
+    """rendering.py:364-376 as the reference runs it under autograd -> (rays_o [n,3], rays_d [n,3], viewdirs [n,3], leading shape): the
+    view directions come from the given rays / pose (`_ViewdirsFn`), the rays that are marched are then the static camera's and / or
+    the NDC ones (`_NdcRaysFn` at near = 1); a pose that requires grad reaches its rays through `_RaygenFn`.  Whatever does not require
+    grad (or everything, under no_grad) takes the untracked calls: the values are the same bits either way."""
+    grad = torch.is_grad_enabled()
+
+    def rays_of(pose):
+        pose = torch.as_tensor(pose, dtype=torch.float32, device=dev)
+        if grad and pose.requires_grad:
+            return tuple(t.reshape(int(H), int(W), 3) for t in _RaygenFn.apply(pose[:3, :4].contiguous(), int(H), int(W), float(focal)))
+        return get_rays(H, W, focal, pose)
+
+    if c2w is not None:
+        rays_o, rays_d = rays_of(c2w)
+    else:
+        rays_o, rays_d = (torch.as_tensor(t, dtype=torch.float32, device=dev) for t in rays)
+    lead = list(rays_d.shape[:-1])
+    view = rays_d.reshape(-1, 3)
+    view = _ViewdirsFn.apply(view) if grad and view.requires_grad else view / torch.norm(view, dim=-1, keepdim=True)
+    if c2w_staticcam is not None:
+        rays_o, rays_d = rays_of(c2w_staticcam)
+    if ndc:
+        if grad and (rays_o.requires_grad or rays_d.requires_grad):
+            rays_o, rays_d = _NdcRaysFn.apply(rays_o, rays_d, int(H), int(W), float(focal), 1.)
+        else:
+            rays_o, rays_d = ndc_rays(H, W, focal, 1., rays_o, rays_d)
+    rays_o, rays_d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
+    if rays_d.shape[0] != view.shape[0]:
+        raise ValueError(f"render(): c2w_staticcam gives {rays_d.shape[0]} rays of an H x W image, the view directions have {view.shape[0]} rows")
+    return rays_o, rays_d, view, lead
+
+
 def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
-           c2w_staticcam=None, img_idx=torch.Tensor(0), ret_maps=False, diff_maps=False, **kwargs):
+           c2w_staticcam=None, img_idx=torch.Tensor(0), ret_maps=False, diff_maps=False, diff_view=False, **kwargs):
     """Drop-in for rendering.py:353-400.  Returns [rgb_map, disp_map, acc_map, extras].
+
+    diff_view (opt-in): ndc=True and c2w_staticcam (rendering.py:364-376) under autograd at test time - rays, c2w or c2w_staticcam
+    requiring grad - and in training mode, as in the reference, where both are plain tensor ops: the view directions of the given rays /
+    pose become a tensor input of the render node, the marched rays are the static camera's and / or the NDC ones, and every gradient
+    reaches what it came from (c2w through the view directions alone once c2w_staticcam replaces its rays).  Composes with retraw and
+    diff_maps.  False: both options are refused there, as ever.  Without ndc / c2w_staticcam the keyword changes nothing.
 
     ret_maps (beyond the reference, test time; under autograd only together with diff_maps): True, or an iterable of names out of depth, depth_static, beta,
     rgb_static, rgb_transient — the maps raw2outputs_NeRFW forms and the reference drops (rendering.py:196-241) are added to
@@ -301,12 +396,16 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     if training:
         # training mode (rendering.py:245-337 with test_time=False): stratified depths, coarse rgb + noise, importance sampling
         # with random u, the training extras — on the exact-fp32 training kernels, attached to autograd (nerf_train.py)
-        _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, training=True, ret_maps=bool(map_list), diff_maps=bool(diff_maps))
+        _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, training=True, ret_maps=bool(map_list), diff_maps=bool(diff_maps),
+                         diff_view=bool(diff_view))
         # The reference's training render is differentiable w.r.t. its rays / pose too: rays that require grad make the autograd node
         # run the exact-fp32 step and return d L / d rays (nerf_train._RenderTrainFn); c2w reaches them through get_rays' own node.
         from . import nerf_train
         dev = torch.device("cuda", torch.cuda.current_device())
-        if c2w is not None:
+        view = None
+        if ndc or c2w_staticcam is not None:   # (diff_view: refused above without it)
+            rays_o, rays_d, view, lead = _diff_view_rays(H, W, focal, rays, c2w, c2w_staticcam, ndc, dev)
+        elif c2w is not None:
             c2w = torch.as_tensor(c2w, dtype=torch.float32, device=dev)
             if torch.is_grad_enabled() and c2w.requires_grad:
                 rays_o, rays_d = _RaygenFn.apply(c2w[:3, :4].contiguous(), int(H), int(W), float(focal))
@@ -317,12 +416,13 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
             rays_o, rays_d = rays
         rays_o = torch.as_tensor(rays_o, dtype=torch.float32, device=dev)
         rays_d = torch.as_tensor(rays_d, dtype=torch.float32, device=dev)
-        lead = list(rays_d.shape[:-1])
+        if view is None:
+            lead = list(rays_d.shape[:-1])
         hist = torch.as_tensor(img_idx, dtype=torch.float32, device=dev).reshape(-1, eng.hist_bin)
         rgb, disp, acc, extras = nerf_train.render_train(trainer, rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), hist, int(kwargs['N_samples']),
                                                          int(kwargs['N_importance']), near, far, float(kwargs.get('perturb', 0.) or 0.),
                                                          float(kwargs.get('raw_noise_std', 0.) or 0.), bool(kwargs.get('retraw', False)),
-                                                         draws=kwargs.get('draws'), diff_maps=bool(diff_maps), maps=map_list)
+                                                         draws=kwargs.get('draws'), diff_maps=bool(diff_maps), maps=map_list, viewdirs=view)
         # (no `stale` mark here: a render does not move the weights; HipQuery.refresh() sees optimizer steps through the tensors'
         #  version counters, and the training loop marks them itself)
         return _shaped(lead, rgb, disp, acc, extras)
@@ -332,9 +432,11 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         if torch.is_tensor(t):
             return t.requires_grad
         return isinstance(t, (tuple, list)) and any(_needs_grad(u) for u in t)
-    track = torch.is_grad_enabled() and (_needs_grad(c2w) or _needs_grad(rays))
+    view_opts = bool(ndc) or c2w_staticcam is not None
+    track = torch.is_grad_enabled() and (_needs_grad(c2w) or _needs_grad(rays) or (bool(diff_view) and view_opts and _needs_grad(c2w_staticcam)))
     diff_maps = bool(diff_maps) and track   # nothing to attach to without autograd
-    _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, tracked=track, ret_maps=bool(map_list), diff_maps=diff_maps)
+    _check_test_time(kwargs, ndc, c2w_staticcam, use_viewdirs, tracked=track, ret_maps=bool(map_list), diff_maps=diff_maps,
+                     diff_view=bool(diff_view))
     Nc, Ni = int(kwargs['N_samples']), int(kwargs['N_importance'])
     retraw = bool(kwargs.get('retraw', False))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -347,21 +449,25 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
             extras['raw'] = raw
         return _shaped(lead, rgb, disp, acc, extras)
 
-    if ndc or c2w_staticcam is not None:
-        # rendering.py:364-376: the view directions come from the given rays / pose; the rays themselves are then replaced by the
-        # static camera's and / or mapped to normalised device coordinates (ndc_rays at near = 1)
-        if c2w is not None:
-            rays_o, rays_d = get_rays(H, W, focal, torch.as_tensor(c2w, dtype=torch.float32, device=dev))
-        else:
-            rays_o, rays_d = (torch.as_tensor(t, dtype=torch.float32, device=dev) for t in rays)
-        view = rays_d.reshape(-1, 3)
-        view = view / torch.norm(view, dim=-1, keepdim=True)
-        if c2w_staticcam is not None:
-            rays_o, rays_d = get_rays(H, W, focal, torch.as_tensor(c2w_staticcam, dtype=torch.float32, device=dev))
-        if ndc:
-            rays_o, rays_d = ndc_rays(H, W, focal, 1., rays_o, rays_d)
+    def _tracked_rays(o, d, h, lead, view=None):
+        """The tracked ray render.  diff_maps: every output attached, the maps of ret_maps among them; otherwise rgb (and raw) alone,
+        and ret_maps was refused above.  view: explicit view directions, a differentiable input of their own."""
+        out = _RenderRaysFn.apply(o, d, eng, h, Nc, Ni, float(near), float(far), retraw, tuple(map_list) if diff_maps else None, view)
+        extras = dict(zip(map_list, out[3:]))
+        if retraw:
+            extras['raw'] = out[-1]
+        return _shaped(lead, *out[:3], extras)
+
+    if view_opts and track:   # (diff_view: refused above without it) rendering.py:364-376 under autograd
+        o, d, view, lead = _diff_view_rays(H, W, focal, rays, c2w, c2w_staticcam, ndc, dev)
         hist = hist.reshape(-1, eng.hist_bin)
-        return _rays(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), hist, list(rays_d.shape[:-1]), view)
+        if hist.shape[0] not in (1, o.shape[0]):
+            raise ValueError(f"img_idx must have 1 or {o.shape[0]} rows of {eng.hist_bin} bins, got {tuple(hist.shape)}")
+        return _tracked_rays(o, d, hist, lead, view)
+    if view_opts:   # untracked: the same composition, every step the plain call
+        with torch.no_grad():
+            o, d, view, lead = _diff_view_rays(H, W, focal, rays, c2w, c2w_staticcam, ndc, dev)
+        return _rays(o, d, hist.reshape(-1, eng.hist_bin), lead, view)
     if c2w is not None:
         c2w = torch.as_tensor(c2w, dtype=torch.float32, device=dev)
         if retraw or diff_maps or hist.numel() != eng.hist_bin:   # what the image entries do not do: through the image's rays
@@ -390,12 +496,7 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     o, d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
     if not track:
         return _rays(o, d, hist, lead)
-    # diff_maps: every output attached, the maps of ret_maps among them; otherwise rgb (and raw) alone, and ret_maps was refused above
-    out = _RenderRaysFn.apply(o, d, eng, hist, Nc, Ni, float(near), float(far), retraw, tuple(map_list) if diff_maps else None)
-    extras = dict(zip(map_list, out[3:]))
-    if retraw:
-        extras['raw'] = out[-1]
-    return _shaped(lead, *out[:3], extras)
+    return _tracked_rays(o, d, hist, lead)
 
 
 # ------------------------------------------------------------------------------------------ the compositor and the sampler as public stages

@@ -137,6 +137,17 @@ int dfn_raygen_frames(int B, int H, int W, float focal, const float* c2w, float*
  * H x W pinhole camera -> normalised device coordinates, out_o / out_d [n,3] (may alias the inputs). */
 int dfn_ndc_rays(int H, int W, float focal, float near, const float* rays_o, const float* rays_d, size_t n, float* out_o,
                  float* out_d, void* stream);
+/* models/ray_utils.py:27-44 under autograd (render(ndc=True) with rays or a pose that require grad, rendering.py:374-376): the
+ * vector-Jacobian product of dfn_ndc_rays.  grad_ndc_o / grad_ndc_d [n,3] = d L / d (out_o, out_d), either may be NULL (= zeros), both
+ * NULL is DFN_ERR_ARG -> grad_rays_o / grad_rays_d [n,3] = d L / d (rays_o, rays_d), overwritten.  The outputs must NOT alias the
+ * inputs.  The third components of out_o / out_d are constants (the shifted origin lies on the near plane) and carry no gradient.
+ * No guard for rays_d z == 0: the reference gives inf there too.  n == 0 is DFN_OK. */
+int dfn_ndc_rays_backward(int H, int W, float focal, float near, const float* rays_o, const float* rays_d, size_t n,
+                          const float* grad_ndc_o, const float* grad_ndc_d, float* grad_rays_o, float* grad_rays_d, void* stream);
+/* viewdirs = rays_d / |rays_d| under autograd (rendering.py:364-371): grad_rays_d [n,3] = (g - v (v . g)) / |rays_d| with g =
+ * grad_viewdirs [n,3]; accumulate != 0 adds to what grad_rays_d holds.  The fold dfn_ray_grad_reduce(derive_viewdirs = 1) does
+ * internally, as a stage of its own (view directions that are a tensor of their own: render(ndc=True) / c2w_staticcam). */
+int dfn_viewdirs_backward(const float* rays_d, const float* grad_viewdirs, size_t n, int accumulate, float* grad_rays_d, void* stream);
 
 /* models/nerfw.py:105-133 Embedder.embed.  x [n,3] -> out [n, 3+6L].  mode 0 = full-range
  * sinf/cosf, 1 = the fast v_sin/v_cos path the f16 MLP kernels use. */
@@ -739,6 +750,14 @@ int dfn_nerfh_train_forward(dfn_nerfh_t h, const float* const* params, const flo
                             const float* t_rand, const float* noise, float raw_noise_std, const float* u, float* rgb,
                             float* disp, float* acc, float* raw, float* rgb0, float* disp0, float* acc0, float* z_std,
                             float* beta, void* workspace, size_t workspace_bytes, void* stream);
+/* The same with explicit view directions (rendering.py:364-376: with ndc or c2w_staticcam the view directions come from the caller's
+ * rays while the rays that are marched are the static camera's and / or the NDC ones): viewdirs [n_rays,3] enter both dir_encodings as
+ * given; NULL = rays_d normalised, bit for bit dfn_nerfh_train_forward.  Every train mode. */
+int dfn_nerfh_train_forward_v(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                              const float* viewdirs, const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, float near,
+                              float far, const float* t_rand, const float* noise, float raw_noise_std, const float* u, float* rgb,
+                              float* disp, float* acc, float* raw, float* rgb0, float* disp0, float* acc0, float* z_std, float* beta,
+                              void* workspace, size_t workspace_bytes, void* stream);
 
 /* models/losses.py:19-57 NerfWLoss(coef, lambda_u) on (rgb_fine, rgb_coarse, beta, transient_sigmas = raw[..., 7])
  * vs target [n,3].  loss5: DEVICE buffer of DFN_NERFW_LOSS_FLOATS floats, 16-byte aligned; [0..4] = c_l, f_l, b_l, s_l and the PSNR
@@ -772,6 +791,13 @@ int dfn_nerfh_train_backward_rays(dfn_nerfh_t h, const float* const* params, con
                                   const float* raw, const float* g_rgb, const float* g_rgb0, const float* g_beta, float g_tsigma,
                                   const float* g_tsigma_dense, float* grad_rays_o, float* grad_rays_d, void* workspace,
                                   size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream);
+/* ... after a dfn_nerfh_train_forward_v with explicit view directions (rendering.py:364-376 under autograd): grad_viewdirs [n,3]
+ * receives d L / d viewdirs of both networks (overwritten) and grad_rays_d the point path alone; NULL = dfn_nerfh_train_backward_rays. */
+int dfn_nerfh_train_backward_rays_v(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d, const float* hist,
+                                    size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise, float raw_noise_std,
+                                    const float* raw, const float* g_rgb, const float* g_rgb0, const float* g_beta, float g_tsigma,
+                                    const float* g_tsigma_dense, float* grad_rays_o, float* grad_rays_d, float* grad_viewdirs,
+                                    void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- the training render with EVERY output attached (render(test_time=False, diff_maps=True))
  * In the reference render(**render_kwargs_train) returns rgb_map, disp_map, acc_map, raw, rgb0, disp0, acc0, beta and transient_sigmas as
@@ -830,6 +856,12 @@ int dfn_nerfh_train_backward_rays_maps(dfn_nerfh_t h, const float* const* params
                                        float raw_noise_std, const float* raw, const dfn_train_map_grads* grads, float g_tsigma,
                                        const float* grad_raw_ext, float* grad_rays_o, float* grad_rays_d, void* workspace,
                                        size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream);
+/* ... with grad_viewdirs [n,3] as in dfn_nerfh_train_backward_rays_v (rendering.py:364-376 under autograd); NULL = the entry above. */
+int dfn_nerfh_train_backward_rays_maps_v(dfn_nerfh_t h, const float* const* params, const float* rays_o, const float* rays_d,
+                                         const float* hist, size_t hist_rows, size_t n_rays, int Nc, int Ni, const float* noise,
+                                         float raw_noise_std, const float* raw, const dfn_train_map_grads* grads, float g_tsigma,
+                                         const float* grad_raw_ext, float* grad_rays_o, float* grad_rays_d, float* grad_viewdirs,
+                                         void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- a TRAINING query on points: one network under autograd with respect to its parameters
  * run_network_NeRFW with test_time=False on given points (models/nerfw.py:47-95, 297-354): in the reference
