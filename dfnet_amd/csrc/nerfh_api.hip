@@ -170,7 +170,7 @@ static int check_grad_prec(int prec, const char* fn) {
 // every kernel launch that carries the guard runs on a committed handle.
 static int* range_flag_of(dfn_nerfh_t h) { return h->range_flag; }
 
-// Kernel variant: DFN_MLP_VARIANT=0..11 (A/B aid; nerfh_layout.h: kVariantFacts, kSelectedByDefault), read once.  What it means for a call
+// Kernel variant: DFN_MLP_VARIANT=0..12 (A/B aid; nerfh_layout.h: kVariantFacts, kSelectedByDefault), read once.  What it means for a call
 // is nerfh_route.h; the gradient paths (render backward, dfn_mlp_fine_saving) run the base variant's / variant 0's plain kernels on
 // the plain table, which their backward kernels read.
 static int mlp_variant_128() {
@@ -206,6 +206,7 @@ static hipError_t launch_route(dfn_nerfh_t h, bool fine, int prec, const Route& 
     case kLaunchKept: return launch_mlp_pe(fine, d, cus, s);
     case kLaunchHoisted: return launch_mlp_hoist(fine, d, cus, s);
     case kLaunchSelected: return launch_mlp_sel(fine, d, cus, s);
+    case kLaunchLean: return launch_mlp_lean(fine, d, cus, s);
     case kLaunchPoints: return launch_mlp_pts(fine, prec, a, cus, s, width);
     case kLaunchPointsFold: return launch_mlp_pts_fold(a, cus, s);
     case kLaunchPointsHalf: return launch_mlp_pts_half(a, cus, s);

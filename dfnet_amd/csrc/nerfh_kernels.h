@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "nerfh_raydiv.h"
+
 namespace dfn {
 
 struct MlpArgs {
@@ -68,6 +70,13 @@ hipError_t launch_mlp_hoist(bool fine, const MlpDynArgs& a, int n_cu, hipStream_
 // Kernel variant 11 (nerfh_mlp_sel.hip): variant 10's fine kernel (fine = true: the scaled table, as launch_mlp_hoist) and variant 9's
 // coarse kernel (fine = false) with one select per head value.  Variant 9's arguments.
 hipError_t launch_mlp_sel(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
+// Kernel variant 12 (nerfh_mlp_lean.hip): variant 11's two kernels with a leaner tile seam and range guard.  The caller passes variant
+// 11's arguments; the launcher adds the magic number by which the kernels turn a point index into a ray index (nerfh_raydiv.h), in a
+// struct of the kernels' own for the reason given at MlpResArgs.
+struct MlpLeanArgs : MlpDynArgs {
+  RayDiv div;   // ray_div_of(n_samples)
+};
+hipError_t launch_mlp_lean(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
 
 // The points flavour (nerfh_mlp_pts*.hip): a.rays_o is pts [n_rays, n_samples, 3] (n_rays = query rows), a.rays_d, a.z and a.partial
 // are unused (a.partial must be null: the raw route only), a.ray_bias has one row per query row.  launch_mlp_pts: f16 / exact fp32 at

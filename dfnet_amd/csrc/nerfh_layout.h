@@ -192,6 +192,12 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //              whose masks were the scalar pressure variant 10 fought: 4 023 -> 3 754 vector instructions per fine tile, 39 -> 0
 //              parked SGPRs).  The same value on the same lane: variant 10's outputs bit for bit, on its networks, resident blob,
 //              scaled table and counters.  The unit has a coarse kernel too (variant 9's code with the select: 2 728 -> 2 707)
+//   variant 12: variant 11 with a LEAN tile seam and range guard (nerfh_mlp_lean.hip): in the fine kernel the eight head activations are
+//              evaluated as four (the static pre-activations ride on lanes 32..63, which carry no sample there); in both kernels the
+//              point -> ray division is a multiply-high and a shift (nerfh_raydiv.h) and the range guard of the ReLU conversions is
+//              one v_pk_maximum3_f16 per two pieces instead of one v_pk_max_u16 per piece (336 -> 168 / 256 -> 128 per tile):
+//              3 754 -> 3 414 / 2 707 -> 2 556 vector instructions.  The same values on the same lanes and the same flag: variant 11's
+//              outputs bit for bit, on its networks, resident blob, scaled table and counters
 constexpr int kVariants = 8;   // packed networks per (coarse | fine, arithmetic): dfn_nerfh_s::net
 constexpr int kFoldVariant = 5;
 constexpr int kHalfVariant = 6;
@@ -200,10 +206,12 @@ constexpr int kDynVariant = 8;
 constexpr int kKeptVariant = 9;
 constexpr int kHoistVariant = 10;
 constexpr int kSelVariant = 11;
-constexpr int kLastVariant = kSelVariant;   // DFN_MLP_VARIANT = 0 .. kLastVariant
+constexpr int kLeanVariant = 12;
+constexpr int kLastVariant = kLeanVariant;   // DFN_MLP_VARIANT = 0 .. kLastVariant
 // kept: the encoding, for the skip concat; hoisted: the fused fine kernel is nerfh_mlp_hoist.hip's and its per-ray table holds in_scale x the seeds;
-// sel: the coarse and the fused fine kernel are nerfh_mlp_sel.hip's (the fine one reads the scaled table as variant 10's)
-struct VariantFacts { int base; bool fold, half, resident, claimed, kept, hoisted, sel; };
+// sel: the coarse and the fused fine kernel are nerfh_mlp_sel.hip's (the fine one reads the scaled table as variant 10's);
+// lean: they are nerfh_mlp_lean.hip's (the same table)
+struct VariantFacts { int base; bool fold, half, resident, claimed, kept, hoisted, sel, lean; };
 constexpr VariantFacts kVariantFacts[kLastVariant + 1] = {
     {0, false, false, false, false}, {1, false, false, false, false}, {2, false, false, false, false}, {3, false, false, false, false},
     {4, false, false, false, false},
@@ -214,9 +222,10 @@ constexpr VariantFacts kVariantFacts[kLastVariant + 1] = {
     {4, true, true, true, true, true},   // kKeptVariant
     {4, true, true, true, true, true, true},   // kHoistVariant: variant 9's row (its plain kernels are variant 4's too) and the new fact
     {4, true, true, true, true, true, true, true},   // kSelVariant: variant 10's row and the new fact
+    {4, true, true, true, true, true, true, true, true},   // kLeanVariant: variant 11's row and the new fact
 };
 // What a process runs without DFN_MLP_VARIANT; the variant whose kernels the point queries run whatever it says
-constexpr int kSelectedByDefault = kSelVariant;
+constexpr int kSelectedByDefault = kLeanVariant;
 constexpr int kDefaultVariant = kResidentVariant;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));

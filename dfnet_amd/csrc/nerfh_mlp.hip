@@ -23,6 +23,7 @@
 
 #include "nerfh_mlp_core.h"
 #include "nerfh_mask.h"
+#include "nerfh_raydiv.h"
 
 namespace dfn {
 
@@ -42,9 +43,11 @@ namespace dfn {
 //                     MlpDynArgs; the unit has no coarse kernel (variant 9's runs)
 //   DFN_MLP_SEL_TU    variant 11, on HOIST: one select per head value (layer(): the candidates behind an opaque copy), coarse and fine,
 //                     MlpDynArgs; the coarse kernel is variant 9's code under the unit's flags
+//   DFN_MLP_LEAN_TU   variant 12, on SEL: the tile seam and the range guard with less vector work (nerfh_mlp_lean.hip: its three parts and
+//                     their switches), coarse and fine, MlpLeanArgs = MlpDynArgs + the point -> ray magic number
 //   DFN_MLP_STATIC_TU the coarse network's training query (nerfw.py:47-60, 326-343), on PTS, plain or FOLD: the fine kernel cut off
 //                     behind static_rgb (kCoarseStaticSeq / kCoarseStaticFoldSeq), 4 floats per point; the unit has that kernel alone
-// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn|_pe|_hoist|_sel][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn|_pe|_hoist|_sel];
+// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn|_pe|_hoist|_sel|_lean][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn|_pe|_hoist|_sel|_lean];
 // DFN_MLP_STATIC_TU: nerfh_coarse_static[_fold]_pts_kernel, launch_mlp_static_pts[_fold].
 #if defined(DFN_MLP_STATIC_TU) && (!defined(DFN_MLP_PTS_TU) || defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_MAPS_TU))
 #error "the static query exists in the points flavour, plain or folded"
@@ -64,7 +67,13 @@ namespace dfn {
 #if defined(DFN_MLP_SEL_TU) && !defined(DFN_MLP_HOIST_TU)
 #error "the selected head values exist in the unit with the hoisted per-tile work"
 #endif
-#if defined(DFN_MLP_SEL_TU)
+#if defined(DFN_MLP_LEAN_TU) && !defined(DFN_MLP_SEL_TU)
+#error "the lean seam and range guard exist in the unit with the selected head values"
+#endif
+#if defined(DFN_MLP_LEAN_TU)
+#define DFN_TU_TAG _lean
+#define DFN_MLP_KARGS MlpLeanArgs
+#elif defined(DFN_MLP_SEL_TU)
 #define DFN_TU_TAG _sel
 #define DFN_MLP_KARGS MlpDynArgs
 #elif defined(DFN_MLP_HOIST_TU)
@@ -157,6 +166,21 @@ DFN_DEV const_kargs* args_here() {
 #else
 DFN_DEV int wave_here(const Stager& st) { return st.wave; }
 #define DFN_ARGS_HERE(a) (a)
+#endif
+
+// Kernel variant 12, the packed head activations of the fused fine kernel (nerfh_mlp_lean.hip: DFN_LEAN_ACT4); off in every other unit.
+#if defined(DFN_MLP_LEAN_TU) && DFN_LEAN_ACT4
+constexpr bool kLeanAct4 = true;
+#else
+constexpr bool kLeanAct4 = false;
+#endif
+// The ray of point q (q < 2^31: launch_tiles).  Variant 12 takes it by multiply-high and shift with the launch's magic number
+// (nerfh_raydiv.h; MlpLeanArgs::div, two SGPRs) where the other units divide: about 16 vector instructions per lane and point, one of
+// them a quarter-rate reciprocal, at the tile seam.
+#if defined(DFN_MLP_LEAN_TU) && DFN_LEAN_MAGIC
+#define DFN_RAY_OF(a, q) ray_div(q, RayDiv{(a).div.magic, (a).div.shift})
+#else
+#define DFN_RAY_OF(a, q) ((q) / uint32_t((a).n_samples))
 #endif
 
 // Head activations per arithmetic mode: f16 = hardware transcendentals (1e-6), split-f16 = the fp32-grade hardware forms
@@ -264,7 +288,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #pragma unroll
       for (int c = 0; c < 3; ++c) x[n][c] = a.rays_o[size_t(q) * 3 + c];   // pts [n_rows, n_samples, 3]
 #else
-      const uint32_t ray = q / uint32_t(a.n_samples);
+      const uint32_t ray = DFN_RAY_OF(a, q);
       const int i = int(q - ray * uint32_t(a.n_samples));
       const float z = coarse_z_at(i, a.n_samples, a.near, a.far, a.lindisp != 0);
 #pragma unroll
@@ -360,7 +384,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     for (int nb = 0; nb < LP; ++nb) {
       pt[nb] = uint32_t(t) * uint32_t(PPT) + st.wave * (NB * 32) + (P::kM16 ? 16 * nb + (lp & 15) : nb * 32 + (lp & 31));
       const uint32_t q = pt[nb] < npts ? pt[nb] : npts - 1;
-      ray_of[nb] = q / uint32_t(a.n_samples);
+      ray_of[nb] = DFN_RAY_OF(a, q);
     }
   };
   tile_coords(tile);
@@ -464,8 +488,13 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #endif
     sign128(7, hid[0]);   // layer 8's output, completed inside the layer above
     float o[NB][9];
+    // kernel variant 12 (kLeanAct4): the four static pre-activations, kept until the transient head's are there (the transient branch's end)
+    [[maybe_unused]] float pre_s[NB][4];
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) o[nb][3] = head_softplus<P, FAST>(head[nb][0]);
+    for (int nb = 0; nb < NB; ++nb) {
+      if constexpr (kLeanAct4) pre_s[nb][3] = head[nb][0];
+      else o[nb][3] = head_softplus<P, FAST>(head[nb][0]);
+    }
     // dir_encoding (per-ray bias = b + W[:,128:] [pe_dir, a]) -> static_rgb
     {
       F de[NB][QC], dummy[NB][chunks_of<P>(16)];
@@ -501,7 +530,10 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) o[nb][c] = head_sigmoid<P, FAST>(head[nb][c]);
+        for (int c = 0; c < 3; ++c) {
+          if constexpr (kLeanAct4) pre_s[nb][c] = head[nb][c];
+          else o[nb][c] = head_sigmoid<P, FAST>(head[nb][c]);
+        }
     }
 #ifndef DFN_MLP_STATIC_TU   // the static query ends behind static_rgb
     // transient branch
@@ -527,7 +559,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #pragma unroll
           for (int c = 0; c < 3; ++c) lds_dma_b32(pa.rays_o + size_t(q) * 3 + c, slot + (r * 8 + c) * 256);
 #else
-          const uint32_t ray = q / uint32_t(a.n_samples);
+          const uint32_t ray = DFN_RAY_OF(a, q);
           lds_dma_b32(pa.z + q, slot + (r * 8) * 256);
           lds_dma_b32(pa.z + (q + 1 < npts ? q + 1 : q), slot + (r * 8 + 7) * 256);
 #pragma unroll
@@ -546,6 +578,34 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
       sign64(19, t0[0]);
       layer<P, UMB, PIPE, NB, QC, 0, false, true, false, !MERGE && R_THEAD < 0, (CY ? 2 : -1), true, false, false, false, true, NOBETA, R_THEAD>(st, smem, t1, dummy, head, norb, carry);
       sign64(20, t1[0]);
+#ifdef DFN_MLP_LEAN_TU
+      if constexpr (kLeanAct4) {
+        // Eight head activations evaluated as four.  A head value of sample p is valid on lane p of half 0 and lanes 32..63 carry no
+        // sample from here on: everything below reads o[][] under `live` / `h == 0` (the alphas, s_rgb, the raw store).  So the static
+        // pre-activation of sample (lane - 32) is put on lanes 32..63 beside the transient one on lanes 0..31 (v_permlane32_swap_b32 t, s:
+        // lanes 32..63 of t <-> lanes 0..31 of s), one sigmoid covers a colour pair and one softplus the two densities, and a second
+        // swap against the first one's dead second operand brings the static results back to lanes 0..31.  Per-lane functions of the
+        // same arguments: the bits of the separate evaluations.
+        static_assert(NOBETA && P::kM16, "the packed activations are the plain fused 16x16x32 kernel's");
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            // (every element goes through a scalar copy: __builtin_bit_cast applied to an ELEMENT of an ext_vector_type value reads element 0)
+            const float tv = head[nb][c], sv = pre_s[nb][c];
+            const auto in = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, tv), __builtin_bit_cast(uint32_t, sv), false, false);
+            const uint32_t in_t = in[0], in_s = in[1];
+            const float v = __builtin_bit_cast(float, in_t);
+            const float r = c < 3 ? head_sigmoid<P, FAST>(v) : head_softplus<P, FAST>(v);
+            const auto out = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, r), in_s, false, false);
+            const uint32_t out_t = out[0], out_s = out[1];
+            o[nb][4 + c] = __builtin_bit_cast(float, out_t);
+            o[nb][c] = __builtin_bit_cast(float, out_s);
+          }
+          o[nb][8] = 0.f;
+        }
+      } else
+#endif
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
@@ -810,7 +870,16 @@ hipError_t DFN_LAUNCH_MLP(bool fine, int prec, const MlpArgs& a, int n_cu, hipSt
 // (nerfh_mlp_hoist.hip); no coarse kernel.
 // launch_mlp_sel: variant 11's two kernels (nerfh_mlp_sel.hip): launch_mlp_hoist's fine kernel and launch_mlp_pe's coarse kernel with one
 // select per head value, their arguments, LDS map and grid.
+// launch_mlp_lean: variant 12's two kernels (nerfh_mlp_lean.hip): launch_mlp_sel's with the leaner seam and range guard, its arguments
+// (the magic number of a.n_samples is formed here), LDS map and grid.
+#ifdef DFN_MLP_LEAN_TU
+hipError_t DFN_LAUNCH_MLP(bool fine, const MlpDynArgs& dyn, int n_cu, hipStream_t stream) {
+  MlpLeanArgs a{};
+  static_cast<MlpDynArgs&>(a) = dyn;
+  a.div = ray_div_of(uint32_t(dyn.n_samples > 0 ? dyn.n_samples : 1));
+#else
 hipError_t DFN_LAUNCH_MLP(bool fine, const DFN_MLP_KARGS& a, int n_cu, hipStream_t stream) {
+#endif
 #if defined(DFN_MLP_HOIST_TU) && !defined(DFN_MLP_SEL_TU)
   void (*kern)(DFN_MLP_KARGS) = fine ? DFN_FINE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true> : nullptr;
 #else

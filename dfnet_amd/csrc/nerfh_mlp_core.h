@@ -107,7 +107,6 @@ DFN_DEV void lds_dma_b32(const void* gptr, const char* lds_dst) {
   const uint32_t off = (uint32_t)(size_t)DFN_LDS_PTR(lds_dst);
   asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dword %0, off" ::"v"(gptr), "s"(off) : "memory");
 }
-
 #ifdef DFN_MLP_DYN_TU
 // Kernel variant 8: one lane's claim, a returning device-scope atomic add whose result nobody waits for here (mid_sync's vmcnt(0) does).
 // The pointer goes through an opaque vector register: on an address it can prove wave-uniform LLVM's atomic optimiser rewrites the add
@@ -442,6 +441,12 @@ DFN_DEV void store_hidden_piece(const f32x16& acc, typename FragOf<P>::type (&ou
 
 // The split-f16 conversion piece in three parts, so that a K-chunk can place them BETWEEN its three dependent MFMAs (A after the
 // first, B after the second, C after the third) instead of as one block behind them: the parts of store_hidden_piece<PrecX3>.
+#if defined(DFN_MLP_LEAN_TU) && DFN_LEAN_MAX3
+#define DFN_X3_GUARD_MAX3 1
+#define DFN_X3_HOLD , rhold   // layer(): the even piece's hi pair, handed to the odd piece's part C
+#else
+#define DFN_X3_HOLD
+#endif
 struct X3Piece {
   uint32_t hb, hs, lb;
   float t0, t1;
@@ -472,6 +477,35 @@ struct X3Piece {
                  "v_fma_mix_f32 %1, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
                  : "+v"(t0), "+v"(t1) : "v"(s), "v"(hs));
   }
+#ifdef DFN_X3_GUARD_MAX3
+  // Kernel variant 12: the guard of a ReLU conversion at one instruction per TWO pieces.  An even piece leaves its unscaled hi pair in
+  // `hold` (a register kept until the odd piece's part C, no instruction); the odd piece takes rmax = maximum3(rmax, hold, hb) as packed
+  // f16 (v_pk_maximum3_f16).  Why range_report() raises the flag in exactly the launches in which it does after two v_pk_max_u16:
+  //   * Both halves of hb come from v_cvt_pkrtz_f16_f32 of t = v_max_f32(acc, 0).  For a finite or +inf t they are non-negative f16
+  //     patterns 0x0000 .. 0x7c00, on which the float order IS the order of the 16-bit patterns, so the two instructions keep the same
+  //     maximum; rmax itself starts as +0 and is such a pattern until something else enters it.
+  //   * A NaN accumulator: v_max_f32(NaN, 0) in the kernels' IEEE mode is 0 for a quiet NaN (hb = 0 under both guards: neither raises,
+  //     as today) and a quiet NaN for a signalling one.  That NaN converts to an f16 NaN, a pattern above 0x7c00 in the low 15 bits:
+  //     v_pk_max_u16 keeps it as the largest unsigned pattern, v_pk_maximum3_f16 returns NaN whenever an operand is NaN, and a NaN in
+  //     rmax stays one through every later maximum3 and is the largest pattern for every later v_pk_max_u16 (the guards of the layers
+  //     without ReLU, which keep their masked form).  With or without its sign bit the 16-bit pattern is >= 0x7c00 > both thresholds:
+  //     the flag is raised under both.
+  //   * -0 (0x8000): as an unsigned pattern it is above the thresholds, as a float it is below +0, so the two guards would differ on it.
+  //     It cannot occur: v_max_f32(x, 0) returns +0 for x = -0 and for every negative x, and the truncating conversion of a non-negative
+  //     value is non-negative.  (Were it to occur, today's guard would raise on an in-range value.)
+  //   * The f16 denormal mode: were v_pk_maximum3_f16 to flush a denormal operand, it would return +0 or the denormal, both below 2^-14;
+  //     no value moves across 0x7bff / 0x7c00, the only patterns range_report() compares with.
+  template <bool RELU, class P = PrecX3, int OC>
+  DFN_DEV void C(half8x2 (&out)[OC], int mb, int i, uint32_t& rmax, uint32_t& hold) {
+    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+    const int c = x3_chunk<P>(i), j = x3_pos<P>(i);
+    asm volatile("v_cvt_pkrtz_f16_f32 %0, %1, %2" : "=v"(lb) : "v"(t0), "v"(t1));
+    // range guard on the UNSCALED hi pair: that conversion is the one that saturates
+    if (RELU) {
+      if ((i & 1) == 0) hold = hb;
+      else asm volatile("v_pk_maximum3_f16 %0, %0, %1, %2" : "+v"(rmax) : "v"(hold), "v"(hb));
+    } else range_track(rmax, hb, false);
+#else
   template <bool RELU, class P = PrecX3, int OC>
   DFN_DEV void C(half8x2 (&out)[OC], int mb, int i, uint32_t& rmax) {
     typedef _Float16 half2v __attribute__((ext_vector_type(2)));
@@ -480,6 +514,7 @@ struct X3Piece {
     // range guard on the UNSCALED hi pair: that conversion is the one that saturates
     if (RELU) asm volatile("v_pk_max_u16 %0, %0, %1" : "+v"(rmax) : "v"(hb));
     else range_track(rmax, hb, false);
+#endif
     const half2v hv = __builtin_bit_cast(half2v, hs), lv = __builtin_bit_cast(half2v, lb);
     out[2 * mb + c].hi[j] = hv[0]; out[2 * mb + c].hi[j + 1] = hv[1];
     out[2 * mb + c].lo[j] = lv[0]; out[2 * mb + c].lo[j + 1] = lv[1];
@@ -538,6 +573,9 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
   const int h = st.lane >> 5, g16 = st.lane >> 4;   // g16: lane group of the 16x16 fragments (PrecX3M16)
   uint32_t rmax_sink = 0;
   uint32_t& rmax_ = TRACK ? st.rmax : rmax_sink;
+#ifdef DFN_X3_GUARD_MAX3
+  uint32_t rhold = 0;   // every M-block's eight pieces are converted in order inside one call: nothing is held across calls
+#endif
   const float pscale = P::kSplit ? st.out_scale * st.lane_mul * kX3ActScale : 1.f;  // split-f16 pieces: accumulator -> operand scale
   uint32_t pscale2 = 0;   // ... the same factor as a packed f16 pair (X3Piece::B)
   if constexpr (P::kSplit) asm("v_cvt_pkrtz_f16_f32 %0, %1, %1" : "=v"(pscale2) : "v"(pscale));
@@ -676,8 +714,8 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
               __builtin_amdgcn_sched_barrier(0);
               c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.lo, Bin[0][bc].hi, c0, 0, 0, 0);
               __builtin_amdgcn_sched_barrier(0);
-              DFN_X3_PARTS(if (from_carry) pc[q].template C<CIN_RELU, P>(Bin[0], CIN / 2, base + q, rmax_);
-                           else pc[q].template C<RELU, P>(Bout[0], mb - 1, base + q, rmax_))
+              DFN_X3_PARTS(if (from_carry) pc[q].template C<CIN_RELU, P>(Bin[0], CIN / 2, base + q, rmax_ DFN_X3_HOLD);
+                           else pc[q].template C<RELU, P>(Bout[0], mb - 1, base + q, rmax_ DFN_X3_HOLD))
               __builtin_amdgcn_sched_barrier(0);
               c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.lo, Bin[0][bc + 1].hi, c1, 0, 0, 0);
 #undef DFN_X3_PARTS
@@ -695,7 +733,7 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
 #pragma unroll
                   for (int q = 0; q < 4; ++q) tp[q].B2(pscale);
 #pragma unroll
-                  for (int q = 0; q < 4; ++q) tp[q].template C<CIN_RELU, P>(Bin[0], CIN / 2, 4 + q, rmax_);
+                  for (int q = 0; q < 4; ++q) tp[q].template C<CIN_RELU, P>(Bin[0], CIN / 2, 4 + q, rmax_ DFN_X3_HOLD);
                 }
               }
               if (from_carry && kc == CINL - 1) asm volatile("s_nop 3");
@@ -719,8 +757,8 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
 #pragma unroll
             for (int q = 0; q < NPMAX; ++q)
               if (q < np && base + q < 8) {
-                if (from_carry) pc[q].template C<CIN_RELU>(Bin[0], CIN / 2, base + q, rmax_);
-                else pc[q].template C<RELU>(Bout[0], mb - 1, base + q, rmax_);
+                if (from_carry) pc[q].template C<CIN_RELU>(Bin[0], CIN / 2, base + q, rmax_ DFN_X3_HOLD);
+                else pc[q].template C<RELU>(Bout[0], mb - 1, base + q, rmax_ DFN_X3_HOLD);
               }
             acc[0] = c0;
             if (from_carry && kc == CIN - 1) asm volatile("s_nop 3");

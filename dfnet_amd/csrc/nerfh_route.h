@@ -19,6 +19,7 @@ enum Launcher {       // nerfh_kernels.h:
   kLaunchKept,        // launch_mlp_pe: claimed tiles as kLaunchClaimed (claims_tiles below)
   kLaunchHoisted,      // launch_mlp_hoist: kLaunchKept's fine kernel on the per-ray table written at the accumulators' scale (Route::seed_scaled)
   kLaunchSelected,    // launch_mlp_sel: kLaunchKept's coarse and kLaunchHoisted's fine kernel (the scaled table) with one select per head value
+  kLaunchLean,        // launch_mlp_lean: kLaunchSelected's two kernels with the leaner tile seam and range guard (the scaled table)
   kLaunchPoints,      // launch_mlp_pts
   kLaunchPointsFold,  // launch_mlp_pts_fold
   kLaunchPointsHalf,  // launch_mlp_pts_half
@@ -34,15 +35,16 @@ struct Route {
 };
 
 // the launchers whose kernels claim their tiles: both tile counters are zeroed in front of a pass in which either kernel is one of them
-constexpr bool claims_tiles(Launcher l) { return l == kLaunchClaimed || l == kLaunchKept || l == kLaunchHoisted || l == kLaunchSelected; }
+constexpr bool claims_tiles(Launcher l) { return l == kLaunchClaimed || l == kLaunchKept || l == kLaunchHoisted || l == kLaunchSelected || l == kLaunchLean; }
 
-// Netwidth 256 has one kernel per arithmetic: variant 0.  Variants 5 to 11 differ from their base in split-f16 only.
+// Netwidth 256 has one kernel per arithmetic: variant 0.  Variants 5 to 12 differ from their base in split-f16 only.
 constexpr VariantFacts route_facts(int variant, int width) { return kVariantFacts[width == kWidth ? variant : 0]; }
 
 // points: the point queries (dfn_mlp_*_points, called with kDefaultVariant); they have no resident / claimed flavour and run variant 6's
 constexpr Route coarse_route(int variant, int width, int prec, bool points = false) {
   const VariantFacts f = route_facts(variant, width);
   const bool x3 = prec == kPrecF16X3;
+  if (x3 && f.lean && !points) return {kLaunchLean, kResidentVariant, f.base, false, false};
   if (x3 && f.sel && !points) return {kLaunchSelected, kResidentVariant, f.base, false, false};
   if (x3 && f.kept && !points) return {kLaunchKept, kResidentVariant, f.base, false, false};
   if (x3 && f.resident && !points) return {f.claimed ? kLaunchClaimed : kLaunchResident, kResidentVariant, f.base, false, false};
@@ -53,6 +55,7 @@ constexpr Route coarse_route(int variant, int width, int prec, bool points = fal
 constexpr Route fine_route(int variant, int width, int prec, bool fused, bool want_maps, bool points = false) {
   const VariantFacts f = route_facts(variant, width);
   const bool x3 = prec == kPrecF16X3, maps = fused && want_maps;
+  if (x3 && f.lean && fused && !want_maps) return {kLaunchLean, kResidentVariant, f.base, true, false, true};
   if (x3 && f.sel && fused && !want_maps) return {kLaunchSelected, kResidentVariant, f.base, true, false, true};
   if (x3 && f.hoisted && fused && !want_maps) return {kLaunchHoisted, kResidentVariant, f.base, true, false, true};
   if (x3 && f.kept && fused && !want_maps) return {kLaunchKept, kResidentVariant, f.base, true, false};
@@ -85,7 +88,7 @@ constexpr bool plain_as(int v, int w, int p, int b) {
          is(fine_route(v, w, p, true, true), kLaunchMaps, b, b, false, true);
 }
 constexpr bool plain_all(int v, int w, int b) { return plain_as(v, w, H, b) && plain_as(v, w, F, b) && plain_as(v, w, X, b); }
-// the raw route of variants 5 to 10 in split-f16: variant 5's fine kernel on net[1][F16X3][5], with or without maps wanted
+// the raw route of variants 5 to 12 in split-f16: variant 5's fine kernel on net[1][F16X3][5], with or without maps wanted
 constexpr bool raw_is_fold(int v) {
   return is(fine_route(v, W, X, false, false), kLaunchFold, 5, 4, true) && is(fine_route(v, W, X, false, true), kLaunchFold, 5, 4, true);
 }
@@ -139,7 +142,16 @@ static_assert(raw_is_fold(11) && is(fine_route(11, W, X, true, false), kLaunchSe
               is(fine_route(11, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 11 fine");
 static_assert(is(coarse_route(11, W, X, true), kLaunchPointsHalf, 6, 4) && is(fine_route(11, W, X, false, false, true), kLaunchPointsFold, 5, 4, true),
               "variant 11 points");
+// variant 12: variant 11 with launch_mlp_lean where variant 11 has launch_mlp_sel (the scaled table in the fine kernel); the maps flavour,
+// the raw route and the point queries as under variant 9
+static_assert(plain_as(12, W, H, 4) && plain_as(12, W, F, 4) && plain_all(12, W2, 0), "variant 12 outside split-f16");
+static_assert(is(coarse_route(12, W, X), kLaunchLean, 7, 4), "variant 12 coarse");
+static_assert(raw_is_fold(12) && is(fine_route(12, W, X, true, false), kLaunchLean, 7, 4, true, false, true) &&
+              is(fine_route(12, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 12 fine");
+static_assert(is(coarse_route(12, W, X, true), kLaunchPointsHalf, 6, 4) && is(fine_route(12, W, X, false, false, true), kLaunchPointsFold, 5, 4, true),
+              "variant 12 points");
 static_assert(claims_tiles(kLaunchClaimed) && claims_tiles(kLaunchKept) && claims_tiles(kLaunchHoisted) && claims_tiles(kLaunchSelected) &&
+              claims_tiles(kLaunchLean) &&
               !claims_tiles(kLaunchResident),
               "who claims tiles");
 // the coarse pass of a split-f16 render under DFN_RENDER_COARSE_F16 is the f16 route: variant 0's kernel on net[0][F16][4]
@@ -151,7 +163,7 @@ static_assert(is(coarse_route(7, W, H, true), kLaunchPoints, 4, 4) && is(fine_ro
               is(coarse_route(7, W2, X, true), kLaunchPoints, 0, 0) && is(fine_route(7, W2, X, false, false, true), kLaunchPoints, 0, 0),
               "points outside split-f16 at netwidth 128");
 // fused compositing: whole segments, no raw, netwidth 128, and not the 3-block f16 kernel (base variant 2)
-static_assert(fused_compositing(11, W, X, 128, false) && fused_compositing(10, W, X, 128, false) &&fused_compositing(9, W, X, 128, false) && fused_compositing(8, W, X, 128, false) && fused_compositing(0, W, H, 128, false) &&
+static_assert(fused_compositing(12, W, X, 128, false) && fused_compositing(11, W, X, 128, false) && fused_compositing(10, W, X, 128, false) &&fused_compositing(9, W, X, 128, false) && fused_compositing(8, W, X, 128, false) && fused_compositing(0, W, H, 128, false) &&
               fused_compositing(2, W, X, 96, false), "fused");
 static_assert(!fused_compositing(8, W, X, 128, true) && !fused_compositing(8, W, X, 40, false) && !fused_compositing(0, W, H, 96, false) &&
               !fused_compositing(2, W, H, 128, false) && !fused_compositing(0, W2, X, 128, false), "not fused");
