@@ -5,7 +5,7 @@ importing callers get a RuntimeError telling them how to build it.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 LIB_PATH = os.environ.get("DFN_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdfnet_hip.so")
 
@@ -230,6 +230,12 @@ SIGNATURES = {
     "dfn_linear_backward_weight_scratch_bytes": (c_size_t, [c_int, c_int, c_size_t]),
     "dfn_linear_backward_weight": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "dfn_adam_step": (c_int, [_P, c_int, c_double, c_double, c_double, c_double, _P]),
+    # mesh export (isosurface.hip; the reference only declares the flags, models/options.py:69-70): grid points for the density query,
+    # marching tetrahedra as count -> read totals -> emit
+    "dfn_isosurface_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dfn_grid_points": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "dfn_isosurface_count": (c_int, [_P, c_int, c_int, c_int, c_float, _P, c_size_t, _P, _P]),
+    "dfn_isosurface_emit": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, _P, c_size_t, _P, c_longlong, _P, c_longlong, _P]),
     "dfn_profile_enable": (c_int, [c_int]),
     "dfn_profile_read": (c_int, [c_int, POINTER(c_double), POINTER(c_int)]),
 }

@@ -1385,3 +1385,49 @@ def frame_post_maps(maps, near, far, gt=None, want=None):
                                   float(far), ctypes.byref(m_out), raw(res.get("beta_max")), raw(res.get("mse_static")), raw(scratch),
                                   current_stream()), "dfn_frame_post_maps")
     return res
+
+
+# ------------------------------------------------------------------ mesh export (isosurface.hip; dfnet_amd/mesh.py is the user's side)
+def _axes3(axes):
+    xs, ys, zs = (_f32c(a).reshape(-1) for a in axes)
+    if not (xs.is_cuda and ys.device == xs.device and zs.device == xs.device):
+        raise ValueError("grid axes must be three fp32 CUDA vectors on one device")
+    return xs, ys, zs
+
+
+def grid_points(axes, i0=0, i1=None):
+    """The nodes of planes i0 <= i < i1 of the grid spanned by axes = (xs [nx], ys [ny], zs [nz]) as pts [(i1 - i0) * ny, nz, 3]: rows
+    of nz points, the layout the point queries read (dfn_grid_points)."""
+    xs, ys, zs = _axes3(axes)
+    nx, ny, nz = xs.numel(), ys.numel(), zs.numel()
+    i1 = nx if i1 is None else int(i1)
+    pts = torch.empty(max(i1 - int(i0), 0) * ny, nz, 3, device=xs.device)
+    check(_lib.load().dfn_grid_points(ptr(xs), ptr(ys), ptr(zs), nx, ny, nz, int(i0), i1, ptr(pts), current_stream()), "dfn_grid_points")
+    return pts
+
+
+def isosurface(sigma, axes, iso):
+    """Marching tetrahedra on the Kuhn split (dfn_isosurface_count -> read the totals -> dfn_isosurface_emit): sigma [nx,ny,nz] and the
+    three axis vectors -> (verts fp32 [V,3], faces int32 [F,3]) on the device; `iso` is an fp32 value.  The read of the two totals is
+    the one synchronisation; an empty surface is two empty tensors."""
+    lib = _lib.load()
+    sigma = _f32c(sigma)
+    xs, ys, zs = _axes3(axes)
+    if sigma.dim() != 3 or tuple(sigma.shape) != (xs.numel(), ys.numel(), zs.numel()) or sigma.device != xs.device:
+        raise ValueError(f"sigma {tuple(sigma.shape)} on {sigma.device} does not match axes of {xs.numel()}, {ys.numel()}, {zs.numel()} "
+                         f"nodes on {xs.device}")
+    nx, ny, nz = sigma.shape
+    dev = sigma.device
+    nbytes = lib.dfn_isosurface_workspace_bytes(nx, ny, nz)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # 0 bytes for refused dimensions: the count entry names the reason
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+    raw = lambda t: ctypes.c_void_p(t.data_ptr())
+    check(lib.dfn_isosurface_count(ptr(sigma), nx, ny, nz, float(iso), raw(ws), nbytes, raw(totals), current_stream()),
+          "dfn_isosurface_count")
+    V, F = (int(v) for v in totals.tolist())
+    verts = torch.empty(V, 3, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    if V or F:
+        check(lib.dfn_isosurface_emit(ptr(sigma), ptr(xs), ptr(ys), ptr(zs), nx, ny, nz, float(iso), raw(ws), nbytes, ptr(verts), V,
+                                      raw(faces), F, current_stream()), "dfn_isosurface_emit")
+    return verts, faces

@@ -75,8 +75,19 @@ _T = [
     ("render_maps", "str", "", "nfd"),         # render maps of --render_test / render_path beside rgb and disparity: "" (off) | all |
                                                # a comma-separated list out of depth, depth_static, beta, rgb_static, rgb_transient
                                                # (render_map_names below turns the value into render_path's ret_maps)
+    # run_nerf.py --mesh_only (dfnet_amd/mesh.py; the reference declares --mesh_only / --mesh_grid_size and reads neither): help in _HELP
+    ("mesh_bounds", "float+", None, "n"), ("mesh_threshold", "float", 20.0, "n"), ("mesh_colors", "flag", False, "n"),
 ]
 _TYPES = {"int": int, "float": float, "str": str}
+_HELP = {
+    "mesh_only": "do not optimize, reload weights and save mesh to a file (<basedir>/<expname>/mesh_<step>.ply; run_nerf.py)",
+    "mesh_grid_size": "number of grid points to sample in each dimension for the iso-surface extraction",
+    "mesh_bounds": "x0 y0 z0 x1 y1 z1 of the grid; default: the box of the training camera centres grown by `far` on every side",
+    "mesh_threshold": "density of the extracted iso-surface.  The default 20 is the convention of common NeRF mesh extractors: a "
+                      "default setting that any user overrides, not a tuned or measured number (--mesh_only prints the deciles of "
+                      "the density grid to pick one from)",
+    "mesh_colors": "store per-vertex colours: the fine network's static rgb at the vertices, appearance of the first training frame",
+}
 
 
 def _read_config(path):
@@ -133,9 +144,9 @@ def _build(which):
         if name == "fff":
             p.add_argument("-f", "--fff", default=default)
         elif kind == "flag":
-            p.add_argument("--" + name, action="store_true", default=default)
+            p.add_argument("--" + name, action="store_true", default=default, help=_HELP.get(name))
         elif kind.endswith("+"):
-            p.add_argument("--" + name, nargs="+", type=_TYPES[kind[:-1]], default=default)
+            p.add_argument("--" + name, nargs="+", type=_TYPES[kind[:-1]], default=default, help=_HELP.get(name))
         elif name == "coarse_precision":
             p.add_argument("--coarse_precision", type=str, default=default, choices=["f16", "same"],
                            help="under --precision f16x3: run the coarse network (sample placement only; z_samples are detached, its colour is "
@@ -149,7 +160,7 @@ def _build(which):
                                 "within 1e-3 of the reference on random-init weights only — on trained checkpoints worst pixels reach 1e-2 "
                                 "(rgb 2.7e-2, disparity 1.0e-2 measured); guarded against overflow by dfn_nerfh_range_status)")
         else:
-            p.add_argument("--" + name, type=_TYPES[kind], default=default)
+            p.add_argument("--" + name, type=_TYPES[kind], default=default, help=_HELP.get(name))
     return p
 
 

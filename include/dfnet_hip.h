@@ -974,6 +974,56 @@ typedef struct dfn_adam_tensor {
 int dfn_adam_step(const dfn_adam_tensor* tensors, int n_tensors, double beta1, double beta2, double eps, double weight_decay,
                   void* stream);
 
+/* ---- mesh export: the points of a regular grid, and the iso-surface of a density volume (isosurface.hip).
+ *
+ * The reference has no counterpart beyond models/options.py:69-70, which declare --mesh_only ("do not optimize, reload weights and
+ * save mesh to a file") and --mesh_grid_size ("number of grid points to sample in each dimension for marching cubes") and are never
+ * read: this comment is the specification.  Plain entries without a handle: caller-allocated device buffers, enqueue and return, no
+ * allocation and no synchronisation inside.
+ *
+ * Grid: three fp32 device axis arrays xs [nx], ys [ny], zs [nz] (any values: coordinates are looked up, never recomputed from
+ * bounds, so non-uniform axes work); node (i,j,k) has id = (i ny + j) nz + k and sigma [nx,ny,nz] is indexed by it (z fastest).
+ * nx, ny, nz >= 2 (DFN_ERR_ARG otherwise) and nx ny nz <= 178 956 970 (DFN_ERR_UNSUPPORTED otherwise: a cell gives at most 12
+ * triangles, and 12 nodes < 2^31 keeps every 32-bit count, prefix and vertex id exact; 512^3 fits).  A null pointer or a workspace
+ * below the bytes the size function gives is DFN_ERR_ARG (the size function returns 0 for dimensions the entries refuse).
+ *
+ * The points entry: the nodes of planes i0 <= i < i1 as pts [(i1 - i0) ny, nz, 3] (rows of nz points, what the point queries read),
+ * pts = (xs[i], ys[j], zs[k]) copied bit for bit.  0 <= i0 <= i1 <= nx; i0 == i1 is DFN_OK and launches nothing (pts may then be NULL).
+ *
+ * The surface: marching tetrahedra on the Kuhn split (no 256-case table, no ambiguous case; the split is the same in every cell, so
+ * the surface is watertight by construction).
+ *   - A node is INSIDE iff sigma >= iso, compared in fp32; NaN is outside.
+ *   - A cell is split into 6 tetrahedra, one per permutation (a,b,c) of the axes in lexicographic order xyz, xzy, yxz, yzx, zxy,
+ *     zyx = tet 0..5, with vertices v0 = (0,0,0), v1 = v0 + e_a, v2 = v1 + e_b, v3 = (1,1,1).
+ *   - The edges of this triangulation leave a node in the directions d in {0,1}^3 \ 0, type = dx + 2 dy + 4 dz - 1 (0..6), and
+ *     key = id(lower node) 7 + type.  An edge is CROSSED iff its ends differ in inside-ness; it then carries one vertex,
+ *       t = clamp((iso - s_a) / (s_b - s_a), 0, 1),   p = p_a + t (p_b - p_a) per component,
+ *     a = the lower node, every operation fp32 and rounded on its own; a NaN quotient (an end is NaN, or both ends infinite) clamps
+ *     to 0.  Vertex ids are the ranks of the crossed edges in increasing key order.
+ *   - Triangles of a tet with k inside vertices, indices in tet-vertex order: k = 0, 4 none; k = 1, 3 one: with w the odd vertex out
+ *     and u1 < u2 < u3 the others, the vertices on (w,u1), (w,u2), (w,u3); k = 2, inside p < q, outside r < s: the quad A = (p,r),
+ *     B = (p,s), C = (q,s), D = (q,r) as (A,B,C) and (A,C,D).  The winding is a function of (tet, case) alone: a table made on
+ *     the unit cell with every crossing at the edge midpoint, so that the normal points from the inside vertices to the outside
+ *     ones (toward lower density); where it asks for the other orientation the last two vertices are exchanged.  It never depends on
+ *     the data: a degenerate triangle still has a defined winding.
+ *   - Faces are ordered by cell (the id of its lowest node), then tet, then triangle.  Nothing is appended with atomics (count ->
+ *     exclusive scan -> emit), so two runs give the same bits.
+ *   - Nodes exactly at iso are inside and their edges cross at t = 0: they produce zero-area triangles, which are emitted as they
+ *     are (no simplification, no dropping of degenerate triangles).
+ *
+ * The count entry fills the workspace (per node the 7 crossing bits and the two exclusive prefixes, scanned inside the library) and
+ * writes totals [2] (device, 64-bit) = the number of vertices V and of triangles F.  The caller READS totals before the emit entry:
+ * that read is the caller's synchronisation, and the two allocations it sizes (verts fp32 [V,3], faces int32 [F,3]) are all a host
+ * needs between the two calls.  The emit entry takes the same sigma, dimensions, iso and workspace and writes both arrays; it bounds
+ * every store by the V and F it was given and every read by the grid, whatever the workspace holds.  V == 0 and F == 0 is DFN_OK and
+ * launches nothing (verts / faces may then be NULL); V or F negative, or above 7 / 12 per node, is DFN_ERR_ARG. */
+size_t dfn_isosurface_workspace_bytes(int nx, int ny, int nz);
+int dfn_grid_points(const float* xs, const float* ys, const float* zs, int nx, int ny, int nz, int i0, int i1, float* pts, void* stream);
+int dfn_isosurface_count(const float* sigma, int nx, int ny, int nz, float iso, void* workspace, size_t workspace_bytes,
+                         unsigned long long* totals, void* stream);
+int dfn_isosurface_emit(const float* sigma, const float* xs, const float* ys, const float* zs, int nx, int ny, int nz, float iso,
+                        const void* workspace, size_t workspace_bytes, float* verts, long long V, int* faces, long long F, void* stream);
+
 /* Timing aid for bench.py: average device time in ms of the `which` kernel of the render path
  * (DFN_PROF_*) over the launches since the last reset, measured with HIP events recorded on the
  * launch `stream` around each launch.  Enabled by dfn_profile_enable(1); costs a sync when read. */

@@ -8,6 +8,7 @@ reference's format, `evaluate_{train,val}_test_<step>/NNN.png`, `trainset_/tests
 Without --render_test it trains NeRF-H as run_nerf.py:32-80,127-240 does: per training image N_rand random rays ->
 render(**render_kwargs_train) -> NerfWLoss -> backward -> Adam -> exponential lr decay, every network product and every
 gradient on the HIP training kernels (dfnet_amd/nerf_train.py); validation renders use the packed test-time engine.
+With --mesh_only it reloads the weights and writes `mesh_{:06d}.ply` (the density's iso-surface, dfnet_amd/mesh.py) instead.
 Single GPU: run as is.  Multi-GPU (one process per GPU; training images of an epoch dealt round-robin to the ranks with
 one flat gradient all-reduce per step over RCCL, frames of render_path sharded with one gather):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run_nerf.py ...
@@ -88,6 +89,39 @@ def _holdout(dl, device, skip=1):
     return torch.cat(imgs, 0).cpu().numpy(), torch.cat(poses, 0).to(device), torch.cat(idxs, 0).to(device)
 
 
+def export_mesh(args, train_dl, far, start, render_kwargs_test):
+    """--mesh_only: the fine network's density on --mesh_grid_size points per axis over --mesh_bounds (default: the box of the
+    training camera centres grown by `far`), its iso-surface at --mesh_threshold as <basedir>/<expname>/mesh_<start>.ply.  Prints
+    V, F and the deciles of the density grid (what to pick a threshold from).  No training, no render.
+    Poses and the histogram of --mesh_colors come from the training SET, not from its loader (which shuffles outside --render_test):
+    the colours are those of training frame 0 whatever the state of the random generators, and no image but that one is decoded.
+    Rank 0 extracts and writes; the other ranks wait at a barrier behind it, so all leave together (also when rank 0 raises)."""
+    from dfnet_amd import mesh
+    rank, _ = ddist.rank_world()
+    path = None
+    try:
+        if rank == 0:
+            frames = train_dl.dataset
+            bounds = args.mesh_bounds
+            if bounds is None:
+                bounds = mesh.default_bounds(np.asarray(frames.poses).reshape(-1, 12), far)
+            if len(bounds) != 6:
+                raise ValueError(f"--mesh_bounds takes six numbers x0 y0 z0 x1 y1 z1, got {bounds}")
+            hist0 = frames[0][2] if args.mesh_colors else None
+            out = mesh.extract_mesh(render_kwargs_test, bounds, args.mesh_grid_size, threshold=args.mesh_threshold, net='fine',
+                                    colors=args.mesh_colors, img_idx=hist0)
+            path = os.path.join(args.basedir, args.expname, 'mesh_{:06d}.ply'.format(start))
+            mesh.save_ply(path, out["verts"], out["faces"], out["colors"])
+            print('MESH bounds', tuple(round(float(b), 6) for b in bounds), 'grid', tuple(out["sigma"].shape), 'threshold', args.mesh_threshold)
+            print('MESH sigma min {:.6g} max {:.6g} deciles {}'.format(out["sigma_min"], out["sigma_max"],
+                                                                       ' '.join('{:.6g}'.format(d) for d in out["sigma_deciles"])))
+            print('MESH V {} F {}'.format(out["verts"].shape[0], out["faces"].shape[0]))
+            print('Saved mesh at', path)
+    finally:
+        ddist.barrier()
+    return path
+
+
 def train_nerf(args, train_dl, val_dl, hwf, i_split, near, far, render_poses=None, render_img=None):
     H, W, focal = hwf
     H, W = int(H), int(W)
@@ -107,6 +141,9 @@ def train_nerf(args, train_dl, val_dl, hwf, i_split, near, far, render_poses=Non
     bds = {'near': near, 'far': far}
     render_kwargs_train.update(bds)
     render_kwargs_test.update(bds)
+    if args.mesh_only:
+        export_mesh(args, train_dl, far, start, render_kwargs_test)
+        return
     if args.render_test:
         print('TRAIN views are', i_split[0])
         print('VAL views are', i_split[1])
