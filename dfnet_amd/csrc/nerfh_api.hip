@@ -170,8 +170,8 @@ static int check_grad_prec(int prec, const char* fn) {
 // every kernel launch that carries the guard runs on a committed handle.
 static int* range_flag_of(dfn_nerfh_t h) { return h->range_flag; }
 
-// Kernel variant: DFN_MLP_VARIANT=0..12 (A/B aid; nerfh_layout.h: kVariantFacts, kSelectedByDefault), read once.  What it means for a call
-// is nerfh_route.h; the gradient paths (render backward, dfn_mlp_fine_saving) run the base variant's / variant 0's plain kernels on
+// Kernel variant: DFN_MLP_VARIANT=0..12 (A/B aid; nerfh_layout.h: kVariantFacts, kSelectedByDefault), read once.  8 to 11 are retired
+// and mean 12: the same outputs bit for bit, at variant 12's speed.  What a variant means for a call is nerfh_route.h; the gradient paths (render backward, dfn_mlp_fine_saving) run the base variant's / variant 0's plain kernels on
 // the plain table, which their backward kernels read.
 static int mlp_variant_128() {
   static int v = -1;
@@ -191,7 +191,7 @@ static const PackedNet& route_net(dfn_nerfh_t h, bool fine, int prec, const Rout
 static hipError_t launch_route(dfn_nerfh_t h, bool fine, int prec, const Route& r, const MlpArgs& a, hipStream_t s) {
   const int cus = device_cu_count(), width = h->desc.width;
   const PackedNet& n = route_net(h, fine, prec, r);
-  MlpDynArgs d{};
+  MlpLeanArgs d{};
   static_cast<MlpArgs&>(d) = a;
   d.res_blob = n.res_blob;
   d.res_bytes = n.res_bytes;
@@ -202,10 +202,6 @@ static hipError_t launch_route(dfn_nerfh_t h, bool fine, int prec, const Route& 
     case kLaunchFold: return launch_mlp_fold(r.maps, a, cus, s);
     case kLaunchHalf: return launch_mlp_half(fine, r.maps, a, cus, s);
     case kLaunchResident: return launch_mlp_res(fine, d, cus, s);
-    case kLaunchClaimed: return launch_mlp_dyn(fine, d, cus, s);
-    case kLaunchKept: return launch_mlp_pe(fine, d, cus, s);
-    case kLaunchHoisted: return launch_mlp_hoist(fine, d, cus, s);
-    case kLaunchSelected: return launch_mlp_sel(fine, d, cus, s);
     case kLaunchLean: return launch_mlp_lean(fine, d, cus, s);
     case kLaunchPoints: return launch_mlp_pts(fine, prec, a, cus, s, width);
     case kLaunchPointsFold: return launch_mlp_pts_fold(a, cus, s);
@@ -647,7 +643,7 @@ extern "C" int dfn_mlp_coarse_points(dfn_nerfh_t h, int prec, const float* pts, 
   if (!n_rows) return DFN_OK;
   if (!pts || !sigma) return set_error(DFN_ERR_ARG, "dfn_mlp_coarse_points: bad argument");
   if (int rc = check_points(n_rows, N, "dfn_mlp_coarse_points")) return rc;
-  const Route r = coarse_route(kDefaultVariant, h->desc.width, prec, true);
+  const Route r = coarse_route(kPointsVariant, h->desc.width, prec, true);
   const PackedNet& n = route_net(h, false, prec, r);
   MlpArgs a{n.blob, n.tab, n.n_units, pts, nullptr, nullptr, nullptr, sigma, nullptr, (long long)n_rows, N, 0.f, 0.f, nullptr, n.in_scale};
   a.status = range_flag_of(h);
@@ -663,7 +659,7 @@ extern "C" int dfn_mlp_fine_points(dfn_nerfh_t h, int prec, const float* pts, co
     return set_error(DFN_ERR_ARG, "dfn_mlp_fine_points: bad argument (hist_rows must be 1 or n_rows)");
   if (int rc = check_points(n_rows, N, "dfn_mlp_fine_points")) return rc;
   float* table = static_cast<float*>(bias_ws);
-  const Route r = fine_route(kDefaultVariant, h->desc.width, prec, false, false, true);
+  const Route r = fine_route(kPointsVariant, h->desc.width, prec, false, false, true);
   CHECK_HIP(launch_ray_bias(r.fold_table ? h->rb_fold : h->rb, viewdirs, hist, hist_rows, n_rows, table, HS(stream)), "dfn_mlp_fine_points(ray_bias)");
   const PackedNet& n = route_net(h, true, prec, r);
   MlpArgs a{n.blob, n.tab, n.n_units, pts, nullptr, nullptr, table, raw, nullptr, (long long)n_rows, N, 0.f, 0.f, nullptr, n.in_scale};

@@ -60,7 +60,7 @@ struct dfn_nerfh_s {
   // two events (nerfh_train_api.hip: dfn_nerfh_train_backward).
   int render_flags = 0;    // DFN_RENDER_* options of every render entry point (dfn_nerfh_set_render_options)
   int* range_flag = nullptr;   // device int the MLP kernels OR their range-guard bits into (dfn_nerfh_range_status)
-  uint32_t* tile_counter = nullptr;   // kernel variant 8: two device words, the tile heads of the coarse [0] and the fine [1] kernel of the
+  uint32_t* tile_counter = nullptr;   // kernel variant 12: two device words, the tile heads of the coarse [0] and the fine [1] kernel of the
                                       // pass in flight (zeroed on the render stream in front of each pass: one render per handle at a time)
   void* fused = nullptr;       // dfn::fused::State: staging-unit / destination tables of the fused training step (nerfh_fused_api.hip)
   bool train_forward_exact = false;   // which implementation the last dfn_nerfh_train_forward ran (dfn_nerfh_train_backward_rays needs the exact one)

@@ -52,31 +52,21 @@ struct MlpResArgs : MlpArgs {
   uint32_t res_bytes;
 };
 hipError_t launch_mlp_res(bool fine, const MlpResArgs& a, int n_cu, hipStream_t stream);
-// Kernel variant 8 (nerfh_mlp_dyn.hip): variant 7's two kernels with the tiles claimed dynamically.  A workgroup starts on tile
-// blockIdx.x and takes every later one as gridDim.x + atomicAdd(tile_counter, 1); *tile_counter (device) must be 0 when the kernel
-// starts and belongs to this launch alone until it ends.  The pointer rides behind MlpResArgs for the reason given there.
-struct MlpDynArgs : MlpResArgs {
+// Kernel variant 12 (nerfh_mlp_lean.hip): variant 7's two kernels with per-tile work that the result does not need taken out.  What the
+// caller owes them beyond variant 7's arguments:
+//   tile_counter  The tiles are claimed dynamically: a workgroup starts on tile blockIdx.x and takes every later one as gridDim.x +
+//                 atomicAdd(tile_counter, 1); *tile_counter (device) must be 0 when the kernel starts and belongs to this launch alone
+//                 until it ends.
+//   ray_bias      fine = true: the per-ray table already holds in_scale x the seeds (launch_ray_bias with scale = a.in_scale): the
+//                 RAYBIAS layers take the loaded seeds as they are.  No other kernel reads such a table.
+//   div           The magic number by which the kernels turn a point index into a ray index (nerfh_raydiv.h).  The caller leaves it
+//                 alone: the launcher forms it from n_samples.
+// The fields ride behind MlpResArgs in a struct of the kernels' own, for the reason given there.
+struct MlpLeanArgs : MlpResArgs {
   uint32_t* tile_counter;
+  RayDiv div;   // ray_div_of(n_samples), filled in by launch_mlp_lean
 };
-hipError_t launch_mlp_dyn(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
-// Kernel variant 9 (nerfh_mlp_pe.hip): variant 8's two kernels with the positional encoding kept for the skip concat instead of
-// formed twice per tile.  Variant 8's arguments, networks, resident blob and counter.
-hipError_t launch_mlp_pe(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
-// Kernel variant 10 (nerfh_mlp_hoist.hip): variant 9's plain fused fine kernel on a per-ray table that already holds in_scale x the
-// seeds (launch_ray_bias with scale = a.in_scale): its RAYBIAS layers take the loaded seeds as they are, and its uniform state is
-// formed at the use instead of parked in VGPR lanes.  Variant 9's arguments otherwise.
-// fine = false is refused: the coarse kernel has no per-ray seeds and stays launch_mlp_pe's.
-hipError_t launch_mlp_hoist(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
-// Kernel variant 11 (nerfh_mlp_sel.hip): variant 10's fine kernel (fine = true: the scaled table, as launch_mlp_hoist) and variant 9's
-// coarse kernel (fine = false) with one select per head value.  Variant 9's arguments.
-hipError_t launch_mlp_sel(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
-// Kernel variant 12 (nerfh_mlp_lean.hip): variant 11's two kernels with a leaner tile seam and range guard.  The caller passes variant
-// 11's arguments; the launcher adds the magic number by which the kernels turn a point index into a ray index (nerfh_raydiv.h), in a
-// struct of the kernels' own for the reason given at MlpResArgs.
-struct MlpLeanArgs : MlpDynArgs {
-  RayDiv div;   // ray_div_of(n_samples)
-};
-hipError_t launch_mlp_lean(bool fine, const MlpDynArgs& a, int n_cu, hipStream_t stream);
+hipError_t launch_mlp_lean(bool fine, const MlpLeanArgs& a, int n_cu, hipStream_t stream);
 
 // The points flavour (nerfh_mlp_pts*.hip): a.rays_o is pts [n_rays, n_samples, 3] (n_rays = query rows), a.rays_d, a.z and a.partial
 // are unused (a.partial must be null: the raw route only), a.ray_bias has one row per query row.  launch_mlp_pts: f16 / exact fp32 at
@@ -118,8 +108,8 @@ struct RayBiasWeights {       // device pointers, fp32
   int hist_bin, dim_a, dim_t, n_vocab;
   int nout;                   // outputs per table = netwidth / 2 (w_dir, w_tr are [*][nout]; the table row is 2 * nout floats)
 };
-// scale: every table entry is stored multiplied by it (1 = the seeds themselves, the kernel every route but variant 10's fused fine
-// one has always run; otherwise the fine network's in_scale, a power of two: launch_mlp_hoist)
+// scale: every table entry is stored multiplied by it (1 = the seeds themselves, the kernel every route but variant 12's fused fine
+// one has always run; otherwise the fine network's in_scale, a power of two: launch_mlp_lean)
 hipError_t launch_ray_bias(const RayBiasWeights& w, const float* viewdirs, const float* hist,
                            size_t hist_rows, size_t n_rays, float* table, hipStream_t stream, float scale = 1.f);
 

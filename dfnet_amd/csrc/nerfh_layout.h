@@ -158,7 +158,7 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //   variant 1: 4 waves per workgroup, 2 workgroups per CU, a unit = 2 M-blocks (f16) / one M-block (f32)
 //   variant 2: 4 waves per workgroup x 3 point blocks, 1 workgroup per CU (1 wave per SIMD, 512 VGPRs), unit as variant 0
 //   variant 3: variant 0's geometry without the pipelined epilogue (A/B reference)
-// 4 to 11 exist in split-f16 at netwidth 128 only and each is the one before it with one thing more (kVariantFacts); every other
+// 4 to 12 exist in split-f16 at netwidth 128 only and each is the one before it with more (kVariantFacts); every other
 // arithmetic mode, width and gradient path under them runs the `base` variant's kernels on its networks, and which kernel, network and
 // per-ray table a call runs is nerfh_route.h:
 //   variant 4: variant 0 on 16x16x32 MFMAs (PrecX3M16)
@@ -171,62 +171,56 @@ struct PrecX3M16 { static constexpr int kSlotsPerChunk = 8, kLaneBytes = 32; sta
 //              kCoarseResident / kFineResident below): copied in once per workgroup behind the input slots, they leave the streamed
 //              unit table (coarse 17 -> 14 units, fine 26 -> 22 per 256-point tile) with their barriers and DMA round trips; the same
 //              fragments, MFMAs and conversion pieces in the same order: variant 6's outputs bit for bit
-//   variant 8: the tiles of variant 7's two kernels CLAIMED from a device counter instead of dealt blockIdx.x, + gridDim.x, ...
-//              (nerfh_mlp_dyn.hip): scheduling only, on variant 7's packed networks (it packs none of its own, so it is no index of
-//              dfn_nerfh_s::net): variant 7's outputs bit for bit
-//   variant 9: the positional encoding of variant 8's two kernels formed ONCE per tile and KEPT for the skip concat in front of layer 5
-//              instead of formed a second time there (nerfh_mlp_pe.hip; trunk() in nerfh_mlp_core.h): 32 registers live across layers
-//              2 to 4, which the 16x16x32 kernels have free, against 231 vector instructions per tile and wave, 32 of them quarter-rate
-//              v_sin / v_cos.  The kept operand is the value the second evaluation gives: variant 8's outputs bit for bit, on variant
-//              7's packed networks, variant 8's per-ray table and tile counters
-//   variant 10: variant 9 with per-tile work the result does not need HOISTED out of the fused fine kernel's tile loop
-//              (nerfh_mlp_hoist.hip): ray_bias_kernel writes the table of that route multiplied by the fine network's in_scale, once
-//              per pass, instead of layer() multiplying the loaded seeds of the two RAYBIAS layers on every tile; and uniform values
-//              (the weight DMA's per-wave piece, prefetch slot addresses, argument pointers) are formed where they are used instead of
-//              parked in VGPR lanes and read back by v_readlane_b32 (79 -> 39 parked SGPRs, 231 -> 62 lane reads per tile).  The same
-//              values by the same arithmetic: variant 9's outputs bit for bit, on its networks, resident blob and counters.  The
-//              coarse kernel has no RAYBIAS layer and parks nothing: variant 9's runs
-//   variant 11: variant 10 with the head values of a PrecX3M16 head block SELECTED by one v_cndmask_b32 each (nerfh_mlp_sel.hip;
-//              layer() in nerfh_mlp_core.h: the two candidates go through an opaque copy, so the select of two extracted elements is
-//              not rewritten as one extract with a lane-dependent index -- a chain of 15 compares and 16 selects per index register,
-//              whose masks were the scalar pressure variant 10 fought: 4 023 -> 3 754 vector instructions per fine tile, 39 -> 0
-//              parked SGPRs).  The same value on the same lane: variant 10's outputs bit for bit, on its networks, resident blob,
-//              scaled table and counters.  The unit has a coarse kernel too (variant 9's code with the select: 2 728 -> 2 707)
-//   variant 12: variant 11 with a LEAN tile seam and range guard (nerfh_mlp_lean.hip): in the fine kernel the eight head activations are
-//              evaluated as four (the static pre-activations ride on lanes 32..63, which carry no sample there); in both kernels the
-//              point -> ray division is a multiply-high and a shift (nerfh_raydiv.h) and the range guard of the ReLU conversions is
-//              one v_pk_maximum3_f16 per two pieces instead of one v_pk_max_u16 per piece (336 -> 168 / 256 -> 128 per tile):
-//              3 754 -> 3 414 / 2 707 -> 2 556 vector instructions.  The same values on the same lanes and the same flag: variant 11's
-//              outputs bit for bit, on its networks, resident blob, scaled table and counters
+//   variant 12: variant 7's two kernels with per-tile work that the result does not need taken out (the lean unit, nerfh_mlp_lean.hip),
+//              on variant 7's packed networks (it packs none of its own, so it is no index of dfn_nerfh_s::net) and resident blob.
+//              Every technique gives the same values on the same lanes and the same range flag: variant 7's outputs bit for bit, which
+//              makes variant 7 the independently written anchor that the lean unit is tested against.  One paragraph per technique:
+//              CLAIMED tiles: the tiles are claimed from a device counter instead of dealt blockIdx.x, + gridDim.x, ...: scheduling
+//              only.  Both tile counters are zeroed in front of a pass in which either kernel is the lean unit's.
+//              KEPT encoding: the positional encoding is formed ONCE per tile and kept for the skip concat in front of layer 5 instead
+//              of formed a second time there (trunk() in nerfh_mlp_core.h): 32 registers live across layers 2 to 4, which the
+//              16x16x32 kernels have free, against 231 vector instructions per tile and wave, 32 of them quarter-rate v_sin / v_cos.
+//              The kept operand is the value the second evaluation gives.
+//              SCALED seeds and uniform values at their use, in the fused fine kernel: ray_bias_kernel writes the table of that route
+//              multiplied by the fine network's in_scale, once per pass, instead of layer() multiplying the loaded seeds of the two
+//              RAYBIAS layers on every tile; and uniform values (the weight DMA's per-wave piece, prefetch slot addresses, argument
+//              pointers) are formed where they are used instead of parked in VGPR lanes and read back by v_readlane_b32 (79 -> 39
+//              parked SGPRs, 231 -> 62 lane reads per tile).  The coarse kernel has no RAYBIAS layer and parks nothing.
+//              ONE SELECT per head value of a PrecX3M16 head block (layer() in nerfh_mlp_core.h: the two candidates go through an
+//              opaque copy, so the select of two extracted elements is not rewritten as one extract with a lane-dependent index -- a
+//              chain of 15 compares and 16 selects per index register, whose masks were the scalar pressure behind the parked SGPRs:
+//              4 023 -> 3 754 vector instructions per fine tile, 39 -> 0 parked SGPRs; coarse 2 728 -> 2 707).
+//              LEAN tile seam and range guard: in the fine kernel the eight head activations are evaluated as four (the static
+//              pre-activations ride on lanes 32..63, which carry no sample there); in both kernels the point -> ray division is a
+//              multiply-high and a shift (nerfh_raydiv.h) and the range guard of the ReLU conversions is one v_pk_maximum3_f16 per two
+//              pieces instead of one v_pk_max_u16 per piece (336 -> 168 / 256 -> 128 per tile): 3 754 -> 3 414 / 2 707 -> 2 556
+//              vector instructions.
+//   variants 8 to 11 were the steps by which variant 12 was reached, one technique at a time in the order above, each with a unit of its
+//              own that gave its predecessor's outputs bit for bit (LABBOOK.md).  They are retired: the numbers stay accepted and
+//              mean variant 12 (kVariantFacts), whose outputs are the bits theirs were
 constexpr int kVariants = 8;   // packed networks per (coarse | fine, arithmetic): dfn_nerfh_s::net
 constexpr int kFoldVariant = 5;
 constexpr int kHalfVariant = 6;
 constexpr int kResidentVariant = 7;
-constexpr int kDynVariant = 8;
-constexpr int kKeptVariant = 9;
-constexpr int kHoistVariant = 10;
-constexpr int kSelVariant = 11;
 constexpr int kLeanVariant = 12;
 constexpr int kLastVariant = kLeanVariant;   // DFN_MLP_VARIANT = 0 .. kLastVariant
-// kept: the encoding, for the skip concat; hoisted: the fused fine kernel is nerfh_mlp_hoist.hip's and its per-ray table holds in_scale x the seeds;
-// sel: the coarse and the fused fine kernel are nerfh_mlp_sel.hip's (the fine one reads the scaled table as variant 10's);
-// lean: they are nerfh_mlp_lean.hip's (the same table)
-struct VariantFacts { int base; bool fold, half, resident, claimed, kept, hoisted, sel, lean; };
+// lean: the coarse and the plain fused fine kernel are nerfh_mlp_lean.hip's: they claim their tiles and the fine one's per-ray table
+// holds in_scale x the seeds
+struct VariantFacts { int base; bool fold, half, resident, lean; };
+constexpr VariantFacts kLeanFacts = {4, true, true, true, true};
 constexpr VariantFacts kVariantFacts[kLastVariant + 1] = {
     {0, false, false, false, false}, {1, false, false, false, false}, {2, false, false, false, false}, {3, false, false, false, false},
     {4, false, false, false, false},
     {4, true, false, false, false},   // kFoldVariant
     {4, true, true, false, false},    // kHalfVariant
     {4, true, true, true, false},     // kResidentVariant
-    {4, true, true, true, true},      // kDynVariant
-    {4, true, true, true, true, true},   // kKeptVariant
-    {4, true, true, true, true, true, true},   // kHoistVariant: variant 9's row (its plain kernels are variant 4's too) and the new fact
-    {4, true, true, true, true, true, true, true},   // kSelVariant: variant 10's row and the new fact
-    {4, true, true, true, true, true, true, true, true},   // kLeanVariant: variant 11's row and the new fact
+    kLeanFacts, kLeanFacts, kLeanFacts, kLeanFacts,   // 8 to 11, retired: kLeanVariant's row
+    kLeanFacts,                       // kLeanVariant
 };
-// What a process runs without DFN_MLP_VARIANT; the variant whose kernels the point queries run whatever it says
+// kSelectedByDefault: what a process runs without DFN_MLP_VARIANT.  kPointsVariant: the variant whose routes the point queries take
+// whatever DFN_MLP_VARIANT says (they have no resident or lean flavour: variant 6's coarse and variant 5's fine kernel)
 constexpr int kSelectedByDefault = kLeanVariant;
-constexpr int kDefaultVariant = kResidentVariant;
+constexpr int kPointsVariant = kResidentVariant;
 template <class P> DFN_HD constexpr int unit_mb(int variant) {
   return P::kSlotsPerChunk == 1 ? 1 : (P::kSplit ? 2 : (variant == 1 ? 2 : 8));
 }

@@ -27,27 +27,25 @@
 
 namespace dfn {
 
-// One translation unit (= one code object) per flavour: a wrapper file (nerfh_mlp_{maps,fold,half,res,dyn,pe,pts,pts_fold,pts_half}.hip)
+// One translation unit (= one code object) per flavour: a wrapper file (nerfh_mlp_{maps,fold,half,res,lean,pts,pts_fold,pts_half}.hip)
 // sets DFN_MLP_*_TU flags and includes this file, and gets the kernels and the launcher named below and nothing else, so the code
 // objects of the other units do not change by a token when a unit is added.  The flags are cumulative (nerfh_layout.h "Kernel variants"):
 //   DFN_MLP_MAPS_TU   launch_mlp_maps: the MAPS instantiations of the plain fine kernels (the render-maps segment record)
 //   DFN_MLP_FOLD_TU   variant 5: the fine kernel with the folded tail (kFineFoldSeq)
 //   DFN_MLP_HALF_TU   variant 6, on FOLD: half-height head M-blocks (layer<..., HALF>), coarse and fine
 //   DFN_MLP_RES_TU    variant 7, on HALF: small layers resident in LDS (layer<..., RES>), MlpResArgs
-//   DFN_MLP_DYN_TU    variant 8, on RES: tiles claimed from a device counter (Stager::claim / next), MlpDynArgs
-//   DFN_MLP_PE_TU     variant 9, on DYN: the positional encoding kept for the skip concat (trunk(): kEncodingKept), MlpDynArgs
+//   DFN_MLP_LEAN_TU   variant 12, on RES: the lean unit (nerfh_mlp_lean.hip lists its techniques), coarse and fine: tiles claimed from a
+//                     device counter (Stager::claim / next), the positional encoding kept for the skip concat (trunk(): kEncodingKept),
+//                     the fine kernel's per-ray seeds stored at the accumulators' scale (layer(): RAYBIAS takes them as loaded), uniform
+//                     values formed at their use (wave_here / args_here below, stage_issue_at), one select per head value (layer(): the
+//                     candidates behind an opaque copy), the packed head activations (kLeanAct4), point -> ray by a magic number
+//                     (DFN_RAY_OF) and the range guard by maximum3 (X3Piece::C); MlpLeanArgs = MlpResArgs + the tile counter + the
+//                     magic number
 //   DFN_MLP_PTS_TU    the points flavour, on none, FOLD or HALF: the inputs are loaded from pts [n_rows, n_samples, 3] (MlpArgs::rays_o)
 //                     instead of being formed as o + d z; the raw route only (no depths, so no compositing)
-//   DFN_MLP_HOIST_TU  variant 10, on PE: the fine kernel's per-ray seeds are stored at the accumulators' scale (layer(): RAYBIAS takes
-//                     them as loaded) and uniform values are formed at their use (wave_here / args_here below, stage_issue_at),
-//                     MlpDynArgs; the unit has no coarse kernel (variant 9's runs)
-//   DFN_MLP_SEL_TU    variant 11, on HOIST: one select per head value (layer(): the candidates behind an opaque copy), coarse and fine,
-//                     MlpDynArgs; the coarse kernel is variant 9's code under the unit's flags
-//   DFN_MLP_LEAN_TU   variant 12, on SEL: the tile seam and the range guard with less vector work (nerfh_mlp_lean.hip: its three parts and
-//                     their switches), coarse and fine, MlpLeanArgs = MlpDynArgs + the point -> ray magic number
 //   DFN_MLP_STATIC_TU the coarse network's training query (nerfw.py:47-60, 326-343), on PTS, plain or FOLD: the fine kernel cut off
 //                     behind static_rgb (kCoarseStaticSeq / kCoarseStaticFoldSeq), 4 floats per point; the unit has that kernel alone
-// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_dyn|_pe|_hoist|_sel|_lean][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_dyn|_pe|_hoist|_sel|_lean];
+// Kernels: nerfh_{fine,coarse}[_fold|_half|_res|_lean][_pts]_kernel; launcher: launch_mlp[_maps][_pts][_fold|_half|_res|_lean];
 // DFN_MLP_STATIC_TU: nerfh_coarse_static[_fold]_pts_kernel, launch_mlp_static_pts[_fold].
 #if defined(DFN_MLP_STATIC_TU) && (!defined(DFN_MLP_PTS_TU) || defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_MAPS_TU))
 #error "the static query exists in the points flavour, plain or folded"
@@ -55,36 +53,12 @@ namespace dfn {
 #if defined(DFN_MLP_RES_TU) && (!defined(DFN_MLP_HALF_TU) || defined(DFN_MLP_PTS_TU))
 #error "the resident layers exist in the half-height render kernels"
 #endif
-#if defined(DFN_MLP_DYN_TU) && !defined(DFN_MLP_RES_TU)
-#error "the claimed tiles exist in the kernels with resident layers"
-#endif
-#if defined(DFN_MLP_PE_TU) && !defined(DFN_MLP_DYN_TU)
-#error "the kept encoding exists in the kernels with claimed tiles"
-#endif
-#if defined(DFN_MLP_HOIST_TU) && !defined(DFN_MLP_PE_TU)
-#error "the hoisted per-tile work is taken out of the kernels with the kept encoding"
-#endif
-#if defined(DFN_MLP_SEL_TU) && !defined(DFN_MLP_HOIST_TU)
-#error "the selected head values exist in the unit with the hoisted per-tile work"
-#endif
-#if defined(DFN_MLP_LEAN_TU) && !defined(DFN_MLP_SEL_TU)
-#error "the lean seam and range guard exist in the unit with the selected head values"
+#if defined(DFN_MLP_LEAN_TU) && !defined(DFN_MLP_RES_TU)
+#error "the lean unit's techniques exist in the kernels with resident layers"
 #endif
 #if defined(DFN_MLP_LEAN_TU)
 #define DFN_TU_TAG _lean
 #define DFN_MLP_KARGS MlpLeanArgs
-#elif defined(DFN_MLP_SEL_TU)
-#define DFN_TU_TAG _sel
-#define DFN_MLP_KARGS MlpDynArgs
-#elif defined(DFN_MLP_HOIST_TU)
-#define DFN_TU_TAG _hoist
-#define DFN_MLP_KARGS MlpDynArgs
-#elif defined(DFN_MLP_PE_TU)
-#define DFN_TU_TAG _pe
-#define DFN_MLP_KARGS MlpDynArgs
-#elif defined(DFN_MLP_DYN_TU)
-#define DFN_TU_TAG _dyn
-#define DFN_MLP_KARGS MlpDynArgs
 #elif defined(DFN_MLP_RES_TU)
 #define DFN_TU_TAG _res
 #define DFN_MLP_KARGS MlpResArgs
@@ -138,19 +112,19 @@ constexpr bool kResident = true;
 #else
 constexpr bool kResident = false;
 #endif
-// the tile a workgroup computes after `tile` (inside the kernels' tile loops): dealt, or claimed (kernel variant 8: Stager::next)
-#ifdef DFN_MLP_DYN_TU
+// What the lean unit (DFN_MLP_LEAN_TU) does differently at the tile seam; every other unit takes the #else forms.
+//   DFN_NEXT_TILE: the tile a workgroup computes after `tile` (inside the kernels' tile loops): claimed (Stager::next), or dealt.
+//   wave_here / args_here: uniform values the tile loop needs once per tile are formed where they are used.  As loop invariants LLVM
+//   hoists them to the prologue, where the scalar file cannot hold them all: they are parked in VGPR lanes and every use costs a
+//   v_readlane_b32 on the vector pipe (79 parked SGPRs and 231 lane reads per tile in the fine kernel without this).  wave_here: the
+//   wave index behind an opaque copy, so that what is derived from it (LDS slot addresses) is scalar arithmetic at the use.  args_here:
+//   the kernel arguments read from the kernarg segment at the use (one s_load) instead of held, or parked, for the whole kernel.
+//   kLeanAct4: the packed head activations of the fused fine kernel (the transient branch's end).
+//   DFN_RAY_OF: the ray of point q (q < 2^31: launch_tiles), by multiply-high and shift with the launch's magic number
+//   (nerfh_raydiv.h; MlpLeanArgs::div, two SGPRs) where the other units divide: about 16 vector instructions per lane and point, one
+//   of them a quarter-rate reciprocal, at the tile seam.
+#ifdef DFN_MLP_LEAN_TU
 #define DFN_NEXT_TILE (static_cast<long long>(st.next))
-#else
-#define DFN_NEXT_TILE (tile + gridDim.x)
-#endif
-
-// Kernel variant 10 (DFN_MLP_HOIST_TU): uniform values the tile loop needs once per tile are formed where they are used.  As loop
-// invariants LLVM hoists them to the prologue, where the scalar file cannot hold them all: they are parked in VGPR lanes and every use
-// costs a v_readlane_b32 on the vector pipe (79 parked SGPRs and 231 lane reads per tile in variant 9's fine kernel).  wave_here: the
-// wave index behind an opaque copy, so that what is derived from it (LDS slot addresses) is scalar arithmetic at the use.  args_here:
-// the kernel arguments read from the kernarg segment at the use (one s_load) instead of held, or parked, for the whole kernel.
-#ifdef DFN_MLP_HOIST_TU
 DFN_DEV int wave_here(const Stager& st) {
   int w = st.wave;
   asm volatile("" : "+s"(w));
@@ -163,23 +137,13 @@ DFN_DEV const_kargs* args_here() {
   return reinterpret_cast<const_kargs*>(p);
 }
 #define DFN_ARGS_HERE(a) (*args_here())
-#else
-DFN_DEV int wave_here(const Stager& st) { return st.wave; }
-#define DFN_ARGS_HERE(a) (a)
-#endif
-
-// Kernel variant 12, the packed head activations of the fused fine kernel (nerfh_mlp_lean.hip: DFN_LEAN_ACT4); off in every other unit.
-#if defined(DFN_MLP_LEAN_TU) && DFN_LEAN_ACT4
 constexpr bool kLeanAct4 = true;
-#else
-constexpr bool kLeanAct4 = false;
-#endif
-// The ray of point q (q < 2^31: launch_tiles).  Variant 12 takes it by multiply-high and shift with the launch's magic number
-// (nerfh_raydiv.h; MlpLeanArgs::div, two SGPRs) where the other units divide: about 16 vector instructions per lane and point, one of
-// them a quarter-rate reciprocal, at the tile seam.
-#if defined(DFN_MLP_LEAN_TU) && DFN_LEAN_MAGIC
 #define DFN_RAY_OF(a, q) ray_div(q, RayDiv{(a).div.magic, (a).div.shift})
 #else
+#define DFN_NEXT_TILE (tile + gridDim.x)
+DFN_DEV int wave_here(const Stager& st) { return st.wave; }
+#define DFN_ARGS_HERE(a) (a)
+constexpr bool kLeanAct4 = false;
 #define DFN_RAY_OF(a, q) ((q) / uint32_t((a).n_samples))
 #endif
 
@@ -216,7 +180,7 @@ static_assert(resident_set_supported(false) && resident_set_supported(true), "a 
 static_assert(lds_bytes<PrecX3M16, unit_mb<PrecX3M16>(0), 8, 1>() + resident_bytes<PrecX3M16>(true) <= kLdsBytes &&
               lds_bytes<PrecX3M16, unit_mb<PrecX3M16>(0), 8, 1>() + resident_bytes<PrecX3M16>(false) <= kLdsBytes,
               "ring + input slots + resident layers must fit the LDS of a CU");
-// Kernel variant 8: the word the claimed tile is published through, behind the resident region (16 bytes keep the region's alignment)
+// The lean unit: the word the claimed tile is published through, behind the resident region (16 bytes keep the region's alignment)
 constexpr uint32_t kClaimBytes = 16;
 static_assert(lds_bytes<PrecX3M16, unit_mb<PrecX3M16>(0), 8, 1>() + resident_bytes<PrecX3M16>(true) + kClaimBytes <= kLdsBytes &&
               lds_bytes<PrecX3M16, unit_mb<PrecX3M16>(0), 8, 1>() + resident_bytes<PrecX3M16>(false) + kClaimBytes <= kLdsBytes,
@@ -262,7 +226,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
   stage_resident(st, smem, a.res_blob, resident_bytes<P>(false), lds_bytes<P, UMB, WAVES, NB, W>());
 #endif
   stage_prime(st, smem, max_unit_bytes<P>(UMB, W), ring_slots<P, W>());
-#ifdef DFN_MLP_DYN_TU
+#ifdef DFN_MLP_LEAN_TU
   // claimed tiles: blockIdx.x first, then gridDim.x + (the counter before this workgroup's add); see Stager.  A workgroup without a
   // first tile has returned above without claiming.
   st.claim = 0; st.grid = gridDim.x; st.next = 0; st.n_tiles = uint32_t(n_tiles); st.more = false;
@@ -401,7 +365,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
     for (int c = 0; c < 3; ++c) { oin[nb][c] = a.rays_o[ray_of[nb] * 3 + c]; din[nb][c] = a.rays_d[ray_of[nb] * 3 + c]; }
 #endif
   }
-#ifdef DFN_MLP_DYN_TU
+#ifdef DFN_MLP_LEAN_TU
   // claimed tiles, as in the coarse kernel: st.next replaces tile + gridDim.x in the three places that name the next tile -- st.more
   // (mid_sync), the input prefetch behind LY_TE0F's mid_sync and tile_coords at the tile's end, all far behind the tile's first mid_sync
   st.claim = 0; st.grid = gridDim.x; st.next = 0; st.n_tiles = uint32_t(n_tiles); st.more = false;
@@ -488,7 +452,7 @@ __global__ __launch_bounds__(WAVES * 64, (mlp_min_blocks<P, WAVES, NB, W>())) vo
 #endif
     sign128(7, hid[0]);   // layer 8's output, completed inside the layer above
     float o[NB][9];
-    // kernel variant 12 (kLeanAct4): the four static pre-activations, kept until the transient head's are there (the transient branch's end)
+    // the lean unit (kLeanAct4): the four static pre-activations, kept until the transient head's are there (the transient branch's end)
     [[maybe_unused]] float pre_s[NB][4];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
@@ -785,7 +749,7 @@ static hipError_t launch_tiles(void (*kern)(A), bool& attr_done, uint32_t lds, c
   hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, b);
   return hipGetLastError();
 }
-// the geometry of the PrecX3M16 kernels of variants 5 to 8: variant 4's (launch_one<PrecX3M16, false, 8, 2, 1, 1, true> below)
+// the geometry of the PrecX3M16 kernels of variants 5 to 12: variant 4's (launch_one<PrecX3M16, false, 8, 2, 1, 1, true> below)
 using PM = PrecX3M16;
 constexpr int kMWaves = 8, kMUmb = unit_mb<PM>(0), kMNb = 1, kMPpt = kMWaves * kMNb * 32;
 
@@ -863,32 +827,21 @@ hipError_t DFN_LAUNCH_MLP(bool fine, int prec, const MlpArgs& a, int n_cu, hipSt
 #elif defined(DFN_MLP_RES_TU)
 // launch_mlp_res: variant 7's kernels, variant 6's geometry with the resident region behind the input slots.  coarse; fine with the
 // compositing fused, plain flavour -- the maps flavour stays with launch_mlp_half, the raw route with launch_mlp_fold.
-// launch_mlp_dyn: variant 8's, the same with the claimed-tile word behind the region.  The grid is variant 7's: min(tiles, CUs)
-// workgroups, each starting on tile blockIdx.x; *a.tile_counter is 0 at the start (the caller's memset).
-// launch_mlp_pe: variant 9's, variant 8's arguments, LDS map and grid (this body under DFN_MLP_PE_TU: nerfh_mlp_pe.hip).
-// launch_mlp_hoist: variant 10's fine kernel, variant 9's arguments, LDS map and grid; a.ray_bias holds in_scale x the seeds
-// (nerfh_mlp_hoist.hip); no coarse kernel.
-// launch_mlp_sel: variant 11's two kernels (nerfh_mlp_sel.hip): launch_mlp_hoist's fine kernel and launch_mlp_pe's coarse kernel with one
-// select per head value, their arguments, LDS map and grid.
-// launch_mlp_lean: variant 12's two kernels (nerfh_mlp_lean.hip): launch_mlp_sel's with the leaner seam and range guard, its arguments
-// (the magic number of a.n_samples is formed here), LDS map and grid.
+// launch_mlp_lean (this body in nerfh_mlp_lean.hip): variant 12's kernels, the same with the claimed-tile word behind the region.  The
+// grid is variant 7's: min(tiles, CUs) workgroups, each starting on tile blockIdx.x; *a.tile_counter is 0 at the start (the caller's
+// memset); a.ray_bias holds in_scale x the seeds; the magic number of a.n_samples is formed here.
 #ifdef DFN_MLP_LEAN_TU
-hipError_t DFN_LAUNCH_MLP(bool fine, const MlpDynArgs& dyn, int n_cu, hipStream_t stream) {
-  MlpLeanArgs a{};
-  static_cast<MlpDynArgs&>(a) = dyn;
-  a.div = ray_div_of(uint32_t(dyn.n_samples > 0 ? dyn.n_samples : 1));
+hipError_t DFN_LAUNCH_MLP(bool fine, const MlpLeanArgs& in, int n_cu, hipStream_t stream) {
+  MlpLeanArgs a = in;
+  a.div = ray_div_of(uint32_t(in.n_samples > 0 ? in.n_samples : 1));
 #else
-hipError_t DFN_LAUNCH_MLP(bool fine, const DFN_MLP_KARGS& a, int n_cu, hipStream_t stream) {
+hipError_t DFN_LAUNCH_MLP(bool fine, const MlpResArgs& a, int n_cu, hipStream_t stream) {
 #endif
-#if defined(DFN_MLP_HOIST_TU) && !defined(DFN_MLP_SEL_TU)
-  void (*kern)(DFN_MLP_KARGS) = fine ? DFN_FINE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true> : nullptr;
-#else
   void (*kern)(DFN_MLP_KARGS) = fine ? DFN_FINE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true> : DFN_COARSE_KERNEL<PM, false, kMWaves, kMUmb, kMNb, true>;
-#endif
   uint32_t lds = lds_bytes<PM, kMUmb, kMWaves, kMNb>() + resident_bytes<PM>(fine);
   if (a.masks || (fine && !a.partial)) kern = nullptr;
   if (!a.res_blob || a.res_bytes != resident_bytes<PM>(fine)) kern = nullptr;   // the kernels copy exactly this many bytes
-#ifdef DFN_MLP_DYN_TU
+#ifdef DFN_MLP_LEAN_TU
   if (!a.tile_counter) kern = nullptr;
   lds += kClaimBytes;
 #endif

@@ -54,8 +54,8 @@ struct Stager {
   unsigned long long* trace;
   int n_trace;
   bool more;           // another tile follows this one (wave-uniform)
-#ifdef DFN_MLP_DYN_TU
-  // Kernel variant 8 (nerfh_mlp_dyn.hip): the tile after this one is CLAIMED -- lane 0 of wave 0 issues a returning atomic add on the
+#ifdef DFN_MLP_LEAN_TU
+  // The lean unit (nerfh_mlp_lean.hip): the tile after this one is CLAIMED -- lane 0 of wave 0 issues a returning atomic add on the
   // launch's tile counter at the top of the tile; the first mid_sync() of the tile publishes the result through one LDS word around
   // its barrier and sets `next` and `more` in every wave.  `more` is first read by the mid_sync() of the tile's second-to-last
   // streamed unit (the wrap to the next tile), many units later.
@@ -107,8 +107,8 @@ DFN_DEV void lds_dma_b32(const void* gptr, const char* lds_dst) {
   const uint32_t off = (uint32_t)(size_t)DFN_LDS_PTR(lds_dst);
   asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dword %0, off" ::"v"(gptr), "s"(off) : "memory");
 }
-#ifdef DFN_MLP_DYN_TU
-// Kernel variant 8: one lane's claim, a returning device-scope atomic add whose result nobody waits for here (mid_sync's vmcnt(0) does).
+#ifdef DFN_MLP_LEAN_TU
+// The lean unit: one lane's claim, a returning device-scope atomic add whose result nobody waits for here (mid_sync's vmcnt(0) does).
 // The pointer goes through an opaque vector register: on an address it can prove wave-uniform LLVM's atomic optimiser rewrites the add
 // as a wave reduction + v_readfirstlane of the result, and with that a wait for the whole L2 round trip right behind the atomic.
 // Named a GLOBAL address again behind it: a flat atomic counts in vmcnt and lgkmcnt both and turns every counted wait behind it into 0.
@@ -125,11 +125,11 @@ DFN_DEV uint32_t claim_tile(uint32_t* counter) {
 
 DFN_DEV void stage_issue_at(const Stager& st, char* smem, uint32_t off, uint32_t size, uint32_t lds_off) {
   const char* src = st.blob + off + st.lane * 16;
-#ifdef DFN_MLP_HOIST_TU
-  // kernel variant 10: whether this wave issues DMA and where its first piece lies are formed HERE from the wave index.  As loop
+#ifdef DFN_MLP_LEAN_TU
+  // the lean unit: whether this wave issues DMA and where its first piece lies are formed HERE from the wave index.  As loop
   // invariants of the tile loop the condition (a 64-bit lane mask) and the 64-bit offset (wave * kPiece, 0) were hoisted to the
   // prologue, parked in VGPR lanes and read back by v_readlane_b32 pairs in front of every unit's DMA: 88 of the 223 reads of parked
-  // SGPRs per tile in variant 9's fine kernel.  Behind the opaque copy they are one scalar compare and one scalar shift per unit.
+  // SGPRs per tile in the fine kernel without this.  Behind the opaque copy they are one scalar compare and one scalar shift per unit.
   uint32_t w = st.wave;
   asm volatile("" : "+s"(w));
   if (int(w) >= st.dma_waves) return;
@@ -182,7 +182,7 @@ DFN_DEV void stage_prime(Stager& st, char* smem, uint32_t unit_stride, uint32_t 
 // STREAMED unit, which every wave has left once it is past u's barrier -- a resident layer between two streamed units is computed
 // out of this region and touches no ring slot, and `st.u == 0` still names the tile's last streamed unit whether or not resident
 // layers follow it, so the wrap to the next tile (units 0 and 1 issued from the last two streamed units' mid_sync) is unchanged.
-// Kernel variant 8 (claimed tiles) leaves this as it is too: units 0 and 1 are the same bytes whichever tile comes next, so the wrap
+// The lean unit's claimed tiles leave this as it is too: units 0 and 1 are the same bytes whichever tile comes next, so the wrap
 // asks only WHETHER a tile follows (st.more), never which; st.more is set by the tile's first mid_sync (streamed unit 0 or 1 of 14 / 22)
 // and read from the second-to-last streamed unit's on, st.u == 0 names the same unit, and a workgroup whose claim is past the last
 // tile sees more == false exactly where the static deal's last tile did: nothing is issued into a ring nobody will read.
@@ -212,7 +212,7 @@ DFN_DEV void mid_sync(Stager& st, char* smem) {
   // does not re-wait for them later with a count that the untracked DMA loads would turn into a wait for the DMA)
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   asm volatile("" ::: "memory");
-#ifdef DFN_MLP_DYN_TU
+#ifdef DFN_MLP_LEAN_TU
   // the tile's first mid_sync: the claim issued at the top of the tile has returned with the wait above.  Wave 0 puts the claimed tile
   // into the LDS word and sees it written (lgkmcnt(0)) BEFORE it signals this unit's barrier; no barrier is added.  The word is
   // rewritten one tile later, behind every barrier of this tile: every wave has read it by then (it reads right behind this barrier).
@@ -243,7 +243,7 @@ DFN_DEV void mid_sync(Stager& st, char* smem) {
   }
   ++st.n_trace;
 #endif
-#ifdef DFN_MLP_DYN_TU
+#ifdef DFN_MLP_LEAN_TU
   if (st.claiming) {   // every wave, behind the barrier wave 0 wrote in front of
     st.next = __builtin_amdgcn_readfirstlane(*claim_word(smem, st.claim_lds));
     st.more = st.next < st.n_tiles;
@@ -441,8 +441,7 @@ DFN_DEV void store_hidden_piece(const f32x16& acc, typename FragOf<P>::type (&ou
 
 // The split-f16 conversion piece in three parts, so that a K-chunk can place them BETWEEN its three dependent MFMAs (A after the
 // first, B after the second, C after the third) instead of as one block behind them: the parts of store_hidden_piece<PrecX3>.
-#if defined(DFN_MLP_LEAN_TU) && DFN_LEAN_MAX3
-#define DFN_X3_GUARD_MAX3 1
+#ifdef DFN_MLP_LEAN_TU
 #define DFN_X3_HOLD , rhold   // layer(): the even piece's hi pair, handed to the odd piece's part C
 #else
 #define DFN_X3_HOLD
@@ -477,8 +476,8 @@ struct X3Piece {
                  "v_fma_mix_f32 %1, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
                  : "+v"(t0), "+v"(t1) : "v"(s), "v"(hs));
   }
-#ifdef DFN_X3_GUARD_MAX3
-  // Kernel variant 12: the guard of a ReLU conversion at one instruction per TWO pieces.  An even piece leaves its unscaled hi pair in
+#ifdef DFN_MLP_LEAN_TU
+  // The lean unit: the guard of a ReLU conversion at one instruction per TWO pieces.  An even piece leaves its unscaled hi pair in
   // `hold` (a register kept until the odd piece's part C, no instruction); the odd piece takes rmax = maximum3(rmax, hold, hb) as packed
   // f16 (v_pk_maximum3_f16).  Why range_report() raises the flag in exactly the launches in which it does after two v_pk_max_u16:
   //   * Both halves of hb come from v_cvt_pkrtz_f16_f32 of t = v_max_f32(acc, 0).  For a finite or +inf t they are non-negative f16
@@ -573,7 +572,7 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
   const int h = st.lane >> 5, g16 = st.lane >> 4;   // g16: lane group of the 16x16 fragments (PrecX3M16)
   uint32_t rmax_sink = 0;
   uint32_t& rmax_ = TRACK ? st.rmax : rmax_sink;
-#ifdef DFN_X3_GUARD_MAX3
+#ifdef DFN_MLP_LEAN_TU
   uint32_t rhold = 0;   // every M-block's eight pieces are converted in order inside one call: nothing is held across calls
 #endif
   const float pscale = P::kSplit ? st.out_scale * st.lane_mul * kX3ActScale : 1.f;  // split-f16 pieces: accumulator -> operand scale
@@ -588,7 +587,7 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
       for (int nb = 0; nb < NB; ++nb) {
         if constexpr (P::kM16) rb[mb][nb] = load_raybias_m16(raybias, mb, g16);
         else rb[mb][nb] = load16(raybias[nb] + (mb * 2 + h) * 16);
-#ifndef DFN_MLP_HOIST_TU   // kernel variant 10: the table holds in_scale x the seeds (ray_bias_kernel<true>)
+#ifndef DFN_MLP_LEAN_TU   // the lean unit: the table holds in_scale x the seeds (ray_bias_kernel<true>)
         if constexpr (P::kSplit) rb[mb][nb] *= st.in_scale;   // accumulators carry in_scale x the true value
 #endif
       }
@@ -632,7 +631,7 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
           for (int nb = 0; nb < NB; ++nb) {
             if constexpr (P::kM16) acc[nb] = RB_ALL ? rb[RB_ALL ? mb : 0][nb] : load_raybias_m16(raybias, mb, g16);
             else acc[nb] = RB_ALL ? rb[RB_ALL ? mb : 0][nb] : load16(raybias[nb] + (mb * 2 + h) * 16);
-#ifndef DFN_MLP_HOIST_TU
+#ifndef DFN_MLP_LEAN_TU
             if constexpr (P::kSplit && !RB_ALL) acc[nb] *= st.in_scale;
 #endif
           }
@@ -809,8 +808,8 @@ DFN_DEV void layer(Stager& st, char* smem, typename FragOf<P>::type (&Bin)[NB][K
 #pragma unroll
               for (int c = 0; c < 8; ++c) {
                 if (HALF && c >= 4) head[nb][c] = 0.f;   // half 1 was not computed (fragments q = nb only)
-#ifdef DFN_MLP_SEL_TU
-                // kernel variant 11: the two candidates behind an opaque copy.  The select of two extractelements of one vector is
+#ifdef DFN_MLP_LEAN_TU
+                // the lean unit: the two candidates behind an opaque copy.  The select of two extractelements of one vector is
                 // otherwise folded into one extract with a lane-dependent index, and an f32x16 in VGPRs has no indexed read: 15
                 // v_cmp_eq_u32 + 16 v_cndmask_b32 per index register, the 15 masks held in SGPR pairs.  This is one v_cndmask_b32.
                 else {
@@ -937,8 +936,8 @@ struct NoTrunkHook {
   template <class A> DFN_DEV void operator()(int, A&) const {}
 };
 // RES_L1 >= 0: layer 1 is LDS-resident at that offset (kernel variant 7's coarse kernel: layer<..., RES>).
-// kEncodingKept: kernel variant 9's translation unit (DFN_MLP_PE_TU), see the skip concat below.
-#ifdef DFN_MLP_PE_TU
+// kEncodingKept: the lean unit (DFN_MLP_LEAN_TU), see the skip concat below.
+#ifdef DFN_MLP_LEAN_TU
 constexpr bool kEncodingKept = true;
 #else
 constexpr bool kEncodingKept = false;
@@ -972,7 +971,7 @@ DFN_DEV void trunk(Stager& st, char* smem, const float (&x)[lane_pts<P>(NB)][3],
     F cat[NB][PC + HC];
     // The skip concat's encoding.  The f16 / split-f16 kernels form it a SECOND time here, from an opaque copy of the coordinates:
     // in the 32x32 kernels (and the f16 one without the pipelined epilogue) 32 more VGPRs live across layers 2 to 4 cost more than
-    // the evaluation.  Kernel variant 9 (kEncodingKept, the 16x16x32 kernels of nerfh_mlp_pe.hip) keeps layer 1's operand instead:
+    // the evaluation.  The lean unit (kEncodingKept, its 16x16x32 kernels) keeps layer 1's operand instead:
     // those kernels have the registers free across layers 2 to 4 and their peak is inside layer 5, where the encoding is an operand
     // in either form.  The pipelined f16 kernel and exact fp32 have always kept it.
     if constexpr (P::kSlotsPerChunk == 8 && (!PIPE || P::kSplit) && !(kEncodingKept && P::kM16)) {

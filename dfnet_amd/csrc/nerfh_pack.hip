@@ -865,7 +865,7 @@ extern "C" int dfn_nerfh_commit(dfn_nerfh_t h) {
     }
     if (hipMemset(h->range_flag, 0, 3 * sizeof(int)) != hipSuccess) return set_error(DFN_ERR_HIP, "dfn_nerfh_commit: clearing the range-guard flag failed");
   }
-  if (!h->tile_counter) {   // kernel variant 8: the tile heads of the coarse and the fine kernel (zeroed in front of every pass that claims from them)
+  if (!h->tile_counter) {   // kernel variant 12: the tile heads of the coarse and the fine kernel (zeroed in front of every pass that claims from them)
     if (hipMalloc(reinterpret_cast<void**>(&h->tile_counter), 2 * sizeof(uint32_t)) != hipSuccess) {
       h->tile_counter = nullptr;
       return set_error(DFN_ERR_HIP, "dfn_nerfh_commit: allocating the tile counters failed");

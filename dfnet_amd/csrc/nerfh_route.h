@@ -15,11 +15,8 @@ enum Launcher {       // nerfh_kernels.h:
   kLaunchFold,        // launch_mlp_fold(maps)
   kLaunchHalf,        // launch_mlp_half(fine, maps)
   kLaunchResident,    // launch_mlp_res
-  kLaunchClaimed,     // launch_mlp_dyn: both tile counters are zeroed in front of a pass in which either kernel takes this route
-  kLaunchKept,        // launch_mlp_pe: claimed tiles as kLaunchClaimed (claims_tiles below)
-  kLaunchHoisted,      // launch_mlp_hoist: kLaunchKept's fine kernel on the per-ray table written at the accumulators' scale (Route::seed_scaled)
-  kLaunchSelected,    // launch_mlp_sel: kLaunchKept's coarse and kLaunchHoisted's fine kernel (the scaled table) with one select per head value
-  kLaunchLean,        // launch_mlp_lean: kLaunchSelected's two kernels with the leaner tile seam and range guard (the scaled table)
+  kLaunchLean,        // launch_mlp_lean: claimed tiles (claims_tiles below); the fine kernel reads the per-ray table written at the
+                      // accumulators' scale (Route::seed_scaled)
   kLaunchPoints,      // launch_mlp_pts
   kLaunchPointsFold,  // launch_mlp_pts_fold
   kLaunchPointsHalf,  // launch_mlp_pts_half
@@ -35,19 +32,17 @@ struct Route {
 };
 
 // the launchers whose kernels claim their tiles: both tile counters are zeroed in front of a pass in which either kernel is one of them
-constexpr bool claims_tiles(Launcher l) { return l == kLaunchClaimed || l == kLaunchKept || l == kLaunchHoisted || l == kLaunchSelected || l == kLaunchLean; }
+constexpr bool claims_tiles(Launcher l) { return l == kLaunchLean; }
 
 // Netwidth 256 has one kernel per arithmetic: variant 0.  Variants 5 to 12 differ from their base in split-f16 only.
 constexpr VariantFacts route_facts(int variant, int width) { return kVariantFacts[width == kWidth ? variant : 0]; }
 
-// points: the point queries (dfn_mlp_*_points, called with kDefaultVariant); they have no resident / claimed flavour and run variant 6's
+// points: the point queries (dfn_mlp_*_points, called with kPointsVariant); they have no resident / lean flavour and run variant 6's
 constexpr Route coarse_route(int variant, int width, int prec, bool points = false) {
   const VariantFacts f = route_facts(variant, width);
   const bool x3 = prec == kPrecF16X3;
   if (x3 && f.lean && !points) return {kLaunchLean, kResidentVariant, f.base, false, false};
-  if (x3 && f.sel && !points) return {kLaunchSelected, kResidentVariant, f.base, false, false};
-  if (x3 && f.kept && !points) return {kLaunchKept, kResidentVariant, f.base, false, false};
-  if (x3 && f.resident && !points) return {f.claimed ? kLaunchClaimed : kLaunchResident, kResidentVariant, f.base, false, false};
+  if (x3 && f.resident && !points) return {kLaunchResident, kResidentVariant, f.base, false, false};
   if (x3 && f.half) return {points ? kLaunchPointsHalf : kLaunchHalf, kHalfVariant, f.base, false, false};
   return {points ? kLaunchPoints : kLaunchPlain, f.base, f.base, false, false};
 }
@@ -56,10 +51,7 @@ constexpr Route fine_route(int variant, int width, int prec, bool fused, bool wa
   const VariantFacts f = route_facts(variant, width);
   const bool x3 = prec == kPrecF16X3, maps = fused && want_maps;
   if (x3 && f.lean && fused && !want_maps) return {kLaunchLean, kResidentVariant, f.base, true, false, true};
-  if (x3 && f.sel && fused && !want_maps) return {kLaunchSelected, kResidentVariant, f.base, true, false, true};
-  if (x3 && f.hoisted && fused && !want_maps) return {kLaunchHoisted, kResidentVariant, f.base, true, false, true};
-  if (x3 && f.kept && fused && !want_maps) return {kLaunchKept, kResidentVariant, f.base, true, false};
-  if (x3 && f.resident && fused && !want_maps) return {f.claimed ? kLaunchClaimed : kLaunchResident, kResidentVariant, f.base, true, false};
+  if (x3 && f.resident && fused && !want_maps) return {kLaunchResident, kResidentVariant, f.base, true, false};
   if (x3 && f.half && fused) return {kLaunchHalf, want_maps ? kNetHalfMaps : kHalfVariant, f.base, true, want_maps};
   if (x3 && f.fold) return {points ? kLaunchPointsFold : kLaunchFold, kFoldVariant, f.base, true, maps};
   return {points ? kLaunchPoints : (maps ? kLaunchMaps : kLaunchPlain), f.base, f.base, false, maps};
@@ -114,50 +106,40 @@ static_assert(plain_as(7, W, H, 4) && plain_as(7, W, F, 4) && plain_all(7, W2, 0
 static_assert(is(coarse_route(7, W, X), kLaunchResident, 7, 4), "variant 7 coarse");
 static_assert(raw_is_fold(7) && is(fine_route(7, W, X, true, false), kLaunchResident, 7, 4, true) &&
               is(fine_route(7, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 7 fine");
-// variant 8: variant 7 with launch_mlp_dyn where variant 7 has launch_mlp_res, on variant 7's networks
-static_assert(plain_as(8, W, H, 4) && plain_as(8, W, F, 4) && plain_all(8, W2, 0), "variant 8 outside split-f16");
-static_assert(is(coarse_route(8, W, X), kLaunchClaimed, 7, 4), "variant 8 coarse");
-static_assert(raw_is_fold(8) && is(fine_route(8, W, X, true, false), kLaunchClaimed, 7, 4, true) &&
-              is(fine_route(8, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 8 fine");
-// variant 9: variant 8 with launch_mlp_pe where variant 8 has launch_mlp_dyn, on variant 7's networks; everything else variant 8's
-static_assert(plain_as(9, W, H, 4) && plain_as(9, W, F, 4) && plain_all(9, W2, 0), "variant 9 outside split-f16");
-static_assert(is(coarse_route(9, W, X), kLaunchKept, 7, 4), "variant 9 coarse");
-static_assert(raw_is_fold(9) && is(fine_route(9, W, X, true, false), kLaunchKept, 7, 4, true) &&
-              is(fine_route(9, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 9 fine");
-static_assert(is(coarse_route(9, W, X, true), kLaunchPointsHalf, 6, 4) && is(fine_route(9, W, X, false, false, true), kLaunchPointsFold, 5, 4, true),
-              "variant 9 points");
-// variant 10: variant 9 with launch_mlp_hoist and the scaled table in the plain fused fine kernel, and there alone: the coarse kernel is
-// variant 9's, and the maps flavour, the raw route and the point queries read the unscaled table as under variant 9
-static_assert(plain_as(10, W, H, 4) && plain_as(10, W, F, 4) && plain_all(10, W2, 0), "variant 10 outside split-f16");
-static_assert(is(coarse_route(10, W, X), kLaunchKept, 7, 4), "variant 10 coarse");
-static_assert(raw_is_fold(10) && is(fine_route(10, W, X, true, false), kLaunchHoisted, 7, 4, true, false, true) &&
-              is(fine_route(10, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 10 fine");
-static_assert(is(coarse_route(10, W, X, true), kLaunchPointsHalf, 6, 4) && is(fine_route(10, W, X, false, false, true), kLaunchPointsFold, 5, 4, true),
-              "variant 10 points");
-// variant 11: variant 10 with launch_mlp_sel in the coarse kernel and in the plain fused fine kernel (the scaled table, as variant 10's);
-// the maps flavour, the raw route and the point queries as under variant 9
-static_assert(plain_as(11, W, H, 4) && plain_as(11, W, F, 4) && plain_all(11, W2, 0), "variant 11 outside split-f16");
-static_assert(is(coarse_route(11, W, X), kLaunchSelected, 7, 4), "variant 11 coarse");
-static_assert(raw_is_fold(11) && is(fine_route(11, W, X, true, false), kLaunchSelected, 7, 4, true, false, true) &&
-              is(fine_route(11, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 11 fine");
-static_assert(is(coarse_route(11, W, X, true), kLaunchPointsHalf, 6, 4) && is(fine_route(11, W, X, false, false, true), kLaunchPointsFold, 5, 4, true),
-              "variant 11 points");
-// variant 12: variant 11 with launch_mlp_lean where variant 11 has launch_mlp_sel (the scaled table in the fine kernel); the maps flavour,
-// the raw route and the point queries as under variant 9
+// variants 8 to 11 are retired and mean variant 12: every route of theirs is the corresponding route of 12 -- coarse, fine raw and
+// fused, each with and without maps, and the point queries, in all three arithmetics and at both widths
+// (same_routes walks every combination of its arguments, a superset of the routes a caller forms: fused with points, or maps without
+// fused, reach no entry point)
+constexpr bool same(const Route& a, const Route& b) { return is(a, b.launcher, b.net, b.variant, b.fold_table, b.maps, b.seed_scaled); }
+constexpr bool same_routes(int v, int u) {
+  const int widths[] = {W, W2}, precs[] = {H, F, X};
+  for (int w : widths)
+    for (int p : precs)
+      for (int points = 0; points < 2; ++points) {
+        if (!same(coarse_route(v, w, p, points), coarse_route(u, w, p, points))) return false;
+        for (int fused = 0; fused < 2; ++fused)
+          for (int maps = 0; maps < 2; ++maps)
+            if (!same(fine_route(v, w, p, fused, maps, points), fine_route(u, w, p, fused, maps, points))) return false;
+      }
+  return true;
+}
+static_assert(same_routes(8, 12), "variant 8");
+static_assert(same_routes(9, 12), "variant 9");
+static_assert(same_routes(10, 12), "variant 10");
+static_assert(same_routes(11, 12), "variant 11");
+// variant 12: variant 7 with launch_mlp_lean where variant 7 has launch_mlp_res (and the scaled table in the fine kernel); the maps
+// flavour, the raw route and the point queries as under variant 7
 static_assert(plain_as(12, W, H, 4) && plain_as(12, W, F, 4) && plain_all(12, W2, 0), "variant 12 outside split-f16");
 static_assert(is(coarse_route(12, W, X), kLaunchLean, 7, 4), "variant 12 coarse");
 static_assert(raw_is_fold(12) && is(fine_route(12, W, X, true, false), kLaunchLean, 7, 4, true, false, true) &&
               is(fine_route(12, W, X, true, true), kLaunchHalf, HM, 4, true, true), "variant 12 fine");
 static_assert(is(coarse_route(12, W, X, true), kLaunchPointsHalf, 6, 4) && is(fine_route(12, W, X, false, false, true), kLaunchPointsFold, 5, 4, true),
               "variant 12 points");
-static_assert(claims_tiles(kLaunchClaimed) && claims_tiles(kLaunchKept) && claims_tiles(kLaunchHoisted) && claims_tiles(kLaunchSelected) &&
-              claims_tiles(kLaunchLean) &&
-              !claims_tiles(kLaunchResident),
-              "who claims tiles");
+static_assert(claims_tiles(kLaunchLean) && !claims_tiles(kLaunchResident), "who claims tiles");
 // the coarse pass of a split-f16 render under DFN_RENDER_COARSE_F16 is the f16 route: variant 0's kernel on net[0][F16][4]
 static_assert(is(coarse_route(kSelectedByDefault, W, H), kLaunchPlain, 4, 4), "f16 coarse pass");
-// point queries: the default variant's kernels -- split-f16 at netwidth 128 variant 6's coarse and variant 5's fine (raw) kernel
-static_assert(kDefaultVariant == 7 && is(coarse_route(7, W, X, true), kLaunchPointsHalf, 6, 4) &&
+// point queries: kPointsVariant's routes (variant 7's, whatever DFN_MLP_VARIANT says) -- split-f16 at netwidth 128 variant 6's coarse and variant 5's fine (raw) kernel
+static_assert(kPointsVariant == 7 && is(coarse_route(7, W, X, true), kLaunchPointsHalf, 6, 4) &&
               is(fine_route(7, W, X, false, false, true), kLaunchPointsFold, 5, 4, true), "split-f16 points");
 static_assert(is(coarse_route(7, W, H, true), kLaunchPoints, 4, 4) && is(fine_route(7, W, F, false, false, true), kLaunchPoints, 4, 4) &&
               is(coarse_route(7, W2, X, true), kLaunchPoints, 0, 0) && is(fine_route(7, W2, X, false, false, true), kLaunchPoints, 0, 0),

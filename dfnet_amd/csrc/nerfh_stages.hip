@@ -208,7 +208,7 @@ hipError_t launch_posenc(const float* x, size_t n, int L, int mode, float* out, 
 // table[ray][0] = b_dir + W_dir[:, W:] . [pe_dir(viewdir) (27), a (hist_bin*dim_a)]     (nout = netwidth / 2 outputs)
 // table[ray][1] = b_tr  + W_tr [:, W:] . t (hist_bin*dim_t)
 // stored in C-fragment order [tbl][mb][h][r] so the fine kernel's accumulators load it directly.
-// SCALED: every entry is stored multiplied by `scale` (kernel variant 10: the split-f16 accumulators carry in_scale x the value, and
+// SCALED: every entry is stored multiplied by `scale` (kernel variant 12: the split-f16 accumulators carry in_scale x the value, and
 // the product by that power of two is formed here once per ray instead of on every tile that loads the entry).  An instantiation of
 // its own: without it `scale` is not read and the code is the kernel's of before.
 template <bool SCALED>

@@ -371,8 +371,9 @@ int dfn_mlp_fine_backward_saved(dfn_nerfh_t h, int prec, const float* rays_o, co
  * (nerfw.py:425-434): each of the n_rows rows of N points has ONE view direction and ONE appearance / transient histogram, as
  * run_network_NeRFW repeats viewdirs[:, None] and ts over the samples of a row.  The kernels are those of dfn_mlp_coarse /
  * dfn_mlp_fine / dfn_mlp_fine_backward behind the three inputs of a point: a point equal to fl(o + fl(d z)) gives the bits the ray
- * entry gives at the default kernel variant.  Under another DFN_MLP_VARIANT these entries still run the default variant's kernels (the
- * variants are an A/B aid of the render path).  Netwidth 128 and 256 (a generic width: DFN_ERR_UNSUPPORTED); n_rows == 0 is DFN_OK;
+ * entry gives under kernel variant 7.  Whatever DFN_MLP_VARIANT says, these entries run variant 7's routes (kPointsVariant; the
+ * variants are an A/B aid of the render path: 0 to 7 and 12; 8 to 11 are retired, stay accepted and mean 12 -- the same outputs bit
+ * for bit, at variant 12's speed).  Netwidth 128 and 256 (a generic width: DFN_ERR_UNSUPPORTED); n_rows == 0 is DFN_OK;
  * n_rows * N must stay below 2^31 (the host chunks by rows).
  * dfn_mlp_coarse_points: nerfw.py:37-46 (test-time coarse query) -> sigma [n_rows, N].
  * dfn_mlp_fine_points: nerfw.py:62-95 -> raw [n_rows, N, 9]; viewdirs [n_rows, 3], hist [hist_rows, hist_bin] with hist_rows 1 or

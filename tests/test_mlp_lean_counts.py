@@ -1,15 +1,18 @@
 """Static counts of kernel variant 12's text (nerfh_mlp_lean.hip), through tools/mfma_free_valu.py and tools/mfma_read_distance.py.
 
-No GPU: the unit is cross-compiled for gfx950 to assembly, once for this file, in the manner of tests/test_mlp_seam_counts.py (whose
-helpers this file takes over in its own words: that file compiles nerfh_mlp_sel.hip and stays as it is).  The bounds were set before
-the first GPU run from variant 11's counts (3 754 vector instructions in the fine kernel, 2 707 in the coarse one) and what each
-part of the variant as specified takes out: the packed head activations and the paired range guard alone give 3 458 in the fine
-kernel, the paired guard alone 2 579 in the coarse one; v_rcp_iflag_f32 is the reciprocal of the 32-bit division by n_samples, and
-v_pk_max_u16 the range guard's old instruction, 336 / 256 per tile in variant 11.  A build that misses a bound has not removed what
-the variant was specified to remove.
+No GPU: the unit is cross-compiled for gfx950 to assembly, once for this file.  The bounds were set before the first GPU run of each
+technique from the counts of the unit without it and what the technique as specified takes out.  A build that misses a bound has not
+removed what the unit was specified to remove:
+  * one select per head value: a build in which the 16-way select chains of the PrecX3M16 head extraction are gone had 125 v_cndmask +
+    v_cmp in the fine kernel, the bound is that plus about 1 % of the kernel's vector instructions; with the chains it had 294, and
+    39 SGPRs parked in VGPR lanes (v_writelane_b32: none may remain);
+  * the lean seam and guard: 3 754 vector instructions in the fine kernel and 2 707 in the coarse one before them; the packed head
+    activations and the paired range guard alone give 3 458 in the fine kernel, the paired guard alone 2 579 in the coarse one;
+    v_rcp_iflag_f32 is the reciprocal of the 32-bit division by n_samples, and v_pk_max_u16 the range guard's old instruction, 336 /
+    256 per tile before.
 
 As shipped: fine 3 414, coarse 2 556; no v_rcp_iflag_f32; v_pk_max_u16 0 / 0 (v_pk_maximum3_f16 168 / 128); VGPRs 250 / 228; MFMAs
-1 920 / 1 560; read distance 6 / 6; eight v_permlane32_swap_b32 in the fine kernel.
+1 920 / 1 560; read distance 6 / 6; eight v_permlane32_swap_b32 in the fine kernel; v_cndmask + v_cmp 60 + 31 / 36 + 24; no v_writelane_b32.
 """
 import os
 import re
@@ -96,6 +99,12 @@ def built(tmp_path_factory):
 @pytest.mark.parametrize("kind,valu", (("fine", 3480), ("coarse", 2590)))
 def test_vector_instructions(built, kind, valu):
     assert built[kind]["valu"] <= valu, built[kind]["valu"]
+
+
+def test_the_select_chains_are_gone(built):
+    f = built["fine"]
+    assert f["writelane"] == 0
+    assert f["cndmask"] + f["cmp"] <= 140, (f["cndmask"], f["cmp"])
 
 
 @pytest.mark.parametrize("kind", ("fine", "coarse"))
